@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """WKV6 fwd+bwd micro-benchmark on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload wkv6|infctx|bi|dp_lora|prefill] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload wkv6|infctx|bi|dp_lora|prefill] [--full] [--no-cpu]
+                    [--dump-outputs DIR]
+
+A plain run does what the headline figure needs: it sets up, pre-warms, runs the W warm-up and the K timed steps and prints the
+result line (roofline.traffic then comes from the committed PMC file and says so).  --full adds the measurements that take runs
+of their own: roofline.traffic measured live under rocprofv3 (N = 1) and the CPU baseline.  --dump-outputs DIR writes what the
+last timed step computed (dump_outputs).
 
 One "step" = one forward + one backward of the WKV6 operator through the C ABI of librwkv6_amd.so on one
 batch of synthetic bf16 inputs that already live in HBM (BASELINE.json configs[1]: B=8, T=4096, C=2048,
@@ -279,6 +285,7 @@ def bench_dp_lora(args, rank, world, dev, dist):
     # the rank's batches, dealt by the sampler, staged in pinned host memory ahead of the timed region
     it = iter([{k: v.pin_memory() for k, v in b.items()} for b in train_dp.batches(sampler, T, vocab)])
     model.train()
+    last = {}
 
     def step():
         batch = {k: v.to(dev, non_blocking=True) for k, v in next(it).items()}
@@ -286,10 +293,19 @@ def bench_dp_lora(args, rank, world, dev, dist):
         loss = train_dp.training_loss(net, batch["query"], batch["positive"], batch["negative"])
         loss.backward()                             # DDP all-reduces the LoRA / dense gradients here
         opt.step()
+        last["loss"] = loss.detach()
 
     step()                                          # allocator / module-load warm-up, outside the W warm-up steps
     torch.cuda.synchronize()
     elapsed = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, dist, dev)
+    if rank == 0 and args.dump_outputs:
+        # the step's loss, and the trainable parameters after the optimizer step and their (all-reduced) gradients, flattened in
+        # parameters() order
+        trained = train_dp.trainable_parameters(model)
+        dump_outputs(args.dump_outputs, {"loss": last["loss"].reshape(1),
+                                         "trainable_params": torch.cat([p.detach().float().reshape(-1) for p in trained]),
+                                         "trainable_grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p))
+                                                                       .float().reshape(-1) for p in trained])})
     if rank == 0:
         tokens = 3 * bs * T                         # per GPU and step
         emit(({
@@ -355,8 +371,36 @@ def timed_launch_clocks(clocks, side, steps, launches_per_pass, what="ghz"):
     return [round(x / launches_per_pass, 3) for x in per] if what == "ghz" else [round(x * 1e-3, 4) for x in per]
 
 
+DUMP_MAX_BYTES = 60 * 2 ** 20      # --dump-outputs: at most this many bytes of float32 in all (< 64 MB)
+DUMP_WHOLE_ELEMS = 2 ** 18         # arrays up to this size are written whole, larger ones as a fixed sample
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: `arrays` (name -> tensor, what a caller of the timed path received in its last step) as out_dir/<name>.npy,
+    float32 (the outputs are bf16 or fp32: exact).  Arrays of at most DUMP_WHOLE_ELEMS elements are written whole; the larger ones share
+    what is left of DUMP_MAX_BYTES equally, each as a sample of its flattened elements at sorted positions drawn from a CPU generator
+    seeded with `seed`, so that two runs with the same arguments write the same positions.  Returns {name: [shape, elements written]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {n: t.detach() for n, t in arrays.items() if t is not None}
+    small = {n for n, t in arrays.items() if t.numel() <= DUMP_WHOLE_ELEMS}
+    left = DUMP_MAX_BYTES // 4 - sum(arrays[n].numel() for n in small)
+    per_large = left // max(1, len(arrays) - len(small))
+    g = torch.Generator().manual_seed(seed)
+    written = {}
+    for n, t in arrays.items():
+        out = t
+        if n not in small and t.numel() > per_large:
+            pos = torch.randint(t.numel(), (per_large,), generator=g).sort().values
+            out = t.reshape(-1)[pos.to(t.device)]
+        np.save(os.path.join(out_dir, n + ".npy"), out.float().cpu().numpy())
+        written[n] = [list(t.shape), int(out.numel())]
+    return written
+
+
 def build_workload(workload, dev, seed=0):
-    """(fwd, bwd, tokens, B, T, H, name) of one of the operator-level workloads: closures over synthetic inputs resident in HBM."""
+    """(fwd, bwd, tokens, B, T, H, name, outputs) of one of the operator-level workloads: closures over synthetic inputs resident in HBM;
+    outputs() returns what the last fwd + bwd handed back to their caller (name -> tensor), for --dump-outputs."""
     from rwkv_lm_ext_amd import wkv6_op
     if workload == "wkv6":
         B, T, H = 8, 4096, 32
@@ -373,6 +417,8 @@ def build_workload(workload, dev, seed=0):
     C = H * 64
     r, k, v, w, u, gy = synth(B, T, H, dev, seed=seed)
     tokens = B * T
+    last = {}               # what the latest fwd / bwd returned (kept from the first call on: no allocation pattern of its own in the timed steps)
+    grads = ("gr", "gk", "gv", "gw", "gu")
 
     if workload == "wkv6":
         y = torch.empty_like(r)
@@ -382,7 +428,10 @@ def build_workload(workload, dev, seed=0):
             wkv6_op.forward_ex(r, k, v, w, u, H, y=y, ckpt=ckpt)
 
         def bwd():
-            wkv6_op.backward_ex(r, k, v, w, u, gy, H, ckpt=ckpt)
+            last["bwd"] = wkv6_op.backward_ex(r, k, v, w, u, gy, H, ckpt=ckpt)
+
+        def outputs():
+            return {"y": y, **dict(zip(grads, last["bwd"]))}
     elif workload == "prefill":
         y = torch.empty_like(r)
 
@@ -391,19 +440,29 @@ def build_workload(workload, dev, seed=0):
 
         def bwd():
             pass
+
+        def outputs():
+            return {"y": y}
     elif workload == "infctx":
         chunks = [slice(2048 * c, 2048 * (c + 1)) for c in range(8)]
         parts = [[x[:, sl].contiguous() for x in (r, k, v, w, gy)] for sl in chunks]
         states = [torch.zeros(B, H, 64, 64, device=dev, dtype=torch.bfloat16) for _ in range(9)]
         ckpts = [wkv6_op.new_checkpoint(B, 2048, C, H, dev) for _ in range(8)]   # as WKV_6STATE_INFCTX keeps them
+        last["fwd"], last["bwd"] = [None] * 8, [None] * 8
 
         def fwd():
             for c, (rc, kc, vc, wc, _) in enumerate(parts):
-                wkv6_op.forward_ex(rc, kc, vc, wc, u, H, s0=states[c], s_out=states[c + 1], ckpt=ckpts[c])
+                last["fwd"][c] = wkv6_op.forward_ex(rc, kc, vc, wc, u, H, s0=states[c], s_out=states[c + 1], ckpt=ckpts[c])
 
         def bwd():      # truncated BPTT as the reference trains it: each chunk's backward from its entry state
             for c, (rc, kc, vc, wc, gc) in enumerate(parts):
-                wkv6_op.backward_ex(rc, kc, vc, wc, u, gc, H, s0=states[c], want_gs=True, ckpt=ckpts[c])
+                last["bwd"][c] = wkv6_op.backward_ex(rc, kc, vc, wc, u, gc, H, s0=states[c], want_gs=True, ckpt=ckpts[c])
+
+        def outputs():  # the chunks' y and gradients joined along T; per-chunk exit states, gu and gs stacked chunk-major
+            per = list(zip(*last["bwd"]))
+            return {"y": torch.cat(last["fwd"], 1), "s_out": torch.stack(states[1:]),
+                    **{n: torch.cat(per[i], 1) for i, n in enumerate(grads[:4])},
+                    "gu": torch.stack(per[4]), "gs": torch.stack(per[5])}
     else:
         g = torch.Generator(device=dev).manual_seed(1)
         lens = torch.randint(64, 513, (B,), device=dev, generator=g)
@@ -413,12 +472,15 @@ def build_workload(workload, dev, seed=0):
         bi_ws = wkv6_op.bi_new_workspace(B, T, C, H, dev)      # as WKV_6_BI keeps it from forward to backward
 
         def fwd():
-            wkv6_op.bi_forward_ex(mask, r, k, v, w, u, H, ws=bi_ws)
+            last["fwd"] = wkv6_op.bi_forward_ex(mask, r, k, v, w, u, H, ws=bi_ws)
 
         def bwd():
-            wkv6_op.bi_backward_ex(mask, r, k, v, w, u, gy, H, ws=bi_ws)
+            last["bwd"] = wkv6_op.bi_backward_ex(mask, r, k, v, w, u, gy, H, ws=bi_ws)
 
-    return fwd, bwd, tokens, B, T, H, name
+        def outputs():
+            return {"y": last["fwd"], **dict(zip(grads, last["bwd"]))}
+
+    return fwd, bwd, tokens, B, T, H, name, outputs
 
 
 def main():
@@ -427,15 +489,31 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="wkv6", choices=["wkv6", "infctx", "bi", "dp_lora", "prefill"])
-    ap.add_argument("--traffic", default="live", choices=["live", "file", "none"],
-                    help="roofline.traffic of the headline workload: measured now under rocprofv3 (N = 1), from the committed PMC file, or omitted")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline.traffic live under rocprofv3 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--traffic", default=None, choices=["live", "file", "none"],
+                    help="roofline.traffic of the headline workload: measured now under rocprofv3 (N = 1), from the committed PMC file, or "
+                         "omitted (default: live with --full, file without)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg of --full")
     ap.add_argument("--spawn", action="store_true",
                     help="start the ranks through torch.distributed.run also at --gpus 1 (the self-launch of `--gpus N`, on the box that exists)")
     ap.add_argument("--layers", type=int, default=24, help="dp_lora: number of RWKV blocks (1B6: 24)")
     ap.add_argument("--per-gpu-batch", type=int, default=32, help="dp_lora: triples per GPU and step")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "file"
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    from rwkv_lm_ext_amd import _build
+    if not _build.needs_build():
+        # the library build() made is current: load it as it is, without the build lock, so that the benchmark needs no write access
+        # to the tree (it may be run by another user than the one who built it); the ranks and profiled children inherit this
+        os.environ.setdefault("RWKV_AMD_NO_BUILD", "1")
     if args.pmc_child:
         return pmc_child(args.workload)
 
@@ -479,7 +557,7 @@ def main():
 
     if args.workload == "dp_lora":
         return bench_dp_lora(args, rank, world, dev, dist)
-    fwd, bwd, tokens, B, T, H, name = build_workload(args.workload, dev, seed=rank)
+    fwd, bwd, tokens, B, T, H, name, outputs = build_workload(args.workload, dev, seed=rank)
     C = H * 64
 
     from rwkv_lm_ext_amd.dp import hold_until_all_ranks_ready, timed_steps
@@ -532,6 +610,8 @@ def main():
             wkv6_op.pass_marker()
         clocks = probe.read()
     gc.enable()
+    if rank == 0 and args.dump_outputs:
+        print("bench.py: wrote", json.dumps(dump_outputs(args.dump_outputs, outputs())), "to", args.dump_outputs, file=sys.stderr)
     fwd_steps = [ev[i][0].elapsed_time(ev[i][1]) for i in range(args.steps)]
     bwd_steps = [ev[i][1].elapsed_time(ev[i + 1][0]) for i in range(args.steps)]
     fwd_ms = sum(fwd_steps) / args.steps
@@ -618,7 +698,7 @@ def main():
                               "traffic": (pmc["_pass_fwd"]["hbm_bytes"] + pmc.get("_pass_bwd", {}).get("hbm_bytes", 0))
                               if pmc.get("_pass_fwd") else None},
         }
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline()
         emit(out)
     if dist is not None:

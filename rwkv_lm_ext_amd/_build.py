@@ -35,6 +35,8 @@ def build(force=False, verbose=False):
     half-written file."""
     import fcntl
     import tempfile
+    if not force and not needs_build():
+        return LIB_PATH         # current: nothing to write, so no lock file either (a tree built by another user, or read-only, loads)
     with open(LIB_PATH + ".lock", "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:

@@ -95,3 +95,26 @@ def test_round6_bench_line_proves_its_steady_state():
         timed = {("fwd" if "chunk_fwd_kernel" in r["Name"] else "bwd"): float(r["AverageNs"]) * 1e-6
                  for r in csv.DictReader(fh) if r["Scope"].startswith("timed") and ("chunk_fwd_kernel" in r["Name"] or "chunk_bwd12k_kernel" in r["Name"])}
     assert abs(timed["fwd"] / c["fwd_ms"] - 1.0) < 0.03 and abs(timed["bwd"] / c["bwd_ms"] - 1.0) < 0.03, (timed, c["fwd_ms"], c["bwd_ms"])
+
+
+def test_dump_outputs_stays_in_budget_and_repeats(tmp_path, monkeypatch):
+    """--dump-outputs: small arrays whole and in their shape, large ones as the same seeded sample on every run, float32, within the
+    byte budget in all; a None output (no gs at the headline workload) is not written."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 6000)
+    monkeypatch.setattr(bench, "DUMP_WHOLE_ELEMS", 1000)
+    g = torch.Generator().manual_seed(1)
+    arrays = {"y": torch.randn(4, 256, 16, generator=g).to(torch.bfloat16), "gr": torch.randn(4, 256, 16, generator=g),
+              "gu": torch.randn(4, 16, generator=g), "gs": None}
+    written = [bench.dump_outputs(str(tmp_path / d), arrays) for d in ("a", "b")]
+    assert written[0] == written[1] == {"y": [[4, 256, 16], 2968], "gr": [[4, 256, 16], 2968], "gu": [[4, 16], 64]}
+    assert sorted(os.listdir(tmp_path / "a")) == ["gr.npy", "gu.npy", "y.npy"]
+    total = 0
+    for n in ("y", "gr", "gu"):
+        a, b = (np.load(tmp_path / d / (n + ".npy")) for d in ("a", "b"))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 4 * 6000
+    assert np.array_equal(np.load(tmp_path / "a" / "gu.npy"), arrays["gu"].numpy())
+    assert set(np.load(tmp_path / "a" / "y.npy").tolist()) <= set(arrays["y"].float().reshape(-1).tolist())

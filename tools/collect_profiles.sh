@@ -20,9 +20,9 @@ done
 # kernel-trace statistics and bench lines of the other single-GPU workloads (BASELINE configs[2], [4])
 for wl in bi infctx; do
     rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/stats_$wl" -- python3 $ROOT/bench.py --workload $wl --steps 20 --warmup 5 --no-cpu > "$ROOT/$OUT/stats_$wl.log" 2>&1 || echo "stats $wl failed"
-    python3 $ROOT/bench.py --workload $wl --steps 20 --warmup 5 --no-cpu > "$ROOT/$OUT/bench_$wl.json" 2> /dev/null
+    python3 $ROOT/bench.py --workload $wl --steps 20 --warmup 5 --full --no-cpu > "$ROOT/$OUT/bench_$wl.json" 2> /dev/null
 done
-python3 $ROOT/bench.py --workload prefill --steps 20 --warmup 5 --no-cpu > "$ROOT/$OUT/bench_prefill.json" 2> /dev/null
+python3 $ROOT/bench.py --workload prefill --steps 20 --warmup 5 --full --no-cpu > "$ROOT/$OUT/bench_prefill.json" 2> /dev/null
 python3 $ROOT/bench.py --workload dp_lora --steps 10 --warmup 3 > "$ROOT/$OUT/bench_dp_lora.json" 2> "$ROOT/$OUT/bench_dp_lora.err" || echo "dp_lora failed"   # configs[3], 24 layers, one GPU (DDP over a one-rank RCCL group)
-python3 $ROOT/bench.py --steps 100 --warmup 20 > "$ROOT/$OUT/bench_wkv6.json" 2> "$ROOT/$OUT/bench_wkv6.err"           # traffic measured live
+python3 $ROOT/bench.py --steps 100 --warmup 20 --full > "$ROOT/$OUT/bench_wkv6.json" 2> "$ROOT/$OUT/bench_wkv6.err"    # traffic measured live, CPU baseline
 echo done
