@@ -227,14 +227,19 @@ int wkv6_selftest(void* stream);
  * the in-kernel shader clock of a launch is d(s_memtime) / d(s_memrealtime) x 100 MHz (MI355X_MICROARCH.md, DVFS give-back item 6), its
  * duration max(end s_memrealtime) - min(start s_memrealtime) over the slots.  buf = NULL (the default) switches it off: the kernels
  * then execute one scalar branch for it and no stamp.  Process-wide; the caller keeps `buf` alive until it has switched the probe off.
- * wkv6_set_clock_buffer(buf, n_slots) = wkv6_set_clock_ring(buf, n_slots, 1): every launch overwrites the one before it.
  * wkv6_clock_ring_counts: chunked forward / backward launches since the ring was set.
  * wkv6_pass_marker: launches an empty kernel named wkv6::pass_marker_kernel on `stream`: a phase boundary in a profiler's
- * dispatch list. */
+ * dispatch list.
+ * wkv6_set_dispatch: overrides one of the library's launch-shape choices, process-wide (tests and A/Bs reach every mode with it).
+ * WKV6_DISPATCH_SPLIT: != 0 forces two workgroups per (batch, head), 0 forces one.
+ * WKV6_DISPATCH_BI_FUSED: 0 runs the two halves of wkv6_bi as two launches, any other value leaves the choice to the library.
+ * WKV6_DISPATCH_TSPLIT: 0 or 1 turns the two-level forward over T off, n forces n segments where T % (64 n) == 0 (off otherwise). */
 void wkv6_set_clock_ring(void* buf, int n_slots, int n_launches);
-void wkv6_set_clock_buffer(void* buf, int n_slots);
 void wkv6_clock_ring_counts(long* fwd, long* bwd);
 int wkv6_pass_marker(void* stream);
+enum { WKV6_DISPATCH_SPLIT = 0, WKV6_DISPATCH_BI_FUSED = 1, WKV6_DISPATCH_TSPLIT = 2 };
+/* value -1: the library's own choice (default).  Returns the previous value, or WKV6_EINVAL for an unknown selector. */
+int wkv6_set_dispatch(int what, int value);
 /* "major.minor" of the library. */
 const char* wkv6_amd_version(void);
 

@@ -2,12 +2,63 @@
 #include "../../include/wkv6_amd.h"
 #include "wkv6_scan.h"
 
+#include <atomic>
 #include <mutex>
 #include <vector>
 #include <cstring>
 #include <cmath>
 
 using namespace wkv6;
+
+// ---- launch-shape policy (host side): how many workgroups the chunked kernels run on.  The library's rules decide from the shape and
+// the device's CU count; wkv6_set_dispatch() (include/wkv6_amd.h) overrides them, so that tests can reach every mode at small shapes.
+namespace wkv6 {
+namespace {
+std::atomic<int> g_dispatch[3] = {-1, -1, -1};    // by WKV6_DISPATCH_*; -1: the library's own choice
+int dispatch_override(int what) { return g_dispatch[what].load(std::memory_order_relaxed); }
+}  // namespace
+
+int cu_count()              // compute units of the current device (0: unknown)
+{
+    static int cus[16] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
+    if (!cus[dev]) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+        cus[dev] = prop.multiProcessorCount;
+    }
+    return cus[dev];
+}
+// two workgroups per (batch, head) when one each would leave at least half of the CUs without work
+int want_split(int BH)
+{
+    if (const int o = dispatch_override(WKV6_DISPATCH_SPLIT); o != -1) return o != 0;
+    return 2 * BH <= cu_count();
+}
+// workgroup slots of the persistent wkv6_bi launches: one per CU at most (0: the halves run as two launches)
+int bi_slots(int BH)
+{
+    if (want_split(BH)) return 0;
+    if (dispatch_override(WKV6_DISPATCH_BI_FUSED) == 0) return 0;
+    const int cus = cu_count();
+    return cus > 0 ? (BH < cus ? BH : cus) : 0;
+}
+// segments of the two-level forward over T (1: one pass)
+int tsplit_segments(const ScanArgs& a)
+{
+    if (a.lens || a.reverse || a.rev_n || a.order || a.accumulate || a.y_f32 || a.zero_tail || a.dsum || a.gn_out) return 1;
+    if (a.g_f32[0] || a.g_f32[1] || a.g_f32[2] || a.g_f32[3]) return 1;
+    if (const int want = dispatch_override(WKV6_DISPATCH_TSPLIT); want != -1) {   // 0 / 1 = off, n = exactly n segments (if T divides)
+        if (want <= 1) return 1;
+        return a.T % (64 * want) == 0 ? want : 1;
+    }
+    const int cus = cu_count();
+    int S = 1;
+    while (2 * S <= 16 && (long)a.B * a.H * 2 * S <= cus && a.T % (64 * 2 * S) == 0 && a.T / (2 * S) >= 512) S *= 2;
+    return S >= 4 ? S : 1;      // two segments do not pay for the extra state pass (two workgroups per pair serve that case)
+}
+}  // namespace wkv6
 
 namespace {
 
@@ -139,21 +190,6 @@ __global__ void tsplit_combine_kernel(const void* s0, int s_f32, long s0_bstride
     }
 }
 
-int tsplit_segments(const ScanArgs& a)
-{
-    if (a.lens || a.reverse || a.rev_n || a.order || a.accumulate || a.y_f32 || a.zero_tail || a.dsum || a.gn_out) return 1;
-    if (a.g_f32[0] || a.g_f32[1] || a.g_f32[2] || a.g_f32[3]) return 1;
-    int want = 0;
-    if (const char* e = getenv("WKV6_TSPLIT")) {       // A/B switch: 0 / 1 = off, n = exactly n segments (if T divides)
-        want = atoi(e);
-        if (want <= 1) return 1;
-        return a.T % (64 * want) == 0 ? want : 1;
-    }
-    const int cus = cu_count();
-    int S = 1;
-    while (2 * S <= 16 && (long)a.B * a.H * 2 * S <= cus && a.T % (64 * 2 * S) == 0 && a.T / (2 * S) >= 512) S *= 2;
-    return S >= 4 ? S : 1;      // two segments do not pay for the extra state pass (two workgroups per pair serve that case)
-}
 // segment entry states of a two-level forward: state pass per segment from zero (A, dsum), chained by tsplit_combine_kernel
 hipError_t tsplit_entry_states(const ScanArgs& a, int S, float* A, float* Sin, float* dsum, hipStream_t st)
 {
@@ -362,7 +398,6 @@ void wkv6_set_clock_ring(void* buf, int n_slots, int n_launches)
     wkv6::g_clock.launches = on ? n_launches : 0;
     wkv6::g_clock.count[0] = wkv6::g_clock.count[1] = 0;
 }
-void wkv6_set_clock_buffer(void* buf, int n_slots) { wkv6_set_clock_ring(buf, n_slots, 1); }
 void wkv6_clock_ring_counts(long* fwd, long* bwd)
 {
     std::lock_guard<std::mutex> lk(wkv6::g_clock.mu);
@@ -373,6 +408,11 @@ int wkv6_pass_marker(void* stream)
 {
     hipLaunchKernelGGL(wkv6::pass_marker_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream);
     return to_rc(hipGetLastError());
+}
+int wkv6_set_dispatch(int what, int value)
+{
+    if (what < WKV6_DISPATCH_SPLIT || what > WKV6_DISPATCH_TSPLIT) return WKV6_EINVAL;
+    return wkv6::g_dispatch[what].exchange(value);
 }
 
 size_t wkv6_backward_workspace_bytes(int B, int T, int C, int H)

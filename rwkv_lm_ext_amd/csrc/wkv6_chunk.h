@@ -3,7 +3,7 @@
 #include "wkv6_scan.h"
 
 // Diagnostic build (-DWKV6_STAMP, tools/ablate.sh): waves accumulate s_memtime cycles per phase into the buffer set through
-// wkv6_set_debug_buffer(); no stamp executes in the normal build.
+// wkv6_set_debug_buffer() -- and, in the backward, the cycles inside each tag group's polls; no stamp executes in the normal build.
 // -DWKV6_CLOCK: only one (s_memtime, s_memrealtime) pair around each wave's whole life, slots 6 / 7 of its record: the in-kernel
 // shader clock = d(s_memtime) / d(s_memrealtime) x 100 MHz with no per-phase stamp in the loop (tools/clock_probe.py).
 // -DWKV6_DEBUG: the LDS tag polls of the backward count their tries and trap with a record in the debug buffer instead of spinning forever.
@@ -12,6 +12,15 @@
 #define WKV6_CLK(c, r) asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(c), "=s"(r) :: "memory")
 namespace wkv6 { extern unsigned long long* g_stamp_buffer; }
 #endif
+namespace wkv6 {
+// the diagnostic builds hand every chunk launch the record buffer set through wkv6_set_debug_buffer(); the product build, nothing
+inline void attach_debug_buffer([[maybe_unused]] ScanArgs& a)
+{
+#ifdef WKV6_DEBUGBUF
+    a.aux = reinterpret_cast<float*>(g_stamp_buffer);
+#endif
+}
+}  // namespace wkv6
 #ifdef WKV6_STAMP
 #define WKV6_T(var) do { __builtin_amdgcn_sched_barrier(0); \
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -111,23 +120,7 @@ __device__ __forceinline__ void load_kernargs(ScanArgs& dst)
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(ScanArgs) / 4); ++i) d[i] = kw[i];
 }
-// Workgroup slot -> (batch, head) row of the plain kernels.  Workgroups are dealt round-robin over the 8 XCDs (slots s and s + 8 share one:
-// MI355X_MICROARCH.md), so in slot order an XCD's L2 sees heads h, h + 8, h + 16, h + 24 of a token row: 128-byte pieces at a 1 KB stride.
-// WKV6_XCD_REMAP = 1 gives every XCD a contiguous range of (batch, head) rows instead -- at B = 8, H = 32 all 32 heads of one batch row,
-// i.e. whole 4 KB token rows per L2 (profiles/r06_xcd_remap.txt has the A/B).  A permutation of the rows: results cannot change.
-#ifndef WKV6_XCD_REMAP
-#define WKV6_XCD_REMAP 0
-#endif
-__device__ __forceinline__ unsigned xcd_row_of_slot(unsigned slot, unsigned n)
-{
-#if WKV6_XCD_REMAP == 1
-    return (n & 7u) ? slot : (slot & 7u) * (n >> 3) + (slot >> 3);
-#else
-    return slot;
-#endif
-}
-
-// In-run clock probe (wkv6_set_clock_buffer): hardware wave 0 of a workgroup stamps {s_memtime, s_memrealtime} at its start (which = 0)
+// In-run clock probe (wkv6_set_clock_ring): hardware wave 0 of a workgroup stamps {s_memtime, s_memrealtime} at its start (which = 0)
 // and its end (which = 1) straight into the buffer -- nothing stays in registers in between.  a.clk == null: one scalar branch.
 __device__ __forceinline__ void clock_stamp(const ScanArgs& a, unsigned slot, int which)
 {

@@ -39,9 +39,6 @@ namespace {
 
 using namespace chunk;
 
-#ifndef WKV6_FWD_PAIR
-#define WKV6_FWD_PAIR 0                     // role -> SIMD pairing of the forward's waves (chunk_fwd_body)
-#endif
 constexpr int GRP_BYTES = NBLK * BLK_BYTES;
 constexpr int CKX_BYTES = 4 * 4096;         // checkpoint transposition buffers of the four consumers (row order: wkv6_scan.h)
 // y leaves through LDS as whole token rows.  A consumer's result tile is 16 tokens x 16 channels = 32-byte pieces of the [B, T, C]
@@ -65,7 +62,7 @@ constexpr int YS_BYTES = GRP * YRS;
 // GroupNorm_H(y) * gate one group later from the y they kept in registers; y makes no round trip through HBM.
 // The kernel proper is a device function of (arguments, workgroup slot): chunk_fwd_kernel runs it on its one argument block,
 // chunk_fwd_pair_kernel (the two WKV problems of a bidirectional composition in ONE launch) on one of two.
-// CLK: the in-run clock probe (wkv6_set_clock_buffer) is compiled into the plain kernel only.
+// CLK: the in-run clock probe (wkv6_set_clock_ring) is compiled into the plain kernel only.
 // The producers' raw input registers of a call.  In the persistent wkv6_bi launch (CHAIN) they outlive the call: a call's producers, idle
 // while the consumers work through its last group, prepare group 0 of the NEXT call (the row's reversed half, or the slot's next row) and
 // leave that call's group 1 in flight into these registers.
@@ -115,7 +112,7 @@ struct FwdChain {
     bool nx_rev, nx_use_u;         // reversed / with the bonus vector
 };
 // (unsplit launches) does hardware wave `hw` of a workgroup play a producer?  One definition: chunk_fwd_body's role map below
-__device__ __forceinline__ bool fwd_hw_wave_produces(int hw) { return WKV6_FWD_PAIR == 1 ? (hw & 3) < 2 : hw >= 4; }
+__device__ __forceinline__ bool fwd_hw_wave_produces(int hw) { return hw >= 4; }
 template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false>
 __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned slot, const unsigned sslot, FwdRaw& raw, const FwdChain& ch = FwdChain{})
 {
@@ -130,28 +127,16 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
     // producer w - 2 (wave id 4 + w - 2) otherwise.  The preparation is duplicated, on CUs that would otherwise idle.
     const int hwid = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave-uniform, provably so
     const int part = a.split ? (int)(slot & 1) : 0;
-    const int bh = a.split ? (int)(slot >> 1) : (CLK ? (int)xcd_row_of_slot(slot, (unsigned)(a.B * a.H)) : (int)slot);   // (CLK: the plain kernel)
+    // (CLK: the plain kernel.  The row count times 0 costs no instruction, but hipcc 7.2 schedules the kernel's prologue by it: written as
+    // plain `slot`, the plain kernel comes out reordered, with one more branch setup.  Kept so that the shipped code stays as measured.)
+    const int bh = a.split ? (int)(slot >> 1) : (CLK ? (int)(slot + 0u * (unsigned)(a.B * a.H)) : (int)slot);
     // Role -> hardware wave.  The waves of a workgroup go to the CU's four SIMDs round-robin (hardware waves w and w + 4 share one:
-    // profiles/r06_fwd_pairing.txt has the HW_ID read-back).  WKV6_FWD_PAIR = 0: waves 0..3 consume, 4..7 produce -- one producer and one
-    // consumer per SIMD.  1: the roles are paired with themselves -- two SIMDs host two producers each, two host two consumers each (split
-    // launches, 6 waves: the two consumers share a SIMD, two producers share one, two have a SIMD to themselves).  cidx: the consumer's
-    // index within its workgroup (its LDS regions, its rows of a y flush, its stagger).
-    int wid, cidx;
-#if WKV6_FWD_PAIR == 1
-    {
-        const int simd = hwid & 3, second = hwid >> 2;
-        if (a.split) {
-            cidx = second;                                               // (consumers: hardware waves 0 and 4)
-            wid = simd == 0 ? 2 * part + second : (simd == 1 ? 4 + second : 4 + simd);   // producers: waves 1, 5 -> blocks 0, 1; 2 -> 2; 3 -> 3
-        } else {
-            cidx = 2 * (simd - 2) + second;                              // (consumers: hardware waves 2, 6, 3, 7)
-            wid = simd < 2 ? 4 + 2 * simd + second : cidx;               // producers: waves 0, 4, 1, 5 -> blocks 0, 1, 2, 3
-        }
-    }
-#else
+    // profiles/r06_fwd_pairing.txt has the HW_ID read-back): waves 0..3 consume, 4..7 produce -- one producer and one consumer per SIMD.
+    // (Pairing the roles with themselves -- two SIMDs with two producers each, two with two consumers each -- was 11.5 % slower: same
+    // profile.)  cidx: the consumer's index within its workgroup (its LDS regions, its rows of a y flush, its stagger).
+    int wid, cidx;                                                   // (declared, then set: as const initialisations the schedule differs)
     wid = a.split ? (hwid < 2 ? 2 * part + hwid : hwid + 2) : hwid;
     cidx = hwid;
-#endif
     const bool producer = wid >= 4;
     const int wv = wid & 3;                                          // block (producer) / column tile (consumer)
     // (CHAIN: the persistent launch has looked the row's batch index and length up -- two dependent memory round trips -- a call ahead)
@@ -214,21 +199,9 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
         // preparation they were in flight only for the barrier wait, ~1000 cycles of every group exposed; on its own the earlier request
         // gained nothing -- the consumers' exposed LDS round trips took the time over -- together with their up-front operand requests
         // 2-3 %: profiles/r04_fwd_prefetch.txt.)
-        // -DWKV6_STAMP -DWKV6_STAMP_PREP: the producers' record holds the cycles of the preparation's phases instead of the loop's:
-        // [unpack / lw / in-lane sums / r.u.k / V copy, next loads' issue, prefix butterfly + block factors, scale + split + stores,
-        //  score tile (LDS round trip, 6 MFMAs, mask, split, store)]
-#if defined(WKV6_STAMP) && defined(WKV6_STAMP_PREP)
-#define WKV6_TP(n) do { unsigned long long t_; WKV6_T(t_); stamp_acc[n] += t_ - tprev; tprev = t_; } while (0)
-        unsigned long long tprev = 0;
-#else
-#define WKV6_TP(n) do { } while (0)
-#endif
         auto prep_group = [&](int grp, int buf, const int ntok, const float (&uu)[4], auto&& request_next) {
             char* const bb = smem + buf * GRP_BYTES + wv * BLK_BYTES;
             float r[4][4], k[4][4], cs[4][4];
-#if defined(WKV6_STAMP) && defined(WKV6_STAMP_PREP)
-            WKV6_T(tprev);
-#endif
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt) {
                 const bool valid = grp * GRP + wv * BLK + 4 * tq + tt < ntok;
@@ -264,7 +237,6 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
                 }
                 *reinterpret_cast<uint2*>(bb + A_V * ARR + (4 * tq + tt) * RSB + 8 * c4) = pv[tt];
             }
-            WKV6_TP(0);
             // (the sixteen loads of the next group: ~2000 cycles of issue for the wave wherever they are placed -- behind the whole
             // preparation, here, or four at a time inside the loop above (+6 %): the four producers' 32 KB per group are a third of
             // what the CU's vector-memory pipe moves in a group at ~10 B per cycle, profiles/r05_fwd_prep_stamps.txt; v moved by the
@@ -274,7 +246,6 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
             // destinations are the raw registers, and copies all eight of them out of the way first)
             __builtin_amdgcn_sched_barrier(0);
             request_next();
-            WKV6_TP(1);
             float pre[4], c8[4], c16[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
@@ -296,7 +267,6 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
                 *reinterpret_cast<float4*>(bb + OFF_E16M8 + 16 * c4) =
                     make_float4(exp2_fast(c16[0] - c8[0]), exp2_fast(c16[1] - c8[1]), exp2_fast(c16[2] - c8[2]), exp2_fast(c16[3] - c8[3]));
             }
-            WKV6_TP(2);
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt) {
                 float rh[4], kh[4];
@@ -316,7 +286,6 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
                 split4(kh, hi, lo, spc);
                 *reinterpret_cast<uint2*>(row + A_KH * ARR) = hi; *reinterpret_cast<uint2*>(row + A_KL * ARR) = lo;
             }
-            WKV6_TP(3);
             if constexpr (!STATE_ONLY) {
                 // Scores of this block, once for all four consumers: sc[b][a] = sum_i Khat[b][i] Rhat[a][i] from the rows this
                 // wave has just written (LDS operations of one wave execute in order), masked to b < a with the bonus
@@ -346,7 +315,6 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
                 split4(scm, sh, sl, spc);
                 *reinterpret_cast<uint4*>(bb + OFF_SC + lane * 16) = make_uint4(sh.x, sh.y, sl.x, sl.y);   // hi (4 key tokens) | lo: the lane's 8 k-slots
             }
-            WKV6_TP(4);
         };
 
         // (the next group's requests go out unconditionally: past the last group they lie past the end of the buffer resources and cost
@@ -374,11 +342,7 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
             WKV6_T(ts3);
             __syncthreads();
             WKV6_T(ts4);
-#ifndef WKV6_STAMP_PREP
             WKV6_ACC(0, ts1, ts0); WKV6_ACC(1, ts2, ts1); WKV6_ACC(2, ts3, ts2); WKV6_ACC(3, ts4, ts3);
-#else
-            WKV6_ACC(5, ts4, ts3);                            // (barrier wait)
-#endif
         }
         if constexpr (CHAIN) {
             // the consumers are busy with this call's last group: the raw registers are dead, the next call's first inputs can fly
@@ -532,14 +496,8 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
             if (staged && grp > 0) flush_y(grp - 1);
             if constexpr (ACC) acc_request(grp + 1, acc_nxt);     // (past the last group: past the end of the resource, reads zero)
 
-            // Rolled (runtime trip count): a fully unrolled 4-block body is no faster.  -DWKV6_FWD_UNROLL builds the unrolled
-            // body for tools/check_unrolled_fwd.sh (the wrong y that build once produced was the mixed-shape
-            // MFMA accumulation hazard, not a reordered LDS read).
-#ifdef WKV6_FWD_UNROLL
-            constexpr bool unrolled = true;
-#else
+            // Rolled (runtime trip count): a fully unrolled 4-block body is no faster.
             constexpr bool unrolled = GN || ACC;                  // the GN epilogue and the ACC addends keep per-block values in registers: static indices
-#endif
             // blocks past the end are neutral (zero-filled operands) in the unrolled form
             const int nb = unrolled ? NBLK : min(NBLK, (ntok - grp * GRP + BLK - 1) / BLK);
             constexpr int unroll_by = unrolled ? NBLK : 1;
@@ -838,17 +796,13 @@ template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN = false> hipError_t lau
 // per-lane byte offsets are 32-bit: bf16 tensors need (T + 64) C < 2^31 (checked by the API), the fp32 decay input half of that
 static bool offsets_fit(const ScanArgs& a) { return a.wkind == 1 || ((long)a.T + 64) * a.C < (1L << 30); }
 
-int want_split(int BH);     // wkv6_chunk_bwd12k.hip
-
 hipError_t launch_chunk_fwd(const ScanArgs& a_, hipStream_t st)
 {
     if (!offsets_fit(a_)) return hipErrorInvalidValue;
     ScanArgs a = a_;
     a.split = want_split(a.B * a.H);
     a.clk = clock_claim(0, &a.clk_slots);
-#ifdef WKV6_DEBUGBUF
-    a.aux = reinterpret_cast<float*>(g_stamp_buffer);
-#endif
+    attach_debug_buffer(a);
     const bool raw = a.wkind == 1;          // 0: fp32 ew = -exp(w), 1: raw w in bf16, 2: fp32 decay exp(-exp(w))
     if (a.gn_out) {                         // fused GroupNorm * gate epilogue: the four consumer waves of a head in one workgroup
         if (a.split || a.accumulate || a.y_f32 || a.zero_tail) return hipErrorNotSupported;
@@ -884,7 +838,6 @@ hipError_t launch_chunk_fwd_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipSt
     return hipGetLastError();
 }
 
-int bi_slots(int BH);       // wkv6_chunk_bwd12k.hip
 hipError_t launch_chunk_fwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* slots, hipStream_t st)
 {
     const int n = bi_slots(a1_.B * a1_.H);
@@ -894,9 +847,8 @@ hipError_t launch_chunk_fwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* sl
     ScanArgs a1 = a1_, a2 = a2_;
     a1.split = a2.split = 0;
     a1.side_compact = a2.side_compact = 1;
-#ifdef WKV6_DEBUGBUF
-    a1.aux = a2.aux = reinterpret_cast<float*>(g_stamp_buffer);
-#endif
+    attach_debug_buffer(a1);
+    attach_debug_buffer(a2);
     constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
     static LdsAttrOnce attr_raw, attr_ew;
     if (a1.wkind == 1) {

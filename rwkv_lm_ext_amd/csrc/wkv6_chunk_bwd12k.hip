@@ -119,7 +119,7 @@ __device__ __forceinline__ void split8(const float (&t0)[4], const float (&t1)[4
 // roles cannot share LDS there: G is kept in both orientations (by rows in the row workgroup for gk, by columns in the column
 // workgroup for gv: no published operand), the producers copy v and gy themselves, and the column waves make their own score
 // tiles.  Every wave does the same arithmetic as in the one-workgroup launch: the outputs are bit-identical.
-// CLK: the in-run clock probe (wkv6_set_clock_buffer) is compiled into the plain kernel only (it costs ~6 SGPRs, which the wkv6_bi
+// CLK: the in-run clock probe (wkv6_set_clock_ring) is compiled into the plain kernel only (it costs ~6 SGPRs, which the wkv6_bi
 // and pair instantiations do not have).
 // What a call of the persistent wkv6_bi launch (CHAIN) knows beyond its argument block: the row's batch index and length, looked up a row ahead
 // by the launch (a.order[row / H] -> a.lens[b]: two dependent memory round trips, ~3000 cycles that used to open every call).
@@ -169,7 +169,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
     const SplitConst spc = split_const();
     const int hwid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int part = SPLIT ? (int)(slot & 1) : 0;
-    const int bh = SPLIT ? (int)(slot >> 1) : (CLK ? (int)xcd_row_of_slot(slot, (unsigned)(a.B * a.H)) : (int)slot);   // (CLK: the plain kernel)
+    const int bh = SPLIT ? (int)(slot >> 1) : (int)slot;
     const int wid = SPLIT ? (hwid < 4 ? hwid + 4 * part : hwid + 4) : hwid;
     const bool rowrole = ROLE ? ROLE == 1 : wid < 4, producer = ROLE ? ROLE == 3 : wid >= 8;
     const int wv = wid & 3;                                              // tile owned by a row / column wave
@@ -218,22 +218,12 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
     };
 #ifdef WKV6_STAMP
     unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0}, ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ts4 = 0, ts5 = 0;
-    [[maybe_unused]] unsigned long long tp0 = 0, tp1 = 0;
-// slot 5 of a wave's record, chosen at build time (-DWKV6_STAMP5=1: cycles inside tag polls; =2: around the issue of vector-memory instructions)
-#ifndef WKV6_STAMP5
-#define WKV6_STAMP5 1
-#endif
-#define WKV6_T5(kind, var) do { if (WKV6_STAMP5 == (kind)) WKV6_T(var); } while (0)
-#define WKV6_ACC5(kind, t1, t0) do { if (WKV6_STAMP5 == (kind)) stamp_acc[5] += (t1) - (t0); } while (0)
+    unsigned long long tp0 = 0, tp1 = 0;
     unsigned long long poll_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // cycles inside the polls of each tag group (DA SC GA GB GC GD GE GF)
-#define WKV6_ACCP(idx, t1, t0) do { if (WKV6_STAMP5 == 1) poll_acc[(idx) >> 2] += (t1) - (t0); } while (0)
-// -DWKV6_STAMP5=3: times of the hand-over events since the start of the stage instead (records 12 / 13, see tools/time_ops.py)
-#define WKV6_EV(k) do { if (WKV6_STAMP5 == 3) { unsigned long long te_; WKV6_T(te_); poll_acc[k] += te_ - ts0; } } while (0)
+// cycles inside tag polls: slot 5 of a wave's record in all, and per tag group (records 12 / 13)
+#define WKV6_ACCP(idx, t1, t0) do { stamp_acc[5] += (t1) - (t0); poll_acc[(idx) >> 2] += (t1) - (t0); } while (0)
 #else
 #define WKV6_ACCP(idx, t1, t0) do { } while (0)
-#define WKV6_EV(k) do { } while (0)
-#define WKV6_T5(kind, var) do { } while (0)
-#define WKV6_ACC5(kind, t1, t0) do { } while (0)
 #endif
     // Gradient stores.  A wave's result tile is 16 tokens x 16 channels: 32 bytes per token row of the [B, T, C] tensors.  Block 1's packed
     // bf16 result waits for block 0's; one v_permlane16_swap per dword then gives the even lane rows block 1 (own four channels + the odd
@@ -564,14 +554,14 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
     auto tags_differ = [&](unsigned f, int tag) { return __builtin_amdgcn_ballot_w64(f != (unsigned)tag) != 0; };
     auto await_n = [&](int idx, int tag, int lane_off) {
         [[maybe_unused]] unsigned spins = 0;
-        WKV6_T5(1, tp0);
+        WKV6_T(tp0);
         for (;;) {
             const unsigned f = (unsigned)*(lds_vint*)((unsigned char __attribute__((address_space(3)))*)xflag_at(idx) + lane_off);
             if (!tags_differ(f, tag)) break;
             WKV6_SPIN_GUARD(idx, tag, f);
             __builtin_amdgcn_s_sleep(1);
         }
-        WKV6_T5(1, tp1); WKV6_ACC5(1, tp1, tp0); WKV6_ACCP(idx, tp1, tp0);
+        WKV6_T(tp1); WKV6_ACCP(idx, tp1, tp0);
     };
     auto await2 = [&](int idx, int tag) { await_n(idx, tag, lane_tag2); };
     auto await4 = [&](int idx, int tag) { await_n(idx, tag, lane_tag4); };
@@ -744,12 +734,10 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
             if constexpr (!SPLIT) {   // first of all: block 1's operand is there (published before the stage barrier; the first stage polls) --
                                       // taking it now releases it ~1500 cycles earlier for the column waves to lay block 0's over it
                 if (grp == ngrp - 1) await4(TAG_GA, grp + 1);
-                WKV6_EV(0);
                 gvb[1] = take_gop(1);
                 // released at once: the reads are in this wave's LDS queue, which is served in order, and the tag store cannot be moved
                 // above loads it may alias (their address is opaque to the compiler) -- no need to wait for their data here
                 publish(TAG_GB, tagv);
-                WKV6_EV(1);
             }
             // (second half of wkv6_bi: the first half's gr of both blocks, requested a pre-phase ahead of the sums they meet)
             float old_gr[SBLK][4] = {}, old_gk[SBLK][4] = {}, old_gw[SBLK][4] = {};
@@ -902,7 +890,6 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                 fetch_old(1, rs_gk, grp * STG + blk * BLK, REV_K, old_gk[blk]);
                 fetch_old(3, rs_gw, grp * STG + blk * BLK, REV_W, old_gw[blk]);
             }
-            WKV6_T5(2, tp0);
             // The even stage of a pair enters with the pair's checkpoint itself -- which its odd stage left untouched in CK (the rebuild
             // above writes ST[0], not CK): only an even stage requests a new one.  (Rounds 4: both stages read it, the second from the
             // L2 -- 16 KB per pair and workgroup through the CU's vector-memory pipe, which these kernels keep ~80 % busy:
@@ -919,11 +906,8 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                     }
                 }
             }
-            WKV6_T5(2, tp1); WKV6_ACC5(2, tp1, tp0);
             if constexpr (!SPLIT) {
-                WKV6_EV(2);
                 settle4(TAG_GC, grp + 1, pk_gc);
-                WKV6_EV(3);
                 gvb[0] = take_gop(0);
                 // Released for the column waves (they lay the NEXT stage's first operand over it): this wave's reads are in the LDS
                 // queue, which serves a wave's requests in order, and a store is never moved above a load it may alias.
@@ -1155,8 +1139,6 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                         gop_write(gh[blk], gl[blk]);
                         publish(TAG_GA, tagv);
                     }
-                    WKV6_EV(0);
-                    WKV6_T5(2, tp0);
                     // this wave's requests for the stages behind (CHAIN: past this call's first stage they go to the call that follows --
                     // stage 1 requests its last stage's v, stage 0 its last stage's gy and the v of the stage in front)
                     if constexpr (CHAIN) {
@@ -1170,15 +1152,11 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                         if (grp > 0) load_gy(cur, lp_vg, grp - 1);
                         if (grp > 1) load_v(cur, lp_vg, grp - 2);
                     }
-                    WKV6_T5(2, tp1); WKV6_ACC5(2, tp1, tp0);
                 } else {
                     scale_split(kb, gh[blk], gl[blk]);
-                    WKV6_EV(1);
                     await4(TAG_GB, grp + 1);     // the row waves have taken block 1's version
-                    WKV6_EV(2);
                     gop_write(gh[blk], gl[blk]);
                     publish(TAG_GC, tagv);
-                    WKV6_EV(3);
                 }
                 const s4v gyT = tr_read(rb + R_GY * ARR + troff + 32 * wv);           // gy[4g+e][16wv + x]
 #pragma unroll
@@ -1332,11 +1310,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
         unsigned long long* const d = reinterpret_cast<unsigned long long*>(a.aux) + ((long)bh * 16 + wid) * 8;
 #ifdef WKV6_STAMP
         for (int i = 0; i < 6; ++i) d[i] = stamp_acc[i];
-#if WKV6_STAMP5 == 3
-        if (wid < 8) for (int i = 0; i < 4; ++i) d[(12 + (wid >> 1) - wid) * 8 + 4 * (wid & 1) + i] = poll_acc[i];  // records 12 .. 15: four events of waves 0 .. 7
-#else
         if (wid == 0 || wid == 4) for (int i = 0; i < 8; ++i) d[(12 + (wid >> 2) - wid) * 8 + i] = poll_acc[i];   // records 12 / 13
-#endif
 #endif
         d[6] = clk1 - clk0;
         d[7] = rtc1 - rtc0;
@@ -1487,25 +1461,6 @@ template <bool W_RAW> hipError_t launch_bwd12k_variant(const ScanArgs& a, hipStr
 
 hipError_t launch_chunk_state_pass(const ScanArgs& a, hipStream_t st);   // wkv6_chunk.hip
 
-// two workgroups per (batch, head) when one each would leave at least half of the CUs without work
-int cu_count()              // compute units of the current device (0: unknown)
-{
-    static int cus[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
-        cus[dev] = prop.multiProcessorCount;
-    }
-    return cus[dev];
-}
-int want_split(int BH)
-{
-    if (const char* e = getenv("WKV6_SPLIT")) return atoi(e) != 0;     // A/B switch
-    return 2 * BH <= cu_count();
-}
-
 // reverse pass over 64-token row-order checkpoints (a.ckpt filled by the forward or by launch_chunk_state_pass); a.split as given
 hipError_t launch_chunk_bwd12k(const ScanArgs& a_, hipStream_t st)
 {
@@ -1513,9 +1468,7 @@ hipError_t launch_chunk_bwd12k(const ScanArgs& a_, hipStream_t st)
     if (a_.split && (a_.g_in || a_.rc_in)) return hipErrorInvalidValue;     // (segment rows of a two-level scan run one workgroup each)
     ScanArgs a = a_;
     a.clk = clock_claim(1, &a.clk_slots);
-#ifdef WKV6_DEBUGBUF
-    a.aux = reinterpret_cast<float*>(g_stamp_buffer);
-#endif
+    attach_debug_buffer(a);
     return a.wkind ? launch_bwd12k_variant<true>(a, st) : launch_bwd12k_variant<false>(a, st);
 }
 
@@ -1530,14 +1483,6 @@ hipError_t launch_chunk_bwd(const ScanArgs& a_, hipStream_t st)
         if (hipError_t e = launch_chunk_state_pass(sp, st)) return e;
     }
     return launch_chunk_bwd12k(a, st);
-}
-
-int bi_slots(int BH)
-{
-    if (want_split(BH)) return 0;
-    if (const char* e = getenv("WKV6_BI_FUSED")) { if (atoi(e) == 0) return 0; }     // A/B switch: 0 = the halves as two launches
-    const int cus = cu_count();
-    return cus > 0 ? (BH < cus ? BH : cus) : 0;
 }
 
 hipError_t launch_chunk_bwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* slots, hipStream_t st)
@@ -1555,9 +1500,7 @@ hipError_t launch_chunk_bwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* sl
             if (hipError_t e = launch_chunk_state_pass(sp, st)) return e;
         }
         a->side_compact = 1;
-#ifdef WKV6_DEBUGBUF
-        a->aux = reinterpret_cast<float*>(g_stamp_buffer);
-#endif
+        attach_debug_buffer(*a);
     }
     // (both decay kinds since round 6: the reference-signature symbols pass fp32 ew = -exp(w), cuda/wkv6_bi_op.cpp:5-13)
     constexpr size_t lds = BWD12K_LDS;
@@ -1588,9 +1531,8 @@ hipError_t launch_chunk_bwd_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipSt
     if (a0_.wkind != 1 && ((long)a0_.T + 64) * a0_.C >= (1L << 30)) return hipErrorInvalidValue;
     ScanArgs a0 = a0_, a1 = a1_;
     a0.split = a1.split = 0;
-#ifdef WKV6_DEBUGBUF
-    a0.aux = a1.aux = reinterpret_cast<float*>(g_stamp_buffer);
-#endif
+    attach_debug_buffer(a0);
+    attach_debug_buffer(a1);
     constexpr size_t lds = BWD12K_LDS;
     static LdsAttrOnce attr_raw, attr_ew;
     if (a0.wkind == 1) {

@@ -92,7 +92,7 @@ struct ScanArgs {
     int side_compact;                 // chunked wkv6_bi halves in one launch: y_f32 / g_f32 are per-workgroup scratch, fp32 [slot][T][64]
                                       // (token stride 64), instead of [B,T,C] arrays addressed by (batch, head)
     unsigned long long* clk;          // chunked kernels: clock stamps of wave 0 of workgroup slots < clk_slots ({memtime, memrealtime} at start
-    int clk_slots;                    //   and end: wkv6_set_clock_buffer, include/wkv6_amd.h), or null (the default: no stamp executes)
+    int clk_slots;                    //   and end: wkv6_set_clock_ring, include/wkv6_amd.h), or null (the default: no stamp executes)
     int split;                        // chunked kernels, set by the launcher when B*H leaves half the chip idle: two workgroups per
                                       // (batch, head), each with its own producers and half of the consuming waves
 };
@@ -169,6 +169,6 @@ hipError_t launch_chunk_state_pass(const ScanArgs& a, hipStream_t st);   // stat
 // or null; takes the launch's place in the ring (host side, one atomic increment per launch)
 unsigned long long* clock_claim(int kind, int* slots);
 int cu_count();
-int want_split(int BH);                      // two workgroups per (batch, head)?  (wkv6_chunk_bwd12k.hip)
+int want_split(int BH);                      // two workgroups per (batch, head)?  (launch-shape policy: wkv6_api.hip)
 
 }  // namespace wkv6

@@ -16,6 +16,8 @@ They are also registered as ``torch.ops.wkv6.forward`` etc. (the reference's TOR
 cuda/wkv6_op.cpp:19-22).  Unlike the reference shims (which check nothing) every call validates
 device, dtype, contiguity and shape and launches on the current stream of the tensors' device.
 """
+import contextlib
+
 import torch
 
 from . import _lib
@@ -485,10 +487,29 @@ def selftest():
 
 
 def pass_marker():
-    """Launch the empty kernel wkv6::pass_marker_kernel on the current stream (a phase boundary in a profiler's dispatch list).
-    A no-op with an explicit A/B library (RWKV_AMD_LIB) that predates the symbol."""
-    if _lib.has_symbol("wkv6_pass_marker"):
-        _lib.check(_lib.load().wkv6_pass_marker(_stream_ptr()), "wkv6_pass_marker")
+    """Launch the empty kernel wkv6::pass_marker_kernel on the current stream (a phase boundary in a profiler's dispatch list)."""
+    _lib.check(_lib.load().wkv6_pass_marker(_stream_ptr()), "wkv6_pass_marker")
+
+
+_DISPATCH = {"split": 0, "bi_fused": 1, "tsplit": 2}      # WKV6_DISPATCH_* of include/wkv6_amd.h
+
+
+@contextlib.contextmanager
+def dispatch(split=None, bi_fused=None, tsplit=None):
+    """Override the library's launch-shape choices for the body (wkv6_set_dispatch, include/wkv6_amd.h), process-wide; None leaves a
+    choice alone.  split: != 0 forces two workgroups per (batch, head), 0 one.  bi_fused = 0: the halves of wkv6_bi as two launches.
+    tsplit: 0 / 1 turns the two-level forward over T off, n forces n segments where T % (64 n) == 0.  The previous values come back on
+    exit, exceptions included."""
+    lib = _lib.load()
+    given = {name: v for name, v in (("split", split), ("bi_fused", bi_fused), ("tsplit", tsplit)) if v is not None}
+    prev = {}
+    try:
+        for name, v in given.items():
+            prev[name] = lib.wkv6_set_dispatch(_DISPATCH[name], int(v))
+        yield
+    finally:
+        for name, v in prev.items():
+            lib.wkv6_set_dispatch(_DISPATCH[name], v)
 
 
 class ClockProbe:
@@ -504,24 +525,13 @@ class ClockProbe:
     each kind, None where nothing was stamped) plus, per kind, the lists "fwd_ghz_launches" / "fwd_us_launches" (oldest first: every
     launch still in the ring; us = max(end) - min(start) of s_memrealtime over the stamped workgroups) and "fwd_count".
     The probe owns the device buffer for as long as the library holds its address: close() (also on __exit__ / __del__) switches the
-    stamps off first.  With an explicit A/B library (RWKV_AMD_LIB) that predates the symbols everything is a no-op and read() returns
-    None values."""
+    stamps off first; read() after close() returns None values."""
 
     def __init__(self, device, n_slots=256, n_launches=1):
         self.n, self.nl = int(n_slots), int(n_launches)
         self.lib = _lib.load()
-        self.ring = _lib.has_symbol("wkv6_set_clock_ring")
-        self.active = self.ring or _lib.has_symbol("wkv6_set_clock_buffer")
-        self.buf = None
-        if not self.active:
-            return
-        if not self.ring:
-            self.nl = 1
         self.buf = torch.zeros(2 * self.nl * self.n * 4, dtype=torch.int64, device=device)
-        if self.ring:
-            self.lib.wkv6_set_clock_ring(self.buf.data_ptr(), self.n, self.nl)
-        else:
-            self.lib.wkv6_set_clock_buffer(self.buf.data_ptr(), self.n)
+        self.lib.wkv6_set_clock_ring(self.buf.data_ptr(), self.n, self.nl)
 
     def __enter__(self):
         return self
@@ -537,8 +547,6 @@ class ClockProbe:
             pass
 
     def counts(self):
-        if not (self.active and self.ring):
-            return None, None
         import ctypes
         f, b = ctypes.c_long(0), ctypes.c_long(0)
         self.lib.wkv6_clock_ring_counts(ctypes.byref(f), ctypes.byref(b))
@@ -547,7 +555,7 @@ class ClockProbe:
     def read(self):
         out = {}
         names = ("fwd", "bwd")
-        if not self.active or self.buf is None:
+        if self.buf is None:
             for nm in names:
                 out[nm + "_ghz"] = None
                 out[nm + "_ghz_launches"], out[nm + "_us_launches"], out[nm + "_count"] = [], [], None
@@ -556,10 +564,7 @@ class ClockProbe:
         cnt = self.counts()
         for i, nm in enumerate(names):
             n = cnt[i]
-            if n is None:                       # plain buffer (no ring in the library): one launch, the last
-                order = [0]
-            else:
-                order = [j % self.nl for j in range(max(0, n - self.nl), n)]
+            order = [j % self.nl for j in range(max(0, n - self.nl), n)]
             ghz, us = [], []
             for j in order:
                 s = d[i, j]
@@ -578,10 +583,7 @@ class ClockProbe:
     def close(self):
         if getattr(self, "buf", None) is None:
             return
-        if self.ring:
-            self.lib.wkv6_set_clock_ring(None, 0, 0)
-        else:
-            self.lib.wkv6_set_clock_buffer(None, 0)
+        self.lib.wkv6_set_clock_ring(None, 0, 0)
         self.buf = None
 
 

@@ -1,6 +1,6 @@
 """GPU parity of the backward kernel (csrc/wkv6_chunk_bwd12k.hip: 64-token row-order checkpoints, K part of the stage image two
 stages ahead) in its ONE-workgroup-per-(batch, head) mode, forced onto every shape of the suite: the suite's small shapes would
-otherwise run its two-workgroups-per-pair mode, so WKV6_SPLIT=0 puts them on the mode the benched shapes use (the split mode is
+otherwise run its two-workgroups-per-pair mode, so wkv6_op.dispatch(split=0) puts them on the mode the benched shapes use (the split mode is
 what the rest of the suite exercises, and both are bit-identical: test_wkv6_gpu.py::test_two_workgroups_per_head_is_the_same_arithmetic).
 Same bf16 contract as everything else: golden vectors generated from the reference, the oracle on random shapes, the exact scan
 kernels at every block / stage / checkpoint boundary, the wkv6_bi and in-kernel-reversal store paths, rows of 0 .. 65 tokens beside
@@ -25,10 +25,11 @@ def ops():
 
 
 @pytest.fixture
-def two_level(monkeypatch):
-    """One workgroup per (batch, head) for every shape (the library reads the switch at each call): small (batch, head) counts would
+def two_level(ops):
+    """One workgroup per (batch, head) for every shape (the library reads the override at each call): small (batch, head) counts would
     otherwise run two workgroups per pair."""
-    monkeypatch.setenv("WKV6_SPLIT", "0")
+    with ops.dispatch(split=0):
+        yield
 
 
 @pytest.mark.parametrize("name", ["wkv6_init", "wkv6_stress", "wkv6_extreme", "wkv6_T1", "wkv6_T2", "wkv6_T3", "wkv6_state", "wkv6_infctx"])
@@ -137,7 +138,7 @@ def test_wkv6_bi_store_paths(ops, two_level):
                 assert float(np.abs(c - s_).max()) <= (4.0 if n in ("gw", "gu") else 2.0) * 2.0 ** -8 * scale, (case, n)
 
 
-def test_in_kernel_reversal(ops, two_level, monkeypatch):
+def test_in_kernel_reversal(ops, two_level):
     """wkv6_backward_rev_ex: per-tensor reversal bits and per-row spans: the chunked kernels against the exact scan kernels."""
     B, T, H = 3, 150, 2
     ri = rand_inputs(4242, B, T, H, "init")
@@ -167,7 +168,7 @@ def test_checkpoint_path_is_the_state_pass_path(ops, two_level):
         assert torch.equal(a_, b_)
 
 
-def test_config2_full_size_vs_oracle_slices_and_scan(ops, oracle, two_level, monkeypatch):
+def test_config2_full_size_vs_oracle_slices_and_scan(ops, oracle, two_level):
     """BASELINE configs[1] at full size (B=8, T=4096, H=32): oracle on (batch, head) slices, and agreement with the exact scan
     backward over the whole tensors."""
     from bench import synth
@@ -267,10 +268,10 @@ def test_ragged_rows_with_the_reference_decay_kind_share_one_fused_launch(ops, t
 
 
 @pytest.mark.parametrize("ew", [False, True], ids=["raw_w", "fp32_ew"])
-def test_chained_persistent_launches_equal_the_two_launch_halves_bit_for_bit(ops, two_level, monkeypatch, ew):
+def test_chained_persistent_launches_equal_the_two_launch_halves_bit_for_bit(ops, two_level, ew):
     """Round 6 chained the calls of the persistent wkv6_bi backward (a call's producers, column and row waves prepare the call that follows;
     the stage -> LDS slot maps rotate across the call boundary) and fused the fp32-ew kind: every wave still does the arithmetic of the plain
-    two-launch kernels (WKV6_BI_FUSED=0), so forward and backward must agree BIT FOR BIT -- on rows of every chaining case: fewer than two
+    two-launch kernels (dispatch(bi_fused=0)), so forward and backward must agree BIT FOR BIT -- on rows of every chaining case: fewer than two
     stages (not chained, nor chained into), exactly two, odd and even stage counts, several rows per workgroup slot."""
     B, T, H = 12, 330, 32                                             # 384 rows on 256 slots: a second row behind half of the slots
     lens = torch.tensor([330, 0, 1, 32, 33, 64, 65, 96, 97, 128, 200, 313], dtype=torch.int32, device="cuda")
@@ -279,10 +280,10 @@ def test_chained_persistent_launches_equal_the_two_launch_halves_bit_for_bit(ops
         d[3] = (-torch.exp(d[3].float())).contiguous()
     outs = {}
     for mode in ("1", "0"):
-        monkeypatch.setenv("WKV6_BI_FUSED", mode)
-        ws = ops.bi_new_workspace(B, T, H * 64, H, "cuda")
-        y = ops.bi_forward_ex(None, *d[:5], H, ws=ws, lens=lens, w_is_ew=ew)
-        g = ops.bi_backward_ex(None, *d, H, ws=ws, lens=lens, w_is_ew=ew)
-        outs[mode] = [host(y)] + [host(t) for t in g]
+        with ops.dispatch(bi_fused=int(mode)):
+            ws = ops.bi_new_workspace(B, T, H * 64, H, "cuda")
+            y = ops.bi_forward_ex(None, *d[:5], H, ws=ws, lens=lens, w_is_ew=ew)
+            g = ops.bi_backward_ex(None, *d, H, ws=ws, lens=lens, w_is_ew=ew)
+            outs[mode] = [host(y)] + [host(t) for t in g]
     for n, a_, b_ in zip(("y", "gr", "gk", "gv", "gw", "gu"), outs["1"], outs["0"]):
         assert np.array_equal(a_, b_), (n, float(np.abs(a_ - b_).max()))

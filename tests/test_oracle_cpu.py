@@ -227,17 +227,36 @@ def test_oracle_matches_the_medium_reference_fixtures(oracle):
 
 def test_clock_ring_host_bookkeeping():
     """wkv6_set_clock_ring / wkv6_clock_ring_counts (include/wkv6_amd.h, measurement aids): setting the ring resets the per-kernel launch
-    counts, nothing is launched or dereferenced on the host, NULL switches the probe off; the python wrapper's no-op contract for A/B
-    libraries that predate the symbols rests on _lib.has_symbol."""
+    counts, nothing is launched or dereferenced on the host, NULL switches the probe off."""
     import ctypes
     from rwkv_lm_ext_amd import _lib
     lib = _lib.load()
-    assert all(_lib.has_symbol(s) for s in _lib.MEASUREMENT_AIDS)
+    for s in ("wkv6_set_clock_ring", "wkv6_clock_ring_counts", "wkv6_pass_marker"):
+        assert hasattr(lib, s), s
     f, b = ctypes.c_long(-1), ctypes.c_long(-1)
     lib.wkv6_set_clock_ring(ctypes.c_void_p(0x1000), 64, 128)      # (a device address as far as the library knows: only handed to kernels)
     lib.wkv6_clock_ring_counts(ctypes.byref(f), ctypes.byref(b))
     assert (f.value, b.value) == (0, 0)
     lib.wkv6_set_clock_ring(None, 0, 0)
-    lib.wkv6_set_clock_buffer(None, 0)
     lib.wkv6_clock_ring_counts(ctypes.byref(f), None)
     assert f.value == 0
+
+
+def test_dispatch_override_host_bookkeeping():
+    """wkv6_set_dispatch (include/wkv6_amd.h): the setter returns the previous value, -1 restores the library's own choice, an unknown
+    selector is refused with WKV6_EINVAL, and wkv6_op.dispatch restores the previous values when its body raises."""
+    from rwkv_lm_ext_amd import _lib, wkv6_op
+    lib = _lib.load()
+    EINVAL = -1
+    for what in (0, 1, 2):                                   # WKV6_DISPATCH_SPLIT, _BI_FUSED, _TSPLIT
+        assert lib.wkv6_set_dispatch(what, 3) == -1          # default: the library's own choice
+        assert lib.wkv6_set_dispatch(what, 0) == 3
+        assert lib.wkv6_set_dispatch(what, -1) == 0
+        assert lib.wkv6_set_dispatch(what, -1) == -1
+    assert lib.wkv6_set_dispatch(3, 1) == EINVAL and lib.wkv6_set_dispatch(-1, 1) == EINVAL
+    with pytest.raises(ZeroDivisionError):
+        with wkv6_op.dispatch(split=1, tsplit=4):
+            assert lib.wkv6_set_dispatch(0, 1) == 1 and lib.wkv6_set_dispatch(2, 4) == 4
+            assert lib.wkv6_set_dispatch(1, -1) == -1        # (not given: left alone)
+            1 // 0
+    assert [lib.wkv6_set_dispatch(what, -1) for what in (0, 1, 2)] == [-1, -1, -1]

@@ -178,45 +178,45 @@ def test_golden_bi(ops, io):
 
 @pytest.mark.parametrize("bwd", ["auto", "12k"], ids=["auto", "unsplit"])
 @pytest.mark.parametrize("io", IOS, ids=["f32", "bf16"])
-def test_golden_medium(ops, monkeypatch, io, bwd):
+def test_golden_medium(ops, io, bwd):
     """Reference-generated vectors at T = 160 (oracle/gen_golden_medium.py): every block, stage, group and checkpoint boundary of
     the chunked kernels meets values that came out of the reference's own recurrence -- plain, per-sample state with gs and
     final state, ragged wkv6_bi; fp32 I/O (scan kernels) and bf16 I/O through either chunked backward."""
-    if bwd != "auto":      # auto: the small grid runs two workgroups per (batch, head); 12k: one workgroup per pair, as at the benched shapes
-        if io == torch.float32:
-            pytest.skip("the backward switch only concerns the chunked bf16 kernels")
-        monkeypatch.setenv("WKV6_SPLIT", "0")
-    tol = F32_TOL if io == torch.float32 else PART_TOL
-    g = load_golden_mid("wkv6_mid")
-    H = g["u"].shape[0]
-    B, T, C = g["r"].shape
-    r, k, v, w, u, gy = (dev(g[n], io) for n in ("r", "k", "v", "w", "u", "gy"))
-    ck = ops.new_checkpoint(B, T, C, H, "cuda") if io == torch.bfloat16 else None
-    check(ops.forward_ex(r, k, v, w, u, H, ckpt=ck), g["y"], io, "mid y")
-    gr, gk, gv, gw, gu, _ = ops.backward_ex(r, k, v, w, u, gy, H, ckpt=ck)
-    for n, t in (("gr", gr), ("gk", gk), ("gv", gv), ("gw", gw)):
-        check(t, g[n], io, "mid " + n)
-    assert max_norm_err(host(gu).sum(0).reshape(H, 64), g["gu"]) <= tol
-    g = load_golden_mid("wkv6_mid_state")
-    H = g["u"].shape[0]
-    r, k, v, w, u, gy, s = (dev(g[n], io) for n in ("r", "k", "v", "w", "u", "gy", "s"))
-    s_out = torch.empty_like(s)
-    check(ops.forward_ex(r, k, v, w, u, H, s0=s, s_out=s_out), g["y"], io, "mid state y")
-    check(s_out, g["s_final"], io, "mid final state")
-    gr, gk, gv, gw, gu, gs = ops.backward_ex(r, k, v, w, u, gy, H, s0=s, want_gs=True)
-    for n, t in (("gr", gr), ("gk", gk), ("gv", gv), ("gw", gw), ("gs", gs.to(io))):
-        check(t, g[n], io, "mid state " + n)
-    assert max_norm_err(host(gu).sum(0).reshape(H, 64), g["gu"]) <= tol
-    g = load_golden_mid("wkv6_mid_bi")
-    H = g["u"].shape[0]
-    r, k, v, w, u, gy = (dev(g[n], io) for n in ("r", "k", "v", "w", "u", "gy"))
-    mask = torch.from_numpy(g["mask"].astype(np.int32)).cuda()
-    check(ops.bi_forward_ex(mask, r, k, v, w, u, H), g["y"], io, "mid bi y")
-    gr, gk, gv, gw, gu = ops.bi_backward_ex(mask, r, k, v, w, u, gy, H)
-    for n, t in (("gr", gr), ("gk", gk), ("gv", gv), ("gw", gw)):
-        check(t, g[n], io, "mid bi " + n)
-        assert np.all(host(t)[2, 33:] == 0) and np.all(host(t)[1, 97:] == 0)
-    assert max_norm_err(host(gu).sum(0).reshape(H, 64), g["gu"]) <= tol
+    if bwd != "auto" and io == torch.float32:
+        pytest.skip("the backward switch only concerns the chunked bf16 kernels")
+    # auto: the small grid runs two workgroups per (batch, head); 12k: one workgroup per pair, as at the benched shapes
+    with ops.dispatch(split=0 if bwd != "auto" else None):
+        tol = F32_TOL if io == torch.float32 else PART_TOL
+        g = load_golden_mid("wkv6_mid")
+        H = g["u"].shape[0]
+        B, T, C = g["r"].shape
+        r, k, v, w, u, gy = (dev(g[n], io) for n in ("r", "k", "v", "w", "u", "gy"))
+        ck = ops.new_checkpoint(B, T, C, H, "cuda") if io == torch.bfloat16 else None
+        check(ops.forward_ex(r, k, v, w, u, H, ckpt=ck), g["y"], io, "mid y")
+        gr, gk, gv, gw, gu, _ = ops.backward_ex(r, k, v, w, u, gy, H, ckpt=ck)
+        for n, t in (("gr", gr), ("gk", gk), ("gv", gv), ("gw", gw)):
+            check(t, g[n], io, "mid " + n)
+        assert max_norm_err(host(gu).sum(0).reshape(H, 64), g["gu"]) <= tol
+        g = load_golden_mid("wkv6_mid_state")
+        H = g["u"].shape[0]
+        r, k, v, w, u, gy, s = (dev(g[n], io) for n in ("r", "k", "v", "w", "u", "gy", "s"))
+        s_out = torch.empty_like(s)
+        check(ops.forward_ex(r, k, v, w, u, H, s0=s, s_out=s_out), g["y"], io, "mid state y")
+        check(s_out, g["s_final"], io, "mid final state")
+        gr, gk, gv, gw, gu, gs = ops.backward_ex(r, k, v, w, u, gy, H, s0=s, want_gs=True)
+        for n, t in (("gr", gr), ("gk", gk), ("gv", gv), ("gw", gw), ("gs", gs.to(io))):
+            check(t, g[n], io, "mid state " + n)
+        assert max_norm_err(host(gu).sum(0).reshape(H, 64), g["gu"]) <= tol
+        g = load_golden_mid("wkv6_mid_bi")
+        H = g["u"].shape[0]
+        r, k, v, w, u, gy = (dev(g[n], io) for n in ("r", "k", "v", "w", "u", "gy"))
+        mask = torch.from_numpy(g["mask"].astype(np.int32)).cuda()
+        check(ops.bi_forward_ex(mask, r, k, v, w, u, H), g["y"], io, "mid bi y")
+        gr, gk, gv, gw, gu = ops.bi_backward_ex(mask, r, k, v, w, u, gy, H)
+        for n, t in (("gr", gr), ("gk", gk), ("gv", gv), ("gw", gw)):
+            check(t, g[n], io, "mid bi " + n)
+            assert np.all(host(t)[2, 33:] == 0) and np.all(host(t)[1, 97:] == 0)
+        assert max_norm_err(host(gu).sum(0).reshape(H, 64), g["gu"]) <= tol
 
 
 @pytest.mark.parametrize("io", IOS, ids=["f32", "bf16"])
@@ -284,10 +284,10 @@ def test_autograd_surface(ops, oracle):
     check(leaves[1].grad, ob["gk"], bf, "WKV_6_BI gk")
 
 
-def test_two_workgroups_per_head_is_the_same_arithmetic(ops, monkeypatch):
+def test_two_workgroups_per_head_is_the_same_arithmetic(ops):
     """Few (batch, head) pairs (B*H <= half the CUs) run as two workgroups per pair -- forward: two consumer waves each, backward:
     row role / column role, each with its own producers and its own copy of G -- with the same per-wave arithmetic: every output is
-    bit-identical to the one-workgroup launch (WKV6_SPLIT forces either mode; the default picks by grid size, so the suite's small
+    bit-identical to the one-workgroup launch (dispatch(split=) forces either mode; the default picks by grid size, so the suite's small
     cases run split and the full-size ones not)."""
     bf = torch.bfloat16
     B, T, H = 3, 200, 2
@@ -297,21 +297,21 @@ def test_two_workgroups_per_head_is_the_same_arithmetic(ops, monkeypatch):
     d = [dev(x, bf) for x in (r, k, v, w, u)]
     res = []
     for split in ("0", "1"):
-        monkeypatch.setenv("WKV6_SPLIT", split)
-        s_out = torch.empty_like(s0)
-        ck = ops.new_checkpoint(B, T, 64 * H, H, s0.device)
-        y = ops.forward_ex(*d, H, s0=s0, s_out=s_out, ckpt=ck)
-        grads = ops.backward_ex(*d, dev(gy, bf), H, s0=s0, want_gs=True, ckpt=ck)
-        grads2 = ops.backward_ex(*d, dev(gy, bf), H, s0=s0, want_gs=True)          # own state pass
-        res.append([y, s_out] + list(grads) + list(grads2))
+        with ops.dispatch(split=int(split)):
+            s_out = torch.empty_like(s0)
+            ck = ops.new_checkpoint(B, T, 64 * H, H, s0.device)
+            y = ops.forward_ex(*d, H, s0=s0, s_out=s_out, ckpt=ck)
+            grads = ops.backward_ex(*d, dev(gy, bf), H, s0=s0, want_gs=True, ckpt=ck)
+            grads2 = ops.backward_ex(*d, dev(gy, bf), H, s0=s0, want_gs=True)          # own state pass
+            res.append([y, s_out] + list(grads) + list(grads2))
     for a, b in zip(*res):
         assert torch.equal(a, b)
 
 
 @pytest.mark.parametrize("segments", [2, 4, 8])
-def test_two_level_scan_forward_for_few_long_sequences(ops, oracle, monkeypatch, segments):
+def test_two_level_scan_forward_for_few_long_sequences(ops, oracle, segments):
     """Forward-only calls on few long sequences are cut into segments that run as extra workgroups (state pass per segment, a
-    chaining kernel, then the ordinary forward from each segment's entry state; wkv6_api.hip: chunk_forward).  WKV6_TSPLIT forces
+    chaining kernel, then the ordinary forward from each segment's entry state; wkv6_api.hip: chunk_forward).  dispatch(tsplit=) forces
     the segment count: y and the final state against the oracle (bf16 contract) and against the one-pass kernel (1 ulp)."""
     bf = torch.bfloat16
     B, T, H = 1, 1024, 2
@@ -321,9 +321,9 @@ def test_two_level_scan_forward_for_few_long_sequences(ops, oracle, monkeypatch,
     d = [dev(x, bf) for x in (r, k, v, w, u)]
     out = {}
     for split in (0, segments):
-        monkeypatch.setenv("WKV6_TSPLIT", str(split))
-        s_out = torch.empty(B, H, 64, 64, device="cuda", dtype=bf)
-        out[split] = (ops.forward_ex(*d, H, s0=dev(s0, bf), s_out=s_out), s_out)
+        with ops.dispatch(tsplit=split):
+            s_out = torch.empty(B, H, 64, 64, device="cuda", dtype=bf)
+            out[split] = (ops.forward_ex(*d, H, s0=dev(s0, bf), s_out=s_out), s_out)
     yo, so = oracle.forward(r, k, v, w, u, s0, return_state=True)
     check(out[segments][0], yo, bf, f"{segments}-segment forward y")
     check(out[segments][1], so, bf, f"{segments}-segment forward final state")
@@ -331,36 +331,36 @@ def test_two_level_scan_forward_for_few_long_sequences(ops, oracle, monkeypatch,
         a, b = host(a), host(b)
         assert float(np.abs(a - b).max()) <= 2.0 ** -8 * float(np.abs(a).max()), n
     # training forward: the segments' checkpoints land in the whole sequence's slots and feed the ordinary backward
-    monkeypatch.setenv("WKV6_TSPLIT", str(segments))
-    gy = rand_inputs(78, B, T, H, "init")[5]
-    ck = ops.new_checkpoint(B, T, 64 * H, H, "cuda")
-    y_ck = ops.forward_ex(*d, H, s0=dev(s0, bf), ckpt=ck)
-    assert torch.equal(y_ck, out[segments][0])
-    grads = ops.backward_ex(*d, dev(gy, bf), H, s0=dev(s0, bf), want_gs=True, ckpt=ck)
-    og = oracle.backward(r, k, v, w, u, gy, s0)
-    for n, t in zip(("gr", "gk", "gv", "gw"), grads[:4]):
-        check(t, og[n], bf, f"{segments}-segment forward checkpoints -> backward {n}")
+    with ops.dispatch(tsplit=segments):
+        gy = rand_inputs(78, B, T, H, "init")[5]
+        ck = ops.new_checkpoint(B, T, 64 * H, H, "cuda")
+        y_ck = ops.forward_ex(*d, H, s0=dev(s0, bf), ckpt=ck)
+        assert torch.equal(y_ck, out[segments][0])
+        grads = ops.backward_ex(*d, dev(gy, bf), H, s0=dev(s0, bf), want_gs=True, ckpt=ck)
+        og = oracle.backward(r, k, v, w, u, gy, s0)
+        for n, t in zip(("gr", "gk", "gv", "gw"), grads[:4]):
+            check(t, og[n], bf, f"{segments}-segment forward checkpoints -> backward {n}")
     # the stateful inference operator (fp32 state in place, decay given as exp(-exp(w))) takes the same path for a prefill
     from rwkv_lm_ext_amd.wkv6_op import rwkv6
     decay = torch.exp(-torch.exp(torch.from_numpy(w))).cuda().contiguous()
     res = []
     for split in (0, segments):
-        monkeypatch.setenv("WKV6_TSPLIT", str(split))
-        state = torch.from_numpy(s0).cuda().contiguous()
-        y = torch.empty(B, T, 64 * H, device="cuda", dtype=bf)
-        rwkv6.forward_bf16(B, T, 64 * H, H, state, d[0], d[1], d[2], decay, d[4], y)
-        res.append((y, state))
+        with ops.dispatch(tsplit=split):
+            state = torch.from_numpy(s0).cuda().contiguous()
+            y = torch.empty(B, T, 64 * H, device="cuda", dtype=bf)
+            rwkv6.forward_bf16(B, T, 64 * H, H, state, d[0], d[1], d[2], decay, d[4], y)
+            res.append((y, state))
     check(res[1][0], yo, bf, "rwkv6 prefill y")
     assert max_norm_err(host(res[1][1]), so) <= 1e-3
     assert float((res[0][0].float() - res[1][0].float()).abs().max()) <= 2.0 ** -8 * float(res[0][0].float().abs().max())
 
 
 @pytest.mark.parametrize("segments", [2, 4, 8])
-def test_two_level_scan_backward_for_few_long_sequences(ops, oracle, monkeypatch, segments):
+def test_two_level_scan_backward_for_few_long_sequences(ops, oracle, segments):
     """The backward of few long sequences as a two-level scan over T (wkv6_api.hip: chunk_backward): every segment runs as its own
     workgroup from the adjoint state entering it from the future (reversed state-only pass with k := r, v := gy, chained last to
     first) and from the gw suffix sum beyond its end (Phi = sum_j G S at the boundary); gu sums over the segments, gs is the adjoint
-    state at the sequence start.  WKV6_TSPLIT forces the segment count: every gradient against the oracle (bf16 contract, fp32
+    state at the sequence start.  dispatch(tsplit=) forces the segment count: every gradient against the oracle (bf16 contract, fp32
     partials) and against the one-pass backward, with the forward's checkpoints and self-contained."""
     bf = torch.bfloat16
     B, T, H = 2, 1024, 2
@@ -371,11 +371,11 @@ def test_two_level_scan_backward_for_few_long_sequences(ops, oracle, monkeypatch
     og = oracle.backward(r, k, v, w, u, gy, s0)
     res = {}
     for split in (0, segments):
-        monkeypatch.setenv("WKV6_TSPLIT", str(split))
-        ck = ops.new_checkpoint(B, T, 64 * H, H, "cuda")
-        ops.forward_ex(*d[:5], H, s0=dev(s0, bf), ckpt=ck)
-        res[split] = (ops.backward_ex(*d, H, s0=dev(s0, bf), want_gs=True, ckpt=ck),          # the forward's checkpoints
-                      ops.backward_ex(*d, H, s0=dev(s0, bf), want_gs=True))                    # self-contained
+        with ops.dispatch(tsplit=split):
+            ck = ops.new_checkpoint(B, T, 64 * H, H, "cuda")
+            ops.forward_ex(*d[:5], H, s0=dev(s0, bf), ckpt=ck)
+            res[split] = (ops.backward_ex(*d, H, s0=dev(s0, bf), want_gs=True, ckpt=ck),          # the forward's checkpoints
+                          ops.backward_ex(*d, H, s0=dev(s0, bf), want_gs=True))                    # self-contained
     for kept, grads in zip(("kept checkpoints", "self-contained"), res[segments]):
         for n, t in zip(("gr", "gk", "gv", "gw"), grads[:4]):
             check(t, og[n], bf, f"{segments}-segment backward ({kept}) {n}")
