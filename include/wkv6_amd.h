@@ -233,11 +233,13 @@ int wkv6_selftest(void* stream);
  * wkv6_set_dispatch: overrides one of the library's launch-shape choices, process-wide (tests and A/Bs reach every mode with it).
  * WKV6_DISPATCH_SPLIT: != 0 forces two workgroups per (batch, head), 0 forces one.
  * WKV6_DISPATCH_BI_FUSED: 0 runs the two halves of wkv6_bi as two launches, any other value leaves the choice to the library.
- * WKV6_DISPATCH_TSPLIT: 0 or 1 turns the two-level forward over T off, n forces n segments where T % (64 n) == 0 (off otherwise). */
+ * WKV6_DISPATCH_TSPLIT: 0 or 1 turns the two-level forward over T off, n forces n segments where T % (64 n) == 0 (off otherwise).
+ * WKV6_DISPATCH_BI_SLOTS: n >= 1 makes both persistent wkv6_bi launches use min(n, B*H) workgroup slots instead of min(B*H, CUs)
+ * (so that a test pins the rows each slot walks on any CU count); WKV6_DISPATCH_SPLIT and WKV6_DISPATCH_BI_FUSED = 0 take precedence. */
 void wkv6_set_clock_ring(void* buf, int n_slots, int n_launches);
 void wkv6_clock_ring_counts(long* fwd, long* bwd);
 int wkv6_pass_marker(void* stream);
-enum { WKV6_DISPATCH_SPLIT = 0, WKV6_DISPATCH_BI_FUSED = 1, WKV6_DISPATCH_TSPLIT = 2 };
+enum { WKV6_DISPATCH_SPLIT = 0, WKV6_DISPATCH_BI_FUSED = 1, WKV6_DISPATCH_TSPLIT = 2, WKV6_DISPATCH_BI_SLOTS = 3 };
 /* value -1: the library's own choice (default).  Returns the previous value, or WKV6_EINVAL for an unknown selector. */
 int wkv6_set_dispatch(int what, int value);
 /* "major.minor" of the library. */

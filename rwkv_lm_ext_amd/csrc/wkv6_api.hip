@@ -14,7 +14,7 @@ using namespace wkv6;
 // the device's CU count; wkv6_set_dispatch() (include/wkv6_amd.h) overrides them, so that tests can reach every mode at small shapes.
 namespace wkv6 {
 namespace {
-std::atomic<int> g_dispatch[3] = {-1, -1, -1};    // by WKV6_DISPATCH_*; -1: the library's own choice
+std::atomic<int> g_dispatch[4] = {-1, -1, -1, -1};    // by WKV6_DISPATCH_*; -1: the library's own choice
 int dispatch_override(int what) { return g_dispatch[what].load(std::memory_order_relaxed); }
 }  // namespace
 
@@ -36,11 +36,14 @@ int want_split(int BH)
     if (const int o = dispatch_override(WKV6_DISPATCH_SPLIT); o != -1) return o != 0;
     return 2 * BH <= cu_count();
 }
-// workgroup slots of the persistent wkv6_bi launches: one per CU at most (0: the halves run as two launches)
+// workgroup slots of the persistent wkv6_bi launches: one per CU at most (0: the halves run as two launches).  An override n >= 1 pins
+// min(n, BH) slots, more than the CUs included: the slots never wait for one another (workgroup-private scratch, LDS-only tags), and the
+// compact side buffers' slot carve (slot * T * 64) stays inside the [B,T,C] buffers as long as slots <= BH.
 int bi_slots(int BH)
 {
     if (want_split(BH)) return 0;
     if (dispatch_override(WKV6_DISPATCH_BI_FUSED) == 0) return 0;
+    if (const int want = dispatch_override(WKV6_DISPATCH_BI_SLOTS); want >= 1) return BH < want ? BH : want;
     const int cus = cu_count();
     return cus > 0 ? (BH < cus ? BH : cus) : 0;
 }
@@ -411,7 +414,7 @@ int wkv6_pass_marker(void* stream)
 }
 int wkv6_set_dispatch(int what, int value)
 {
-    if (what < WKV6_DISPATCH_SPLIT || what > WKV6_DISPATCH_TSPLIT) return WKV6_EINVAL;
+    if (what < WKV6_DISPATCH_SPLIT || what > WKV6_DISPATCH_BI_SLOTS) return WKV6_EINVAL;
     return wkv6::g_dispatch[what].exchange(value);
 }
 
@@ -631,12 +634,14 @@ int wkv6_backward_pair_ex(int B, int T, int C, int H, const void* u, const wkv6_
     return to_rc(launch_chunk_bwd_pair(a[0], a[1], (hipStream_t)stream));
 }
 
-// The chunked halves of wkv6_bi address their fp32 side buffers with 32-bit byte offsets (buffer resources): (T + 128) C fp32 elements must
-// stay below 2^32 bytes (where two workgroups serve a pair the side buffers are [B,T,C] arrays; the one-launch path's are [T][64]).
+// The chunked halves of wkv6_bi address their fp32 side buffers with 32-bit byte offsets (buffer resources; where two workgroups serve a
+// pair the side buffers are [B,T,C] arrays, the one-launch path's are [T][64]).  Measured: the chunked backward agrees with the scan kernels
+// at T = 2^23 - 1 (C = 64) and puts gr off at scattered reverse-scan group starts (and gw, through its suffix sum, everywhere) once a row's
+// fp32 byte offsets pass 2^31, at T = 2^23 + 4096 and 2^24 - 129 -- so (T + 128) C fp32 elements must stay below 2^31 bytes, not 2^32.
 // Longer rows take the exact scan kernels, whose indices are 64-bit -- decided before the call enqueues anything.
 static unsigned bi_route(unsigned flags, int T, int C)
 {
-    if (!(flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN)) && ((long)T + 128) * C >= (1L << 30)) flags |= WKV6_ALGO_SCAN;
+    if (!(flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN)) && ((long)T + 128) * C >= (1L << 29)) flags |= WKV6_ALGO_SCAN;
     return flags;
 }
 

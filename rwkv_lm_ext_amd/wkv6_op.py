@@ -491,17 +491,19 @@ def pass_marker():
     _lib.check(_lib.load().wkv6_pass_marker(_stream_ptr()), "wkv6_pass_marker")
 
 
-_DISPATCH = {"split": 0, "bi_fused": 1, "tsplit": 2}      # WKV6_DISPATCH_* of include/wkv6_amd.h
+_DISPATCH = {"split": 0, "bi_fused": 1, "tsplit": 2, "bi_slots": 3}      # WKV6_DISPATCH_* of include/wkv6_amd.h
 
 
 @contextlib.contextmanager
-def dispatch(split=None, bi_fused=None, tsplit=None):
+def dispatch(split=None, bi_fused=None, tsplit=None, bi_slots=None):
     """Override the library's launch-shape choices for the body (wkv6_set_dispatch, include/wkv6_amd.h), process-wide; None leaves a
     choice alone.  split: != 0 forces two workgroups per (batch, head), 0 one.  bi_fused = 0: the halves of wkv6_bi as two launches.
-    tsplit: 0 / 1 turns the two-level forward over T off, n forces n segments where T % (64 n) == 0.  The previous values come back on
-    exit, exceptions included."""
+    tsplit: 0 / 1 turns the two-level forward over T off, n forces n segments where T % (64 n) == 0.  bi_slots = n >= 1: the persistent
+    wkv6_bi launches use min(n, B*H) workgroup slots (-1: min(B*H, CUs)); split and bi_fused = 0 take precedence.  The previous values
+    come back on exit, exceptions included."""
     lib = _lib.load()
-    given = {name: v for name, v in (("split", split), ("bi_fused", bi_fused), ("tsplit", tsplit)) if v is not None}
+    given = {name: v for name, v in (("split", split), ("bi_fused", bi_fused), ("tsplit", tsplit), ("bi_slots", bi_slots))
+             if v is not None}
     prev = {}
     try:
         for name, v in given.items():

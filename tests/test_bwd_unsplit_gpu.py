@@ -273,14 +273,14 @@ def test_chained_persistent_launches_equal_the_two_launch_halves_bit_for_bit(ops
     the stage -> LDS slot maps rotate across the call boundary) and fused the fp32-ew kind: every wave still does the arithmetic of the plain
     two-launch kernels (dispatch(bi_fused=0)), so forward and backward must agree BIT FOR BIT -- on rows of every chaining case: fewer than two
     stages (not chained, nor chained into), exactly two, odd and even stage counts, several rows per workgroup slot."""
-    B, T, H = 12, 330, 32                                             # 384 rows on 256 slots: a second row behind half of the slots
+    B, T, H = 12, 330, 32                                             # 384 rows on 256 slots (pinned: any CU count): a second row behind half of the slots
     lens = torch.tensor([330, 0, 1, 32, 33, 64, 65, 96, 97, 128, 200, 313], dtype=torch.int32, device="cuda")
     d = [dev(t, BF) for t in rand_inputs(9393, B, T, H, "stress")]
     if ew:
         d[3] = (-torch.exp(d[3].float())).contiguous()
     outs = {}
     for mode in ("1", "0"):
-        with ops.dispatch(bi_fused=int(mode)):
+        with ops.dispatch(bi_fused=int(mode), bi_slots=256):
             ws = ops.bi_new_workspace(B, T, H * 64, H, "cuda")
             y = ops.bi_forward_ex(None, *d[:5], H, ws=ws, lens=lens, w_is_ew=ew)
             g = ops.bi_backward_ex(None, *d, H, ws=ws, lens=lens, w_is_ew=ew)

@@ -248,15 +248,15 @@ def test_dispatch_override_host_bookkeeping():
     from rwkv_lm_ext_amd import _lib, wkv6_op
     lib = _lib.load()
     EINVAL = -1
-    for what in (0, 1, 2):                                   # WKV6_DISPATCH_SPLIT, _BI_FUSED, _TSPLIT
+    for what in (0, 1, 2, 3):                                # WKV6_DISPATCH_SPLIT, _BI_FUSED, _TSPLIT, _BI_SLOTS
         assert lib.wkv6_set_dispatch(what, 3) == -1          # default: the library's own choice
         assert lib.wkv6_set_dispatch(what, 0) == 3
         assert lib.wkv6_set_dispatch(what, -1) == 0
         assert lib.wkv6_set_dispatch(what, -1) == -1
-    assert lib.wkv6_set_dispatch(3, 1) == EINVAL and lib.wkv6_set_dispatch(-1, 1) == EINVAL
+    assert lib.wkv6_set_dispatch(4, 1) == EINVAL and lib.wkv6_set_dispatch(-1, 1) == EINVAL
     with pytest.raises(ZeroDivisionError):
-        with wkv6_op.dispatch(split=1, tsplit=4):
-            assert lib.wkv6_set_dispatch(0, 1) == 1 and lib.wkv6_set_dispatch(2, 4) == 4
+        with wkv6_op.dispatch(split=1, tsplit=4, bi_slots=7):
+            assert lib.wkv6_set_dispatch(0, 1) == 1 and lib.wkv6_set_dispatch(2, 4) == 4 and lib.wkv6_set_dispatch(3, 7) == 7
             assert lib.wkv6_set_dispatch(1, -1) == -1        # (not given: left alone)
             1 // 0
-    assert [lib.wkv6_set_dispatch(what, -1) for what in (0, 1, 2)] == [-1, -1, -1]
+    assert [lib.wkv6_set_dispatch(what, -1) for what in (0, 1, 2, 3)] == [-1, -1, -1, -1]
