@@ -185,7 +185,8 @@ int wkv6_backward_pair_ex(int B, int T, int C, int H, const void* u, const wkv6_
 /* ---- elementwise neighbours of the operator in the RWKV-6 time-mix block; bf16 only ----
  * ddlerp (src/model.py:435-448): xx = shift(x) - x; out[s] = x + xx * (maa[s] + m[s]), s < NS.
  *   x [B,T,C]; shifted0 [B,C] = token in front of each row (NULL: zero, nn.ZeroPad2d((0,0,1,-1))); m [NS,B,T,C] or NULL;
- *   maa [NS,C]; out [NS,B,T,C].  Supported: (NS=1, m NULL or not), (NS=5, m given).
+ *   maa [NS,C]; out [NS,B,T,C].  Supported: (NS=1, m NULL or not), (NS=5, m given), (NS=2, m NULL: the channel-mix FFN's
+ *   two lerps); any other pair returns WKV6_EUNSUPPORTED.
  * backward: dx [B,T,C], dm [NS,B,T,C] (NULL iff m NULL), dmaa_part fp32 [nparts,NS,C] partial sums (caller adds them). */
 int wkv6_ddlerp_forward(int B, int T, int C, int NS, const void* x, const void* shifted0, const void* m, const void* maa,
                         void* out, void* stream);

@@ -49,6 +49,24 @@ def bf16_report(out, ref, floor=1e-3):
     return rel_rms, frac_off, max_ulps
 
 
+def bf16_report_torch(out, ref, floor=1e-3):
+    """bf16_report on torch tensors, computed in fp64 where they live (a GPU test's 10^8-element outputs never leave the device).
+    The same three numbers: RNE_bf16 of the reference taken through fp32 as there, the same floors."""
+    import torch
+    out = out.to(torch.float64)
+    ref = ref.to(torch.float64)
+    want = ref.to(torch.float32).to(torch.bfloat16).to(torch.float64)
+    d = out - want
+    rms = max(float(ref.square().mean().sqrt()), floor)
+    rel_rms = float(d.square().mean().sqrt()) / rms
+    floor = max(1e-2 * float(ref.abs().max()), floor)
+    big = ref.abs() >= floor
+    frac_off = float((d[big] != 0).double().mean()) if bool(big.any()) else 0.0
+    ulp = ref.abs().clamp_min(floor) * 2.0 ** -7
+    max_ulps = float((d.abs() / ulp).max())
+    return rel_rms, frac_off, max_ulps
+
+
 def bf16_ok(out, ref, floor=1e-3, exact=BF16_EXACT):
     """(passed, message) of the bf16 contract for one tensor."""
     rms, off, ulps = bf16_report(out, ref, floor)

@@ -82,7 +82,8 @@ __global__ void ddlerp_fwd_kernel(const LerpArgs a)
 }
 
 // Backward: dx_t = sum_s dout_{s,t} (1 - c_{s,t}) + sum_s dout_{s,t+1} c_{s,t+1}  (c = maa + m; the second term is the adjoint
-// of the token shift), dm_{s,t} = dout_{s,t} xx_t, dmaa_s = sum_rows dout_s xx.  Workgroup p handles rows p, p + nparts, ...
+// of the token shift), dm_{s,t} = dout_{s,t} xx_t, dmaa_s = sum_rows dout_s xx.  Plain stream: workgroup p walks the contiguous
+// rows [p per, (p + 1) per), per = ceil(rows / nparts), backwards; reversed-span streams: workgroup p handles rows p, p + nparts, ...
 template <int NS, bool HAS_M>
 __global__ void ddlerp_bwd_kernel(const LerpArgs a)
 {
@@ -282,7 +283,7 @@ template <bool BWD> __global__ __launch_bounds__(256) void sqrelu_kernel(const F
             float d[8];
             ld8(a.dout + 8 * i, d);
 #pragma unroll
-            for (int q = 0; q < 8; ++q) o[q] = 2.f * fmaxf(x[q], 0.f) * d[q];
+            for (int q = 0; q < 8; ++q) o[q] = fmaxf(x[q], 0.f) * d[q] * 2.f;   // r d first: exact, so inf only where 2 r d overflows
             st8(a.da + 8 * i, o);
         } else {
 #pragma unroll
