@@ -143,6 +143,29 @@ int wkv6bi_backward_ex(int B, int T, int C, int H, const int* mask, const int* l
 size_t wkv6bi_workspace_bytes(int B, int T, int C, int H);
 size_t wkv6bi_kept_bytes(int B, int T, int C, int H);
 
+/* ---- wkv5 (RWKV-5: the decay is a parameter, constant over batch and time): replaces cuda_forward / cuda_backward of
+ * cuda/wkv5_op.cpp:5-6 (cuda/wkv5_cuda.cu:190-202).  w, u : [H,N];  gw, gu : [B,C] per-batch partials (the caller sums them over
+ * the batch, src/model.py:283-284).  `eew` is the fp32 decay exp(-exp(w_raw)) and `ew` the fp32 -exp(w_raw) that src/model.py:260-261
+ * builds; gw is the gradient with respect to the RAW w (gw[b][i] = ew[i] eew[i] dL_b/d eew[i], cuda/wkv5_cuda.cu:119-143) and is
+ * exactly 0 for T <= 2.  Exact fp32 token-serial kernels with the decay, u and the gw / gu sums in registers: 8 B per token-channel
+ * in the forward (r, k, v in, y out), 14 B of tensors in the backward (r, k, v, gy in, gr, gk, gv out), no workspace, no atomics
+ * (results are bit-reproducible).  gw, gu may be NULL (skipped). */
+int wkv5_cuda_forward(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* eew, const void* u,
+                      void* y, void* stream);
+int wkv5_cuda_backward(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* eew, const float* ew,
+                       const void* u, const void* gy, void* gr, void* gk, void* gv, void* gw, void* gu, void* stream);
+/* The same with flags (declared below; any other bit returns WKV6_EUNSUPPORTED):
+ *   WKV6_W_RAW         w is the raw [H,N] parameter in the I/O type, decay and ew are formed in the kernel (`ew` is ignored, may be NULL);
+ *                      without it w is the fp32 decay and the backward needs `ew` unless gw is NULL
+ *   WKV6_IO_F32        every bf16 tensor (w under WKV6_W_RAW and the partials included) is fp32
+ *   WKV6_PARTIALS_F32  gw, gu [B,C] are fp32: the parameter gradient is rounded once, after the caller's sum over the batch
+ *   WKV6_ALGO_SCAN     accepted, no effect: these are the only kernels of the operator */
+int wkv5_forward_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v, const void* w, const void* u,
+                    void* y, unsigned flags, void* stream);
+int wkv5_backward_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v, const void* w, const float* ew,
+                     const void* u, const void* gy, void* gr, void* gk, void* gv, void* gw, void* gu, unsigned flags,
+                     void* stream);
+
 /* ---- partially reversed sequences: replaces the torch.gather round trips around the operator in the
  * bidirectional compositions -- src/model_bi.py:331-348 (k, v reversed, y un-reversed) and src/model_ext.py:410-437 (every
  * tensor reversed).  For batch row b, tokens [0, rev_n[b]) of the tensors named in rev_mask are read in reverse order (scan

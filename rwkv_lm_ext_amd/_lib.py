@@ -66,6 +66,14 @@ SIGNATURES = {
     "wkv6_amd_version": (ctypes.c_char_p, []),
 }
 
+# the RWKV-5 operator's symbols of the same header (a table of their own: SIGNATURES is the list of the header's wkv6 / rwkv6 names)
+SIGNATURES_WKV5 = {
+    "wkv5_cuda_forward": (_I, [_I] * 4 + [_VP] * 7),
+    "wkv5_cuda_backward": (_I, [_I] * 4 + [_VP] * 13),
+    "wkv5_forward_ex": (_I, [_I] * 4 + [_VP] * 6 + [_U, _VP]),
+    "wkv5_backward_ex": (_I, [_I] * 4 + [_VP] * 12 + [_U, _VP]),
+}
+
 # flags of include/wkv6_amd.h
 W_EW_F32, W_RAW, IO_F32, S0_PER_BATCH, ALGO_SCAN, CKPT_VALID, BI_KEEP_CKPT, PARTIALS_F32 = 0, 1, 2, 4, 16, 32, 64, 128
 REV_R, REV_K, REV_V, REV_W, REV_Y, REV_ALL = 1, 2, 4, 8, 16, 31      # wkv6_*_rev_ex: tensors held in reversed order
@@ -95,7 +103,7 @@ def load():
             if not os.path.exists(path):
                 raise ImportError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
             lib = ctypes.CDLL(path)
-            for name, (res, args) in SIGNATURES.items():
+            for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_WKV5.items()):
                 fn = getattr(lib, name)          # AttributeError if the ABI is incomplete
                 fn.restype = res
                 fn.argtypes = args

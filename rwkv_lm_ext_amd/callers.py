@@ -3,6 +3,7 @@
 Parameter names equal the reference's state_dict keys, so a reference checkpoint loads with ``load_state_dict``.
 
   reverse helpers      src/model_ext.py:398-419 (create_mask, reverse_x_idx, reverse_x)            SURVEY a12
+  RWKV_Tmix_x052       src/model.py:292-374 (RWKV-5 time-mix: static lerps, static decay, WKV5 operator)
   Tmix_x060            src/model.py:376-477 == src/model_encoder_run.py:96-186 (time-mix)          SURVEY a13
   CMix_x060            src/model.py:616-644 == src/model_encoder_run.py:189-219 (channel-mix)      SURVEY a14
   Tmix_x060.forward_bi_c   composition C: (WKV(x) + unrev(WKV(rev x))) / 2, src/model_ext.py:421-437    SURVEY a15
@@ -326,3 +327,79 @@ def info_nce_loss(query, positive, negative=None, scale=20.0):
         scores = torch.cat([scores, pairwise_cos_sim(query, negative).unsqueeze(1) * scale], dim=1)
     labels = torch.arange(scores.shape[0], dtype=torch.long, device=scores.device)
     return F.cross_entropy(scores, labels)
+
+
+# ---- RWKV-5 time-mix (src/model.py:292-374) ------------------------------------------------------------------------
+def _default_wkv5(B, T, C, H, r, k, v, w, u):
+    from .wkv import RUN_CUDA_RWKV5
+    bf = torch.bfloat16
+    y = RUN_CUDA_RWKV5(B, T, C, H, *(t.to(bf).contiguous() for t in (r, k, v, w, u)))
+    return y.to(r.dtype)
+
+
+class RWKV_Tmix_x052(nn.Module):
+    """RWKV-5 time-mix around the WKV5 operator (RWKV_TimeMix_RWKV5, src/model.py:292-374): token shift, four static lerps,
+    r / k / v / gate projections, the operator with the [H,N] parameters time_decay (raw w) and time_faaaa (u),
+    GroupNorm_H(y / head_size_divisor) * silu-gate, output projection.  Parameter names are the reference's state_dict keys;
+    everything around the operator is plain PyTorch."""
+
+    def __init__(self, n_embd, dim_att, head_size=64, head_size_divisor=8, wkv=None):
+        super().__init__()
+        assert dim_att % head_size == 0
+        self.n_head = dim_att // head_size
+        self.head_size_divisor = head_size_divisor
+        self.wkv = wkv or _default_wkv5
+        z = lambda *s: nn.Parameter(torch.zeros(*s))
+        for n in ("k", "v", "r", "g"):
+            setattr(self, "time_mix_" + n, z(1, 1, n_embd))
+        self.time_decay = z(self.n_head, head_size)
+        self.time_faaaa = z(self.n_head, head_size)
+        self.receptance = nn.Linear(n_embd, dim_att, bias=False)
+        self.key = nn.Linear(n_embd, dim_att, bias=False)
+        self.value = nn.Linear(n_embd, dim_att, bias=False)
+        self.output = nn.Linear(dim_att, n_embd, bias=False)
+        self.gate = nn.Linear(n_embd, dim_att, bias=False)
+        self.ln_x = nn.GroupNorm(self.n_head, dim_att)
+
+    @torch.no_grad()
+    def init_like_reference(self, layer_id, n_layer):
+        """The reference's initial values of the mix weights, the decay ramp and the bonus (src/model.py:304-329)."""
+        n_embd, dim_att = self.time_mix_k.shape[-1], self.time_decay.numel()
+        r01 = layer_id / max(n_layer - 1, 1)
+        r10 = 1.0 - layer_id / n_layer
+        ddd = (torch.arange(n_embd, dtype=torch.float32) / n_embd).view(1, 1, n_embd)
+        self.time_mix_k.copy_(ddd.pow(r10))
+        self.time_mix_v.copy_(ddd.pow(r10) + 0.3 * r01)
+        self.time_mix_r.copy_(ddd.pow(0.5 * r10))
+        self.time_mix_g.copy_(ddd.pow(0.5 * r10))
+        n = torch.arange(dim_att, dtype=torch.float32)
+        self.time_decay.copy_((-6 + 5 * (n / (dim_att - 1)) ** (0.7 + 1.3 * r01)).view_as(self.time_decay))
+        zigzag = ((n + 1) % 3 - 1) * 0.1
+        self.time_faaaa.copy_((r01 * (1 - n / (dim_att - 1)) + zigzag).view_as(self.time_faaaa))
+        return self
+
+    def jit_func(self, x):
+        xx = F.pad(x, (0, 0, 1, -1))                                    # nn.ZeroPad2d((0, 0, 1, -1))
+        xk = x * self.time_mix_k + xx * (1 - self.time_mix_k)
+        xv = x * self.time_mix_v + xx * (1 - self.time_mix_v)
+        xr = x * self.time_mix_r + xx * (1 - self.time_mix_r)
+        xg = x * self.time_mix_g + xx * (1 - self.time_mix_g)
+        return self.receptance(xr), self.key(xk), self.value(xv), F.silu(self.gate(xg))
+
+    def jit_func_2(self, x, g):
+        B, T, C = x.size()
+        # GroupNorm_H(y / divisor) written out on [B*T, H, N] in at least fp32 (y / 8 has a variance not far above eps), then back to
+        # the module's dtype for the gate and the output projection
+        H = self.n_head
+        ct = torch.promote_types(x.dtype, torch.float32)
+        xh = x.reshape(B * T, H, C // H).to(ct) / self.head_size_divisor
+        xh = xh - xh.mean(-1, keepdim=True)
+        xh = xh * torch.rsqrt(xh.square().mean(-1, keepdim=True) + self.ln_x.eps)
+        x = (xh.reshape(B * T, C) * self.ln_x.weight.to(ct) + self.ln_x.bias.to(ct)).to(g.dtype).view(B, T, C)
+        return self.output(x * g)
+
+    def forward(self, x):
+        r, k, v, g = self.jit_func(x)
+        B, T, C = r.shape
+        y = self.wkv(B, T, C, self.n_head, r, k, v, self.time_decay, self.time_faaaa)
+        return self.jit_func_2(y, g)

@@ -1,7 +1,7 @@
 // C++ torch-extension shim over the C ABI of librwkv6_amd.so (include/wkv6_amd.h): the pybind module and the
 // TORCH_LIBRARY registrations that the reference builds from cuda/wkv6_op.cpp:8-22, cuda/wkv6_bi_op.cpp:8-22,
-// cuda/wkv6state_op.cpp:8-22, cuda/wkv6infctx_op.cpp:8-22 and cuda/rwkv6_op.cpp:12-34 -- same operator names and
-// positional signatures (caller-allocated outputs, in-place writes, void return), one extension instead of five.
+// cuda/wkv6state_op.cpp:8-22, cuda/wkv6infctx_op.cpp:8-22, cuda/rwkv6_op.cpp:12-34 and cuda/wkv5_op.cpp:8-22 -- same operator names
+// and positional signatures (caller-allocated outputs, in-place writes, void return), one extension instead of six.
 // What the reference shims do not do and this one does: device guard, launch on the current stream of the tensors'
 // device, dtype / contiguity / shape checks, error codes turned into exceptions.
 //
@@ -178,6 +178,36 @@ void rwkv6_forward_fp16(int64_t B, int64_t T, int64_t C, int64_t H, Tensor& stat
                                u.data_ptr(), y.data_ptr(), stream_of(r)), "rwkv6 forward_fp16");
 }
 
+// ---- wkv5 (cuda/wkv5_op.cpp:8-13): w = fp32 decay eew [H,N], ww = fp32 ew [H,N]; gw, gu [B,C] per-batch partials
+void need_hn(const Tensor& t, const char* name, int64_t H, at::ScalarType dt, const Tensor& like)
+{
+    need(t, name, dt, like);
+    TORCH_CHECK(t.numel() == H * 64, name, " must be [H,N]");
+}
+void wkv5_forward(int64_t B, int64_t T, int64_t C, int64_t H, Tensor& r, Tensor& k, Tensor& v, Tensor& w, Tensor& u, Tensor& y)
+{
+    need_sizes(B, T, C, H);
+    need_btc(r, "r", B, T, C, BF, r); need_btc(k, "k", B, T, C, BF, r); need_btc(v, "v", B, T, C, BF, r);
+    need_hn(w, "w", H, F32, r); need_hn(u, "u", H, BF, r); need_btc(y, "y", B, T, C, BF, r);
+    const DeviceGuard guard(r.device());
+    ok(wkv5_cuda_forward(B, T, C, H, r.data_ptr(), k.data_ptr(), v.data_ptr(), w.data_ptr<float>(), u.data_ptr(), y.data_ptr(),
+                         stream_of(r)), "wkv5 forward");
+}
+void wkv5_backward(int64_t B, int64_t T, int64_t C, int64_t H, Tensor& r, Tensor& k, Tensor& v, Tensor& w, Tensor& ww, Tensor& u,
+                   Tensor& gy, Tensor& gr, Tensor& gk, Tensor& gv, Tensor& gw, Tensor& gu)
+{
+    need_sizes(B, T, C, H);
+    need_btc(r, "r", B, T, C, BF, r); need_btc(k, "k", B, T, C, BF, r); need_btc(v, "v", B, T, C, BF, r);
+    need_hn(w, "w", H, F32, r); need_hn(ww, "ww", H, F32, r); need_hn(u, "u", H, BF, r); need_btc(gy, "gy", B, T, C, BF, r);
+    need_btc(gr, "gr", B, T, C, BF, r); need_btc(gk, "gk", B, T, C, BF, r); need_btc(gv, "gv", B, T, C, BF, r);
+    need(gw, "gw", BF, r); need(gu, "gu", BF, r);
+    TORCH_CHECK(gw.numel() == B * C && gu.numel() == B * C, "gw and gu must be [B,C]");
+    const DeviceGuard guard(r.device());
+    ok(wkv5_cuda_backward(B, T, C, H, r.data_ptr(), k.data_ptr(), v.data_ptr(), w.data_ptr<float>(), ww.data_ptr<float>(),
+                          u.data_ptr(), gy.data_ptr(), gr.data_ptr(), gk.data_ptr(), gv.data_ptr(), gw.data_ptr(), gu.data_ptr(),
+                          stream_of(r)), "wkv5 backward");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -199,6 +229,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     rw.def("forward_bf16", &rwkv6_forward_bf16, "rwkv6 forward_bf16");
     rw.def("forward_fp16", &rwkv6_forward_fp16, "rwkv6 forward_fp16");
     rw.def("forward_fp32", &rwkv6_forward_fp32, "rwkv6 forward_fp32");
+    auto w5 = m.def_submodule("wkv5");
+    w5.def("forward", &wkv5_forward, "wkv5 forward");
+    w5.def("backward", &wkv5_backward, "wkv5 backward");
 }
 
 #ifndef WKV6_SHIM_PREFIX
@@ -218,3 +251,4 @@ WKV6_SHIM_TORCH_LIBRARY(WKV6_SHIM_LIB(wkv6bi), m) { m.def("forward", wkv6bi_forw
 WKV6_SHIM_TORCH_LIBRARY(WKV6_SHIM_LIB(wkv6state), m) { m.def("forward", state_forward<false>); m.def("backward", state_backward<false>); }
 WKV6_SHIM_TORCH_LIBRARY(WKV6_SHIM_LIB(wkv6infctx), m) { m.def("forward", state_forward<true>); m.def("backward", state_backward<true>); }
 WKV6_SHIM_TORCH_LIBRARY(WKV6_SHIM_LIB(rwkv6), m) { m.def("forward_bf16", rwkv6_forward_bf16); m.def("forward_fp16", rwkv6_forward_fp16); m.def("forward_fp32", rwkv6_forward_fp32); }
+WKV6_SHIM_TORCH_LIBRARY(WKV6_SHIM_LIB(wkv5), m) { m.def("forward", wkv5_forward); m.def("backward", wkv5_backward); }

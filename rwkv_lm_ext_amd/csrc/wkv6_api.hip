@@ -1,6 +1,7 @@
 // extern "C" entry points of librwkv6_amd.so (declared in include/wkv6_amd.h).
 #include "../../include/wkv6_amd.h"
 #include "wkv6_scan.h"
+#include "wkv5_scan.h"
 
 #include <atomic>
 #include <mutex>
@@ -724,6 +725,47 @@ int wkv6bi_backward_ex(int B, int T, int C, int H, const int* mask, const int* l
     if (hipError_t e = run_bwd(a, flags, ws.scan[0], st)) return (int)e;             // adjoint of the forward scan
     a.reverse = 1; a.use_u = 0; a.accumulate = 1; a.zero_tail = 0; a.gu = nullptr;   // adjoint of the reverse scan
     return to_rc(run_bwd(a, flags, ws.scan[1], st));
+}
+
+// ---- wkv5: the static-decay operator (wkv5_scan.h).  Exact token-serial kernels only; no workspace ----------------
+int wkv5_forward_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v, const void* w, const void* u,
+                    void* y, unsigned flags, void* stream)
+{
+    if (int rc = check_shape(B, T, C, H)) return rc;
+    if (!r || !k || !v || !w || !u || !y) return WKV6_ENULL;
+    if (flags & ~(unsigned)(WKV6_W_RAW | WKV6_IO_F32 | WKV6_PARTIALS_F32 | WKV6_ALGO_SCAN)) return WKV6_EUNSUPPORTED;
+    Wkv5Args a = {};
+    a.B = B; a.T = T; a.C = C; a.H = H;
+    a.r = r; a.k = k; a.v = v; a.w = w; a.u = u; a.y = y;
+    a.wkind = (flags & WKV6_W_RAW) ? 1 : 0;
+    return to_rc(launch_wkv5_fwd(a, flags & WKV6_IO_F32, (hipStream_t)stream));
+}
+int wkv5_backward_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v, const void* w, const float* ew,
+                     const void* u, const void* gy, void* gr, void* gk, void* gv, void* gw, void* gu, unsigned flags,
+                     void* stream)
+{
+    if (int rc = check_shape(B, T, C, H)) return rc;
+    if (!r || !k || !v || !w || !u || !gy || !gr || !gk || !gv) return WKV6_ENULL;
+    if (!(flags & WKV6_W_RAW) && !ew && gw) return WKV6_ENULL;      // gw = ew (.) d (.) dL/dd needs ew beside the decay
+    if (flags & ~(unsigned)(WKV6_W_RAW | WKV6_IO_F32 | WKV6_PARTIALS_F32 | WKV6_ALGO_SCAN)) return WKV6_EUNSUPPORTED;
+    Wkv5Args a = {};
+    a.B = B; a.T = T; a.C = C; a.H = H;
+    a.r = r; a.k = k; a.v = v; a.w = w; a.ew = ew; a.u = u;
+    a.wkind = (flags & WKV6_W_RAW) ? 1 : 0;
+    a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu;
+    a.part_f32 = (flags & WKV6_PARTIALS_F32) ? 1 : 0;
+    return to_rc(launch_wkv5_bwd(a, flags & WKV6_IO_F32, (hipStream_t)stream));
+}
+int wkv5_cuda_forward(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* eew, const void* u,
+                      void* y, void* stream)
+{
+    return wkv5_forward_ex(B, T, C, H, r, k, v, eew, u, y, 0, stream);
+}
+int wkv5_cuda_backward(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* eew, const float* ew,
+                       const void* u, const void* gy, void* gr, void* gk, void* gv, void* gw, void* gu, void* stream)
+{
+    if (!ew) return WKV6_ENULL;
+    return wkv5_backward_ex(B, T, C, H, r, k, v, eew, ew, u, gy, gr, gk, gv, gw, gu, 0, stream);
 }
 
 // ---- reference-signature entry points ------------------------------------------------------------

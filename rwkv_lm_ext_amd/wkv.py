@@ -8,6 +8,7 @@ Mirrors, argument for argument:
   RUN_CUDA_RWKV6_STATE(B, T, C, H, r, k, v, w, u, s)              src/model.py:184-185 (states -> y)
                                                                   src/model.py:130-132 (infctx -> (y, s))
   WKV_6_BI.apply(B, T, C, H, mask, r, k, v, w, u) -> y            cuda/wkv6_bi.py:13-60
+  WKV_5.apply(B, T, C, H, r, k, v, w, u) -> y, RUN_CUDA_RWKV5     src/model.py:241-288  (w, u: [H,N] parameters)
 
 Same dtype/contiguity asserts and the same gradient tuples.  Differences, all deliberate:
   * the raw bf16 decay `w` goes straight to the kernel (no fp32 `ew = -exp(w.float())` pass, no fp32
@@ -68,6 +69,33 @@ class WKV_6(torch.autograd.Function):
             ctx.ckpt = None
             gu = _sum_bf16(gu, (ctx.H, ctx.C // ctx.H))
             return (None, None, None, None, gr, gk, gv, gw, gu)
+
+
+class WKV_5(torch.autograd.Function):
+    """The RWKV-5 operator (src/model.py:241-285): w (time_decay) and u (time_faaaa) are [H,N] bf16 parameters.  The raw w goes to
+    the kernel (no fp32 ew / eew tensors, src/model.py:260-261) and the per-batch gw / gu partials come back in fp32, are summed
+    over the batch in fp32 and rounded once (the reference sums bf16 partials in bf16, src/model.py:283-284)."""
+
+    @staticmethod
+    def forward(ctx, B, T, C, H, r, k, v, w, u):
+        with torch.no_grad():
+            _assert_inputs(C, H, r, k, v, w, u)
+            ctx.B, ctx.T, ctx.C, ctx.H = B, T, C, H
+            ctx.save_for_backward(r, k, v, w, u)
+            return wkv6_op.wkv5_forward_ex(r, k, v, w, u, H)
+
+    @staticmethod
+    def backward(ctx, gy):
+        with torch.no_grad():
+            assert gy.dtype == torch.bfloat16
+            r, k, v, w, u = ctx.saved_tensors
+            gr, gk, gv, gw, gu = wkv6_op.wkv5_backward_ex(r, k, v, w, u, gy.contiguous(), ctx.H)
+            hn = (ctx.H, ctx.C // ctx.H)
+            return (None, None, None, None, gr, gk, gv, _sum_bf16(gw, hn), _sum_bf16(gu, hn))
+
+
+def RUN_CUDA_RWKV5(B, T, C, H, r, k, v, w, u):
+    return WKV_5.apply(B, T, C, H, r, k, v, w, u)
 
 
 class WKV_6_REV(torch.autograd.Function):

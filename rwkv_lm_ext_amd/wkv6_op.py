@@ -1,5 +1,5 @@
 """Operator layer: the torch-extension surface of cuda/wkv6_op.cpp, cuda/wkv6_bi_op.cpp,
-cuda/wkv6state_op.cpp and cuda/wkv6infctx_op.cpp, served by librwkv6_amd.so.
+cuda/wkv6state_op.cpp, cuda/wkv6infctx_op.cpp and cuda/wkv5_op.cpp, served by librwkv6_amd.so.
 
 The reference obtains four module objects from ``torch.utils.cpp_extension.load`` (src/model.py:80-81,
 134-135, 188-189; cuda/wkv6_bi.py:7) and calls ``module.forward(...)`` / ``module.backward(...)`` on
@@ -11,6 +11,8 @@ in-place output convention and dtypes:
     wkv6_bi_cuda.forward / backward: same with `mask` (int32 [B,T]) after H        cuda/wkv6_bi_op.cpp:8-13
     wkv6state_cuda / wkv6infctx_cuda.forward(B,T,C,H, r,k,v, w[bf16 raw], u, s, y) cuda/wkv6state_op.cpp:8-10
                                    .backward(..., s, gy, gr,gk,gv,gw, gu, gs)      cuda/wkv6state_op.cpp:11-13
+    wkv5.forward (B,T,C,H, r,k,v, eew[f32 H,N], u, y)                              cuda/wkv5_op.cpp:8-10
+    wkv5.backward(B,T,C,H, r,k,v, eew, ew[f32 H,N], u, gy, gr,gk,gv, gw[B,C], gu[B,C])   cuda/wkv5_op.cpp:11-13
 
 They are also registered as ``torch.ops.wkv6.forward`` etc. (the reference's TORCH_LIBRARY blocks,
 cuda/wkv6_op.cpp:19-22).  Unlike the reference shims (which check nothing) every call validates
@@ -192,7 +194,35 @@ class _Rwkv6:
         _Rwkv6._call(B, T, C, H, state, r, k, v, w, u, y, torch.float16)
 
 
+class _Wkv5:
+    """Stand-in for the module object of `load(name="wkv5", ...)` (src/model.py:238-239): the RWKV-5 operator, whose decay is an
+    [H,N] parameter.  forward (B,T,C,H, r,k,v, eew[f32 decay], u, y); backward(B,T,C,H, r,k,v, eew, ew[f32], u, gy, gr,gk,gv,
+    gw[B,C], gu[B,C])  (cuda/wkv5_op.cpp:8-13)."""
+
+    @staticmethod
+    def forward(B, T, C, H, r, k, v, w, u, y):
+        btc, hn = (B, T, C), (H, HEAD_SIZE)
+        dev = _check_tensors(B, T, C, H, dict(r=(r, btc, None), k=(k, btc, None), v=(v, btc, None),
+                                              w=(w, hn, torch.float32), u=(u, hn, None), y=(y, btc, None)))
+        with torch.cuda.device(dev):
+            rc = _lib.load().wkv5_cuda_forward(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _stream_ptr())
+        _lib.check(rc, "wkv5 forward")
+
+    @staticmethod
+    def backward(B, T, C, H, r, k, v, w, ww, u, gy, gr, gk, gv, gw, gu):
+        btc, hn = (B, T, C), (H, HEAD_SIZE)
+        dev = _check_tensors(B, T, C, H, dict(
+            r=(r, btc, None), k=(k, btc, None), v=(v, btc, None), w=(w, hn, torch.float32), ww=(ww, hn, torch.float32),
+            u=(u, hn, None), gy=(gy, btc, None), gr=(gr, btc, None), gk=(gk, btc, None), gv=(gv, btc, None),
+            gw=(gw, (B, C), None), gu=(gu, (B, C), None)))
+        with torch.cuda.device(dev):
+            rc = _lib.load().wkv5_cuda_backward(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(ww), _ptr(u), _ptr(gy),
+                                                _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu), _stream_ptr())
+        _lib.check(rc, "wkv5 backward")
+
+
 rwkv6 = _Rwkv6
+wkv5 = _Wkv5
 wkv6_cuda = _Wkv6
 wkv6_bi_cuda = _Wkv6Bi
 wkv6state_cuda = _Wkv6State
@@ -294,6 +324,42 @@ def backward_ex(r, k, v, w, u, gy, H, s0=None, w_is_ew=False, want_gs=False, alg
                                           _ptr(ws), ws.numel(), flags, _stream_ptr())
     _lib.check(rc, "wkv6 backward_ex")
     return gr, gk, gv, gw, gu, gs
+
+
+def wkv5_forward_ex(r, k, v, w, u, H, y=None):
+    """y = WKV5(r,k,v,w,u): w, u [H,N] raw parameters in the I/O type of `r` (bf16, or fp32 for numerics tests)."""
+    B, T, C = r.shape
+    io = r.dtype
+    if io not in (torch.bfloat16, torch.float32):
+        raise RuntimeError(f"unsupported I/O dtype {io}")
+    btc, hn = (B, T, C), (H, HEAD_SIZE)
+    if y is None:
+        y = torch.empty(btc, device=r.device, dtype=io)
+    dev = _check_tensors(B, T, C, H, dict(r=(r, btc, io), k=(k, btc, io), v=(v, btc, io), w=(w, hn, io), u=(u, hn, io),
+                                          y=(y, btc, io)), dtype=io)
+    flags = _lib.W_RAW | (_lib.IO_F32 if io == torch.float32 else 0)
+    with torch.cuda.device(dev):
+        rc = _lib.load().wkv5_forward_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), flags, _stream_ptr())
+    _lib.check(rc, "wkv5 forward_ex")
+    return y
+
+
+def wkv5_backward_ex(r, k, v, w, u, gy, H):
+    """Returns (gr, gk, gv, gw[B,C], gu[B,C]): gradients in the I/O type of `r`, the per-batch partials gw (with respect to the raw
+    w) and gu in fp32 (WKV6_PARTIALS_F32), for the caller to sum over the batch and round once."""
+    B, T, C = r.shape
+    io = r.dtype
+    btc, hn = (B, T, C), (H, HEAD_SIZE)
+    dev = _check_tensors(B, T, C, H, dict(r=(r, btc, io), k=(k, btc, io), v=(v, btc, io), w=(w, hn, io), u=(u, hn, io),
+                                          gy=(gy, btc, io)), dtype=io)
+    gr, gk, gv = (torch.empty(btc, device=dev, dtype=io) for _ in range(3))
+    gw, gu = (torch.empty((B, C), device=dev, dtype=torch.float32) for _ in range(2))
+    flags = _lib.W_RAW | _lib.PARTIALS_F32 | (_lib.IO_F32 if io == torch.float32 else 0)
+    with torch.cuda.device(dev):
+        rc = _lib.load().wkv5_backward_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), None, _ptr(u), _ptr(gy), _ptr(gr),
+                                          _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu), flags, _stream_ptr())
+    _lib.check(rc, "wkv5 backward_ex")
+    return gr, gk, gv, gw, gu
 
 
 REV_R, REV_K, REV_V, REV_W, REV_Y, REV_ALL = _lib.REV_R, _lib.REV_K, _lib.REV_V, _lib.REV_W, _lib.REV_Y, _lib.REV_ALL
@@ -620,6 +686,13 @@ def _register():
         lib.impl("forward", impl.forward, "CUDA")
         lib.impl("backward", impl.backward, "CUDA")
         libs.append(lib)
+    w5 = torch.library.Library("wkv5", "DEF")           # TORCH_LIBRARY(wkv5, m), cuda/wkv5_op.cpp:19-22
+    w5.define("forward(int B, int T, int C, int H, Tensor r, Tensor k, Tensor v, Tensor w, Tensor u, Tensor(a!) y) -> ()")
+    w5.define("backward(int B, int T, int C, int H, Tensor r, Tensor k, Tensor v, Tensor w, Tensor ww, Tensor u, Tensor gy, "
+              "Tensor(a!) gr, Tensor(b!) gk, Tensor(c!) gv, Tensor(d!) gw, Tensor(e!) gu) -> ()")
+    w5.impl("forward", _Wkv5.forward, "CUDA")
+    w5.impl("backward", _Wkv5.backward, "CUDA")
+    libs.append(w5)
     return libs
 
 
