@@ -143,6 +143,34 @@ int wkv6bi_backward_ex(int B, int T, int C, int H, const int* mask, const int* l
 size_t wkv6bi_workspace_bytes(int B, int T, int C, int H);
 size_t wkv6bi_kept_bytes(int B, int T, int C, int H);
 
+/* ---- packed variable-length batches ("varlen"): the sequences of a batch lie back to back in [total_T, C] tensors, no padding anywhere.
+ * cu_seqlens: int32 [n_seq + 1] on the device, sequence s = tokens cu[s] .. cu[s+1]-1; the host never reads it (stream-ordered,
+ * graph-capturable, nothing synchronises).  Lengths are clamped on the device: len_s = clamp(cu[s+1] - cu[s], 0, max_seqlen), and a
+ * sequence never reaches past total_T; a zero-length sequence is legal and touches no token.  Every sequence starts from s0 (NULL: zero):
+ *   r,k,v,w,y,gy,gr,gk,gv,gw : [total_T,C]     u : [H,N]
+ *   s0 : [H,N,N] shared, or [n_seq,H,N,N] with WKV6_S0_PER_BATCH     s_out, gs : [n_seq,H,N,N]     gu : [n_seq,C]
+ * (gu, gs are per-SEQUENCE partials that the caller sums, as over the batch elsewhere; s_out of an empty sequence is s0, its gu / gs are 0).
+ * One workgroup per (sequence, head), longest sequences first.  Per-lane offsets are 32-bit within a sequence:
+ * (max_seqlen + 64) * C < 2^31 (2^30 with the fp32 ew decay on the chunked kernels), else WKV6_EUNSUPPORTED; the sequence origin is
+ * 64-bit, so total_T * C may pass 2^31.
+ * flags: WKV6_W_RAW, WKV6_IO_F32, WKV6_ALGO_SCAN (the last two run the exact scan kernels), WKV6_S0_PER_BATCH, WKV6_PARTIALS_F32,
+ * WKV6_CKPT_VALID as elsewhere; any other bit returns WKV6_EINVAL.
+ * workspace: wkv6_varlen_workspace_bytes() bytes -- a host-side bound that needs no device data: H * (total_T / 64 + n_seq) checkpoint
+ * slots of 16 KB (sequence s uses ceil(len_s / 64) of them per head) + four int32 [n_seq] arrays (lengths, token offsets, checkpoint
+ * offsets, dispatch order).  It carries the checkpoints from the forward to a backward called with WKV6_CKPT_VALID on the same inputs;
+ * without that flag the backward runs its own state pass.  Forward: workspace NULL = keep no checkpoints (the int arrays are a
+ * stream-ordered allocation of the call).  Backward: NULL = stream-ordered allocation of the whole workspace (WKV6_ENULL together with
+ * WKV6_CKPT_VALID).  A non-NULL workspace shorter than the bound is refused with WKV6_EWORKSPACE.
+ * Not available packed (out of scope, not half-supported): two workgroups per head, the two-level scan over T, reversal maps, the pair
+ * launch, the GroupNorm epilogue, wkv6_bi. */
+size_t wkv6_varlen_workspace_bytes(long total_T, int n_seq, int C, int H);
+int wkv6_forward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                           const void* v, const void* w, const void* u, const void* s0, void* s_out, void* y, void* workspace,
+                           size_t workspace_bytes, unsigned flags, void* stream);
+int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                            const void* v, const void* w, const void* u, const void* s0, const void* gy, void* gr, void* gk, void* gv,
+                            void* gw, void* gu, void* gs, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+
 /* ---- wkv5 (RWKV-5: the decay is a parameter, constant over batch and time): replaces cuda_forward / cuda_backward of
  * cuda/wkv5_op.cpp:5-6 (cuda/wkv5_cuda.cu:190-202).  w, u : [H,N];  gw, gu : [B,C] per-batch partials (the caller sums them over
  * the batch, src/model.py:283-284).  `eew` is the fp32 decay exp(-exp(w_raw)) and `ew` the fp32 -exp(w_raw) that src/model.py:260-261
@@ -222,6 +250,14 @@ int wkv6_ddlerp_rev_forward(int B, int T, int C, int NS, const void* x, const vo
                             const int* rev_n, void* out, void* stream);
 int wkv6_ddlerp_rev_backward(int B, int T, int C, int NS, const void* x, const void* shifted0, const void* m, const void* maa,
                              const int* rev_n, const void* dout, void* dx, void* dm, float* dmaa_part, int nparts, void* stream);
+/* The same on a packed variable-length batch: x, m, out, dout, dx, dm are [total_T,C] / [NS,total_T,C]; the token in front of the first
+ * token of sequence s is shifted0[s] ([n_seq,C], NULL: zero), never the last token of sequence s-1.  cu_seqlens: int32 [n_seq + 1] on
+ * the device (not read by the host).  A token finds its sequence by bisection in cu_seqlens: no per-token flag, 0 extra bytes per token. */
+int wkv6_ddlerp_varlen_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                               const void* m, const void* maa, void* out, void* stream);
+int wkv6_ddlerp_varlen_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                                const void* m, const void* maa, const void* dout, void* dx, void* dm, float* dmaa_part, int nparts,
+                                void* stream);
 /* gn_gate (src/model.py:462-468): out = GroupNorm_H(y; gamma, beta, eps) * g on rows of C = 64 H channels (nn.GroupNorm(H, C)
  * applied to [rows, C]); stats fp32 [rows,H,2] (mean, rstd) is written for the backward (may be NULL in inference).
  * backward: dy, dg [rows,C]; dgamma_part, dbeta_part fp32 [nparts,C] partial sums. */

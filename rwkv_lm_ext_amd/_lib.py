@@ -48,6 +48,11 @@ SIGNATURES = {
     "wkv6_backward_pair_ex": (_I, [_I] * 4 + [_VP, ctypes.POINTER(SeqSet), _U, _VP]),
     "wkv6bi_forward_ex": (_I, [_I] * 4 + [_VP] * 9 + [_SZ, _U, _VP]),
     "wkv6bi_backward_ex": (_I, [_I] * 4 + [_VP] * 14 + [_SZ, _U, _VP]),
+    "wkv6_varlen_workspace_bytes": (_SZ, [_L, _I, _I, _I]),
+    "wkv6_forward_varlen_ex": (_I, [_L] + [_I] * 4 + [_VP] * 10 + [_SZ, _U, _VP]),
+    "wkv6_backward_varlen_ex": (_I, [_L] + [_I] * 4 + [_VP] * 15 + [_SZ, _U, _VP]),
+    "wkv6_ddlerp_varlen_forward": (_I, [_L] + [_I] * 3 + [_VP] * 7),
+    "wkv6_ddlerp_varlen_backward": (_I, [_L] + [_I] * 3 + [_VP] * 9 + [_I, _VP]),
     "wkv6_ddlerp_forward": (_I, [_I] * 4 + [_VP] * 6),
     "wkv6_ddlerp_backward": (_I, [_I] * 4 + [_VP] * 8 + [_I, _VP]),
     "wkv6_ddlerp_rev_forward": (_I, [_I] * 4 + [_VP] * 7),

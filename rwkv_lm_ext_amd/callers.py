@@ -12,7 +12,8 @@ Parameter names equal the reference's state_dict keys, so a reference checkpoint
   pooling / info_nce_loss  src/model_ext.py:1708-1738, 1882-1911                                       SURVEY a17
 
 The WKV call itself is `wkv(B, T, C, H, r, k, v, w, u) -> y` (default: rwkv_lm_ext_amd.wkv.RUN_CUDA_RWKV6, the HIP
-kernels; bf16 on the GPU).  Everything else is plain PyTorch (the GEMMs ride rocBLAS), as in the reference.
+kernels; bf16 on the GPU); on a packed variable-length batch (forward(x, cu_seqlens=...)) it is the second hook
+`wkv_varlen(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen) -> y`.  Everything else is plain PyTorch (the GEMMs ride rocBLAS), as in the reference.
 """
 import torch
 import torch.nn as nn
@@ -44,14 +45,34 @@ def _default_wkv(B, T, C, H, r, k, v, w, u):
     return y.to(r.dtype)
 
 
+def _default_wkv_varlen(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen):
+    from .wkv import RUN_CUDA_RWKV6_VARLEN
+    bf = torch.bfloat16
+    y = RUN_CUDA_RWKV6_VARLEN(total_T, C, H, *(t.to(bf).contiguous() for t in (r, k, v, w, u)), cu_seqlens, max_seqlen)
+    return y.to(r.dtype)
+
+
+def _packed_prev(x, cu_seqlens):
+    """x delayed by one token on a packed batch [1,total_T,C]: zero in front of every sequence's first token (eager path; the index
+    arithmetic stays on the device of x)."""
+    T = x.shape[1]
+    opens = torch.zeros(T + 1, dtype=torch.bool, device=x.device)
+    opens[cu_seqlens[:-1].long().clamp(0, T)] = True
+    return F.pad(x, (0, 0, 1, -1)).masked_fill(opens[:T].view(1, T, 1), 0)
+
+
 class Tmix_x060(nn.Module):
     """RWKV-6 time-mix around the WKV operator (src/model.py:376-477)."""
 
-    def __init__(self, n_embd, dim_att, head_size=64, head_size_divisor=8, wkv=None, fused=None):
-        """fused: None = the HIP elementwise kernels of mix_op whenever the input is a bf16 GPU tensor; True / False force."""
+    def __init__(self, n_embd, dim_att, head_size=64, head_size_divisor=8, wkv=None, fused=None, wkv_varlen=None):
+        """fused: None = the HIP elementwise kernels of mix_op whenever the input is a bf16 GPU tensor; True / False force.
+        wkv_varlen: the operator call of forward(x, cu_seqlens=...) on a packed batch,
+        `wkv_varlen(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen) -> y` with [1,total_T,C] tensors (default:
+        wkv.RUN_CUDA_RWKV6_VARLEN)."""
         super().__init__()
         self.n_head = dim_att // head_size
         self.wkv = wkv or _default_wkv
+        self.wkv_varlen = wkv_varlen or _default_wkv_varlen
         self.fused = fused
         # forward(): GroupNorm * gate inside the operator's forward kernel (wkv.WKV_6_GN) instead of a second kernel.  Off by
         # default: it saves the y round trip through HBM but the layer is not faster for it -- B x T = 48 x 512, C = 2048 on
@@ -95,7 +116,7 @@ class Tmix_x060(nn.Module):
                     and C % 64 == 0 and C <= 4096)
         return self.fused
 
-    def jit_func(self, x, shifted=None, rev_n=None):
+    def jit_func(self, x, shifted=None, rev_n=None, cu_seqlens=None):
         """Inputs of the WKV operator from the block input (src/model.py:435-459): every projection reads its own
         data-dependent blend of x_t and x_{t-1},  x + (x_{t-1} - x) * (maa_s + m_s),  where the five corrections m_s come
         from one shared low-rank pair (tanh(blend_x @ W1) -> per-stream W2).  Then r, k, v = Linear(blend), g = silu(Linear),
@@ -104,18 +125,25 @@ class Tmix_x060(nn.Module):
         previous chunk's last token in front (src/model.py:740-741).
         On bf16 GPU tensors the two blend stages are one HIP kernel each (mix_op.ddlerp).
         `rev_n` (fused path only, int32 [B]): the token shift runs over the stream whose first rev_n[b] tokens are reversed
-        while every tensor stays in the original token order (row n2)."""
+        while every tensor stays in the original token order (row n2).
+        `cu_seqlens` (int32 [n_seq + 1]): x is a packed variable-length batch [1,total_T,C]; the shift does not cross a sequence
+        boundary (zero in front of every sequence)."""
         B, T, C = x.size()
+        if cu_seqlens is not None:
+            assert B == 1 and shifted is None and rev_n is None, "a packed batch is [1,total_T,C], zero-padded per sequence"
         if self._use_fused(x):
             from . import mix_op
             first = None if shifted is None else shifted[:, 0].contiguous()
-            lead = mix_op.ddlerp(x, self.time_maa_x.view(1, C), None, first, rev_n)[0]
+            lead = mix_op.ddlerp(x, self.time_maa_x.view(1, C), None, first, rev_n, cu_seqlens=cu_seqlens)[0]
             low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
             corr = torch.bmm(low, self.time_maa_w2).view(5, B, T, C)
-            xw, xk, xv, xr, xg = mix_op.ddlerp(x, self._maa5(), corr, first, rev_n).unbind(0)
+            xw, xk, xv, xr, xg = mix_op.ddlerp(x, self._maa5(), corr, first, rev_n, cu_seqlens=cu_seqlens).unbind(0)
         else:
             assert rev_n is None, "the reversed-stream shift exists in the fused (HIP) path only"
-            prev = F.pad(x, (0, 0, 1, -1)) if shifted is None else shifted
+            if cu_seqlens is not None:
+                prev = _packed_prev(x, cu_seqlens)
+            else:
+                prev = F.pad(x, (0, 0, 1, -1)) if shifted is None else shifted
             delta = prev - x
             lead = torch.addcmul(x, delta, self.time_maa_x)
             low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
@@ -139,10 +167,18 @@ class Tmix_x060(nn.Module):
         B, T, C = r.shape
         return self.wkv(B, T, C, self.n_head, r, k, v, w, self.time_faaaa)
 
-    def forward(self, x):
+    def forward(self, x, cu_seqlens=None, max_seqlen=None):
         """causal time-mix (src/model.py:470-477).  With the HIP operator on bf16 GPU tensors the operator, the per-head
         GroupNorm and the gate multiply are ONE kernel (wkv.WKV_6_GN): y never leaves the chip on its way to
-        the normalisation."""
+        the normalisation.
+        cu_seqlens (int32 [n_seq + 1] on the device of x): x is a packed variable-length batch [1,total_T,C] -- the sequences back
+        to back, no padding; token shift and operator restart at every boundary.  max_seqlen: the longest sequence (default:
+        total_T, which is always safe; the kernels need (max_seqlen + 64) * C < 2^31)."""
+        if cu_seqlens is not None:
+            r, k, v, g, w = self.jit_func(x, cu_seqlens=cu_seqlens)
+            _, T, C = r.shape
+            y = self.wkv_varlen(T, C, self.n_head, r, k, v, w, self.time_faaaa, cu_seqlens, T if max_seqlen is None else max_seqlen)
+            return self.jit_func_2(y, g)
         r, k, v, g, w = self.jit_func(x)
         if self.wkv is _default_wkv and self._use_fused(x) and self.fuse_epilogue:
             from .wkv import RUN_CUDA_RWKV6_GN
@@ -232,13 +268,15 @@ class CMix_x060(nn.Module):
                     and self.key.weight.dtype == torch.bfloat16)
         return self.fused
 
-    def forward(self, x):
+    def forward(self, x, cu_seqlens=None, max_seqlen=None):
+        """cu_seqlens (int32 [n_seq + 1]): x is a packed variable-length batch [1,total_T,C]; the token shift does not cross a
+        sequence boundary.  (max_seqlen is accepted for symmetry with Tmix_x060.forward; the FFN has no use for it.)"""
         if self._use_fused(x):
             from . import mix_op
-            xk, xr = mix_op.ddlerp(x, torch.cat([self.time_maa_k, self.time_maa_r], 0).view(2, -1))
+            xk, xr = mix_op.ddlerp(x, torch.cat([self.time_maa_k, self.time_maa_r], 0).view(2, -1), cu_seqlens=cu_seqlens)
             k = mix_op.sqrelu(self.key(xk))
             return mix_op.sigmoid_mul(self.receptance(xr), self.value(k))
-        xx = F.pad(x, (0, 0, 1, -1)) - x
+        xx = (F.pad(x, (0, 0, 1, -1)) if cu_seqlens is None else _packed_prev(x, cu_seqlens)) - x
         k = torch.relu(self.key(x + xx * self.time_maa_k)) ** 2
         return torch.sigmoid(self.receptance(x + xx * self.time_maa_r)) * self.value(k)
 

@@ -157,6 +157,50 @@ __global__ void length_order_kernel(const int* __restrict__ lens, int* __restric
     }
 }
 
+// Packed variable-length batches: from cu_seqlens[n_seq + 1] (token boundaries of the sequences in a [total_T, C] tensor), per sequence
+//   lens    = clamp(cu[s + 1] - cu[s], 0, max_seqlen), cut so that the row ends at or before total_T,
+//   tok_off = clamp(cu[s], 0, total_T),
+//   ck_off  = exclusive prefix sum of ceil(lens / 64): the sequence's first checkpoint slot within its head (a sequence whose slots would
+//             pass ck_stride -- only a cu_seqlens that is not a partition of [0, total_T) can do that -- is given length 0),
+//   order   = the sequences by decreasing length (as length_order_kernel).
+// One workgroup; everything the kernels index with is clamped here, on the device: the host never reads cu_seqlens.
+__global__ __launch_bounds__(256) void varlen_prepare_kernel(const int* __restrict__ cu, int n_seq, long total_T, int max_seqlen, long ck_stride,
+                                                             int* lens, int* __restrict__ tok_off, int* __restrict__ ck_off, int* __restrict__ order)
+{
+    __shared__ long part[256];
+    const int tid = threadIdx.x, per = (n_seq + 255) / 256;
+    const int s_begin = min(tid * per, n_seq), s_end = min(s_begin + per, n_seq);
+    long slots = 0;
+    for (int s = s_begin; s < s_end; ++s) {
+        const long c0 = cu[s], c1 = cu[s + 1];
+        const long t0 = min(max(c0, 0L), total_T);
+        const long len = min(min(max(c1 - c0, 0L), (long)max_seqlen), total_T - t0);
+        lens[s] = (int)len;
+        tok_off[s] = (int)t0;
+        slots += (len + 63) / 64;
+    }
+    part[tid] = slots;
+    __syncthreads();
+    long off = 0;
+    for (int t = 0; t < tid; ++t) off += part[t];
+    for (int s = s_begin; s < s_end; ++s) {
+        long n = (lens[s] + 63) / 64;
+        if (off + n > ck_stride) { lens[s] = 0; n = 0; }
+        ck_off[s] = (int)off;
+        off += n;
+    }
+    __syncthreads();                                         // (one workgroup: its global writes are visible to it behind the barrier)
+    for (int s = tid; s < n_seq; s += 256) {
+        const int ls = lens[s];
+        int rank = 0;
+        for (int o = 0; o < n_seq; ++o) {
+            const int lo = lens[o];
+            rank += (lo > ls) || (lo == ls && o < s);
+        }
+        order[rank] = s;
+    }
+}
+
 int to_rc(hipError_t e) { return e == hipSuccess ? WKV6_OK : (int)e; }
 
 // ---- forward over few, long sequences (inference prefill: B*H << CUs): two-level scan over T.  The sequence is cut into S
@@ -552,6 +596,108 @@ int wkv6_backward_ex(int B, int T, int C, int H, const void* r, const void* k, c
     a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
     a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu; a.gs = gs;
     return to_rc(run_bwd(a, flags, reinterpret_cast<float*>(workspace), (hipStream_t)stream));
+}
+
+// ---- packed variable-length batches -----------------------------------------------------------------------------------------
+// workspace: lens, tok_off, ck_off, order (int32 [n_seq] each) | checkpoints [H][ck_stride][4096] fp32, ck_stride = total_T / 64 + n_seq
+// (sum_s ceil(len_s / 64) <= total_T / 64 + n_seq for any partition of total_T tokens); the scan path's fp32 [total_T, C] scratch lies
+// over the checkpoint area (H * (total_T / 64) * 16 KB = total_T * C * 4 B).
+static long varlen_ck_stride(long total_T, int n_seq) { return total_T / CKPT_TOK + n_seq; }
+static size_t varlen_int_bytes(int n_seq) { return align_up((size_t)4 * n_seq * sizeof(int)); }
+size_t wkv6_varlen_workspace_bytes(long total_T, int n_seq, int C, int H)
+{
+    if (total_T < 1 || n_seq < 1 || H < 1 || (long)H * HEAD != (long)C) return 0;
+    return varlen_int_bytes(n_seq) + align_up((size_t)H * (size_t)varlen_ck_stride(total_T, n_seq) * HEAD * HEAD * sizeof(float));
+}
+constexpr unsigned VARLEN_FLAGS = WKV6_W_RAW | WKV6_IO_F32 | WKV6_S0_PER_BATCH | WKV6_ALGO_SCAN | WKV6_CKPT_VALID | WKV6_PARTIALS_F32;
+static int varlen_check(long total_T, int n_seq, int max_seqlen, int C, int H, unsigned flags)
+{
+    if (total_T < 1 || n_seq < 1 || max_seqlen < 1 || C < 1 || H < 1) return WKV6_EINVAL;
+    if ((long)H * HEAD != (long)C) return WKV6_EINVAL;
+    if (flags & ~VARLEN_FLAGS) return WKV6_EINVAL;
+    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;                 // cu_seqlens is int32
+    // one ROW must stay 32-bit addressable (per-lane byte offsets; half of that with the fp32 ew decay of the chunked kernels); the row
+    // origin is 64-bit, so total_T * C may pass 2^31
+    const bool chunked = !(flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN));
+    const long lim = (chunked && !(flags & WKV6_W_RAW)) ? (1L << 30) : (1L << 31);
+    if (((long)max_seqlen + 64) * C >= lim) return WKV6_EUNSUPPORTED;
+    return WKV6_OK;
+}
+static void varlen_carve(ScanArgs& a, void* workspace, long total_T, int n_seq, float** area)
+{
+    int* const ints = reinterpret_cast<int*>(workspace);
+    a.lens = ints; a.tok_off = ints + n_seq; a.ck_off = ints + 2 * (size_t)n_seq; a.order = ints + 3 * (size_t)n_seq;
+    a.ck_stride = varlen_ck_stride(total_T, n_seq);
+    *area = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + varlen_int_bytes(n_seq));
+}
+static hipError_t varlen_prepare(const ScanArgs& a, const int* cu, long total_T, int max_seqlen, hipStream_t st)
+{
+    hipLaunchKernelGGL(varlen_prepare_kernel, dim3(1), dim3(256), 0, st, cu, a.B, total_T, max_seqlen, a.ck_stride, const_cast<int*>(a.lens),
+                       const_cast<int*>(a.tok_off), const_cast<int*>(a.ck_off), const_cast<int*>(a.order));
+    return hipGetLastError();
+}
+
+int wkv6_forward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                           const void* v, const void* w, const void* u, const void* s0, void* s_out, void* y, void* workspace,
+                           size_t workspace_bytes, unsigned flags, void* stream)
+{
+    if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, flags)) return rc;
+    if (!cu_seqlens || !r || !k || !v || !w || !u || !y) return WKV6_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    StreamScratch scratch;
+    const bool keep = workspace != nullptr;
+    if (workspace) {
+        if (workspace_bytes < wkv6_varlen_workspace_bytes(total_T, n_seq, C, H)) return WKV6_EWORKSPACE;
+    } else {
+        workspace = scratch.get(varlen_int_bytes(n_seq), st);       // the int arrays only: no checkpoints are kept
+        if (!workspace) return WKV6_EWORKSPACE;
+    }
+    ScanArgs a = base_args(n_seq, max_seqlen, C, H, r, k, v, w, u, flags);
+    float* area = nullptr;
+    varlen_carve(a, workspace, total_T, n_seq, &area);
+    a.s0 = s0;
+    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
+    a.s_out = s_out;
+    a.y = y;
+    if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, st)) return to_rc(e);
+    if (flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN)) return to_rc(launch_scan_fwd_varlen(a, flags & WKV6_IO_F32, st));
+    a.ckpt = keep ? area : nullptr;
+    return to_rc(launch_chunk_fwd_varlen(a, false, st));
+}
+
+int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                            const void* v, const void* w, const void* u, const void* s0, const void* gy, void* gr, void* gk, void* gv,
+                            void* gw, void* gu, void* gs, void* workspace, size_t workspace_bytes, unsigned flags, void* stream)
+{
+    if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, flags)) return rc;
+    if (!cu_seqlens || !r || !k || !v || !w || !u || !gy || !gr || !gk || !gv || !gw) return WKV6_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t need = wkv6_varlen_workspace_bytes(total_T, n_seq, C, H);
+    StreamScratch scratch;
+    if (!workspace) {
+        if (flags & WKV6_CKPT_VALID) return WKV6_ENULL;             // the checkpoints live in the workspace
+        workspace = scratch.get(need, st);
+        if (!workspace) return WKV6_EWORKSPACE;
+    } else if (workspace_bytes < need) {
+        return WKV6_EWORKSPACE;
+    }
+    ScanArgs a = base_args(n_seq, max_seqlen, C, H, r, k, v, w, u, flags);
+    float* area = nullptr;
+    varlen_carve(a, workspace, total_T, n_seq, &area);
+    a.s0 = s0;
+    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
+    a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu; a.gs = gs;
+    const bool scan = flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN);
+    // (WKV6_CKPT_VALID on the chunked path: the forward left the int arrays beside its checkpoints)
+    if (scan || !(flags & WKV6_CKPT_VALID))
+        if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, st)) return to_rc(e);
+    if (scan) {
+        a.aux = area;
+        return to_rc(launch_scan_bwd_varlen(a, flags & WKV6_IO_F32, st));
+    }
+    a.ckpt = area;
+    a.ckpt_valid = (flags & WKV6_CKPT_VALID) ? 1 : 0;
+    return to_rc(launch_chunk_bwd_varlen(a, st));
 }
 
 int wkv6_forward_rev_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v, const void* w,

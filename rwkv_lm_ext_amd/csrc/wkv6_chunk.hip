@@ -113,7 +113,9 @@ struct FwdChain {
 };
 // (unsplit launches) does hardware wave `hw` of a workgroup play a producer?  One definition: chunk_fwd_body's role map below
 __device__ __forceinline__ bool fwd_hw_wave_produces(int hw) { return hw >= 4; }
-template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false>
+// VARLEN (packed batches, chunk_fwd_varlen_kernel): row b is sequence b of a [total_T, C] tensor -- its tokens start at a.tok_off[b], its
+// checkpoints at slot a.ck_off[b] of its head's a.ck_stride slots; a.T is the longest sequence allowed, a.lens / a.order are always set
+template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false, bool VARLEN = false>
 __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned slot, const unsigned sslot, FwdRaw& raw, const FwdChain& ch = FwdChain{})
 {
     [[maybe_unused]] const bool nxvalid = ch.nx_valid, chained_in = ch.chained_in, nx_use_u = ch.nx_use_u;
@@ -141,8 +143,8 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
     const int wv = wid & 3;                                          // block (producer) / column tile (consumer)
     // (CHAIN: the persistent launch has looked the row's batch index and length up -- two dependent memory round trips -- a call ahead)
     const int b = CHAIN ? b_known : (a.order ? a.order[bh / a.H] : bh / a.H), h = bh % a.H;
-    const long base = (long)b * a.T * a.C + (long)h * HEAD;   // (batch, head) origin: uniform, folded into the pointers;
-                                                              // per-lane offsets below stay 32-bit (T*C < 2^31, checked by the API)
+    // (batch, head) origin: uniform, folded into the pointers; per-lane offsets below stay 32-bit (T*C < 2^31, checked by the API)
+    const long base = VARLEN ? (long)a.tok_off[b] * a.C + (long)h * HEAD : (long)b * a.T * a.C + (long)h * HEAD;
     const bf16_t* const gr_ = reinterpret_cast<const bf16_t*>(a.r) + base;
     const bf16_t* const gk_ = reinterpret_cast<const bf16_t*>(a.k) + base;
     const bf16_t* const gv_ = reinterpret_cast<const bf16_t*>(a.v) + base;
@@ -379,11 +381,12 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
         int trow = (4 * g + (x >> 2)) * RSB + 16 * (x & 3);      // transposed read, tile-labelled columns: + tile_tr(t)
         // (a null y -- the fused-epilogue forward of an inference call -- gets a zero-sized resource: its stores are dropped)
         const rsrc_t rs_y = make_rsrc(a.y ? gy_ : nullptr, (!STATE_ONLY && a.y && ntok > 0) ? (unsigned)(ntok - 1) * a.C * 2u + 128u : 0u);
-        const unsigned nst = ((unsigned)a.T + CKPT_TOK - 1) / CKPT_TOK;         // checkpoint slots of this (batch, head): 16 KB each
+        // checkpoint slots of this (batch, head): 16 KB each  (VARLEN: of this sequence -- slots past its last group belong to the next one)
+        const unsigned nst = VARLEN ? (unsigned)ngrp : ((unsigned)a.T + CKPT_TOK - 1) / CKPT_TOK;
         // (two-level scan: this batch row is segment b % S of sequence b / S; the S segments' slots are consecutive, which is the
         // whole sequence's ordinary checkpoint layout)
         const int segs = a.ckpt_segs > 1 ? a.ckpt_segs : 1;
-        const long ck_slot0 = ((long)((b / segs) * a.H + h) * segs + b % segs) * nst;
+        const long ck_slot0 = VARLEN ? (long)h * a.ck_stride + a.ck_off[b] : ((long)((b / segs) * a.H + h) * segs + b % segs) * nst;
         const rsrc_t rs_ck = make_rsrc(a.ckpt ? a.ckpt + ck_slot0 * (HEAD * HEAD) : nullptr, a.ckpt ? nst * 16384u : 0u);
         // ACC (second half of wkv6_bi): the addends of a whole group are requested a group ahead, as raw bits, into a second register
         // set (handed over at the end of the group).  They used to be requested one block ahead through a two-way branch (fp32 side
@@ -697,6 +700,15 @@ __global__ __launch_bounds__(512) void chunk_fwd_kernel(const ScanArgs a)
     chunk_fwd_body<W_RAW, STATE_ONLY, ACC, GN, AFF, !STATE_ONLY && !ACC && !GN>(a, blockIdx.x, 0u, raw);
 }
 
+// Packed variable-length batch: one workgroup per (sequence, head), the sequences longest first (a.order).  Instantiations of their own, so
+// that the dense kernels' instruction streams do not depend on this path.
+template <bool W_RAW, bool STATE_ONLY>
+__global__ __launch_bounds__(512) void chunk_fwd_varlen_kernel(const ScanArgs a)
+{
+    FwdRaw raw;
+    chunk_fwd_body<W_RAW, STATE_ONLY, false, false, true, false, false, true>(a, blockIdx.x, 0u, raw);
+}
+
 // Two problems of the same shape in one grid of 2 B H workgroups: slots [0, B H) serve a0, the rest a1 (src/model_bi.py:331-348,
 // src/model_ext.py:421-437: the forward-direction and the reversed-direction operator calls of a bidirectional time-mix layer).
 template <bool W_RAW>
@@ -859,6 +871,31 @@ hipError_t launch_chunk_fwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* sl
         hipLaunchKernelGGL((chunk_fwd_bi_kernel<false>), dim3(n), dim3(512), lds, st, a1, a2.ckpt);
     }
     return hipGetLastError();
+}
+
+// Packed rows (a.tok_off / a.ck_off / a.lens / a.order set by the API's preparation kernel; a.B = sequences, a.T = longest length allowed).
+// One workgroup per (sequence, head) only: no split, no reversal maps, no accumulation, no GroupNorm epilogue, no two-level scan.
+template <bool W_RAW, bool STATE_ONLY> static hipError_t launch_fwd_varlen_inst(const ScanArgs& a, hipStream_t st)
+{
+    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
+    static LdsAttrOnce attr;
+    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_kernel<W_RAW, STATE_ONLY>), lds)) return e;
+    hipLaunchKernelGGL((chunk_fwd_varlen_kernel<W_RAW, STATE_ONLY>), dim3(a.B * a.H), dim3(512), lds, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_chunk_fwd_varlen(const ScanArgs& a_, bool state_only, hipStream_t st)
+{
+    if (!offsets_fit(a_)) return hipErrorInvalidValue;
+    if (!a_.tok_off || !a_.ck_off || !a_.lens || !a_.order) return hipErrorInvalidValue;
+    if (a_.reverse || a_.rev_n || a_.accumulate || a_.y_f32 || a_.zero_tail || a_.gn_out || a_.dsum || a_.ckpt_segs > 1 || a_.side_compact)
+        return hipErrorNotSupported;
+    ScanArgs a = a_;
+    a.split = 0;
+    a.clk = nullptr; a.clk_slots = 0;
+    attach_debug_buffer(a);
+    const bool raw = a.wkind == 1;
+    if (state_only) return raw ? launch_fwd_varlen_inst<true, true>(a, st) : launch_fwd_varlen_inst<false, true>(a, st);
+    return raw ? launch_fwd_varlen_inst<true, false>(a, st) : launch_fwd_varlen_inst<false, false>(a, st);
 }
 
 // state recurrence only, dumping the stage-entry states into a.ckpt (first half of the self-contained backward)

@@ -155,7 +155,9 @@ struct BwdCarry {
 // ROLE: 0 = the wave finds its role from its index (every kernel but the persistent wkv6_bi launch); 1 / 2 / 3 = this instantiation holds the
 // row / column / producer role only -- chunk_bwd12k_bi_kernel branches on the role ONCE and runs each role's row loop as its own code, so
 // that what one role carries from call to call (BwdCarry) is not live through the other roles' paths.
-template <bool W_RAW, int GEN, bool SPLIT, bool AFF, bool CLK = false, bool CHAIN = false, int ROLE = 0>
+// VARLEN (packed batches, chunk_bwd12k_varlen_kernel): row b is sequence b of [total_T, C] tensors -- tokens from a.tok_off[b], checkpoints from
+// slot a.ck_off[b] of its head's a.ck_stride slots (wkv6_scan.h)
+template <bool W_RAW, int GEN, bool SPLIT, bool AFF, bool CLK = false, bool CHAIN = false, int ROLE = 0, bool VARLEN = false>
 __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsigned slot, BwdCarry& cy, const unsigned sslot = 0, const BwdChain& ch = BwdChain{})
 {
     [[maybe_unused]] const bool chained_in = CHAIN && ch.chained_in, nx_chain = CHAIN && ch.nx_chain;
@@ -175,8 +177,8 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
     const int wv = wid & 3;                                              // tile owned by a row / column wave
     const int pb = wid & 1, half = (wid >> 1) & 1;                       // producer: block of the stage, channel half
     const int b = CHAIN ? ch.b : (a.order ? a.order[bh / a.H] : bh / a.H), h = bh % a.H;
-    const long base = (long)b * a.T * a.C + (long)h * HEAD;   // (batch, head) origin: uniform, folded into the pointers;
-                                                              // per-lane offsets below stay 32-bit (T*C < 2^31, checked by the API)
+    // (batch, head) origin: uniform, folded into the pointers; per-lane offsets below stay 32-bit (T*C < 2^31, checked by the API)
+    const long base = VARLEN ? (long)a.tok_off[b] * a.C + (long)h * HEAD : (long)b * a.T * a.C + (long)h * HEAD;
     const bf16_t* const gr_ = reinterpret_cast<const bf16_t*>(a.r) + base;
     const bf16_t* const gk_ = reinterpret_cast<const bf16_t*>(a.k) + base;
     const bf16_t* const gv_ = reinterpret_cast<const bf16_t*>(a.v) + base;
@@ -652,11 +654,11 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
         // registers.  Requested behind a stage's pre-phase (the registers of the stage's own states are dead by then) for the NEXT
         // stage: the latency runs under the chain, the barrier and the next stage's tile work.  Both stages of a pair use the
         // same checkpoint: requested once, ahead of the odd stage, and kept in CK for the even one.
-        const unsigned nslots = ((unsigned)a.T + CKT - 1) / CKT;
+        const unsigned nslots = VARLEN ? ((unsigned)ntok + CKT - 1) / CKT : ((unsigned)a.T + CKT - 1) / CKT;
         // (two-level scan over T: this batch row is segment b % S of sequence b / S; the S segments' slots are consecutive -- the
         // whole sequence's ordinary checkpoint layout, exactly as the forward wrote them: wkv6_chunk.hip)
         const int segs = a.ckpt_segs > 1 ? a.ckpt_segs : 1;
-        const long ck_slot0 = ((long)((b / segs) * a.H + h) * segs + b % segs) * nslots;
+        const long ck_slot0 = VARLEN ? (long)h * a.ck_stride + a.ck_off[b] : ((long)((b / segs) * a.H + h) * segs + b % segs) * nslots;
         const rsrc_t rs_ck = make_rsrc(a.ckpt + ck_slot0 * (HEAD * HEAD), nslots * 16384u);
         f4v (&CK)[4] = cy.CK;                                     // (BwdCarry: a chained call finds its first checkpoint requested)
         auto request_ckpt = [&](int stg) {
@@ -1336,6 +1338,14 @@ __global__ __launch_bounds__(SPLIT ? 512 : 768) void chunk_bwd12k_kernel(const S
     chunk_bwd12k_body<W_RAW, GEN, SPLIT, AFF, GEN == 0>(a, blockIdx.x, cy);
 }
 
+// Packed variable-length batch: one workgroup per (sequence, head), longest first (a.order); instantiations of their own (wkv6_chunk.hip)
+template <bool W_RAW>
+__global__ __launch_bounds__(768) void chunk_bwd12k_varlen_kernel(const ScanArgs a)
+{
+    BwdCarry cy;
+    chunk_bwd12k_body<W_RAW, 0, false, true, false, false, 0, true>(a, blockIdx.x, cy);
+}
+
 // the backward of chunk_fwd_pair_kernel (wkv6_chunk.hip): two problems of one shape, slots [0, B H) serve a0, the rest a1
 template <bool W_RAW>
 __global__ __launch_bounds__(768) void chunk_bwd12k_pair_kernel(const ScanArgs a0, const ScanArgs a1)
@@ -1483,6 +1493,34 @@ hipError_t launch_chunk_bwd(const ScanArgs& a_, hipStream_t st)
         if (hipError_t e = launch_chunk_state_pass(sp, st)) return e;
     }
     return launch_chunk_bwd12k(a, st);
+}
+
+// Packed rows: state pass (unless the forward left the checkpoints) + reverse pass, one workgroup per (sequence, head).  No split, no
+// reversal maps, no wkv6_bi halves, no two-level scan over T.
+template <bool W_RAW> static hipError_t launch_bwd12k_varlen_inst(const ScanArgs& a, hipStream_t st)
+{
+    static LdsAttrOnce attr;
+    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_kernel<W_RAW>), BWD12K_LDS)) return e;
+    hipLaunchKernelGGL((chunk_bwd12k_varlen_kernel<W_RAW>), dim3(a.B * a.H), dim3(768), BWD12K_LDS, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_chunk_bwd_varlen(const ScanArgs& a_, hipStream_t st)
+{
+    if (!a_.ckpt || !a_.tok_off || !a_.ck_off || !a_.lens || !a_.order) return hipErrorInvalidValue;
+    if (a_.wkind != 1 && ((long)a_.T + 64) * a_.C >= (1L << 30)) return hipErrorInvalidValue;
+    if (a_.reverse || a_.rev_n || a_.accumulate || a_.zero_tail || a_.g_f32[0] || a_.g_f32[1] || a_.g_f32[2] || a_.g_f32[3] || a_.g_in || a_.rc_in ||
+        a_.ckpt_segs > 1 || a_.side_compact)
+        return hipErrorNotSupported;
+    ScanArgs a = a_;
+    a.split = 0;
+    a.clk = nullptr; a.clk_slots = 0;
+    if (!a.ckpt_valid) {
+        ScanArgs sp = a;
+        sp.y = nullptr; sp.s_out = nullptr;
+        if (hipError_t e = launch_chunk_fwd_varlen(sp, true, st)) return e;
+    }
+    attach_debug_buffer(a);
+    return a.wkind ? launch_bwd12k_varlen_inst<true>(a, st) : launch_bwd12k_varlen_inst<false>(a, st);
 }
 
 hipError_t launch_chunk_bwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* slots, hipStream_t st)

@@ -36,7 +36,25 @@ struct LerpArgs {
     bf16_t* dm;               // [NS,B,T,C] or null
     float* dmaa_part;         // [nparts,NS,C]
     int nparts;
+    // packed variable-length batch (the VARLEN instantiations; B = 1, T = total_T): token boundaries of the n_seq sequences; shifted0 is
+    // then [n_seq,C], the token in front of each sequence's first one
+    const int* cu;            // [n_seq + 1]
+    int n_seq;
 };
+
+// Packed batches: the sequence that holds row r = the last s with cu[s] <= r (-1: none), by bisection in cu_seqlens -- workgroup-uniform
+// scalar loads of a few cached words, no per-token flag array: 0 bytes per token beyond the dense kernel's traffic.  Row r opens its
+// sequence when cu[s] == r (empty sequences in front of it share that boundary: the last index wins, which is the sequence that holds the row).
+__device__ __forceinline__ int seq_of_row(const int* __restrict__ cu, int n_seq, long r)
+{
+    int lo = 0, hi = n_seq;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long)cu[mid] <= r) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo - 1;
+}
 
 __device__ __forceinline__ void ld4(const bf16_t* p, float (&o)[4]) { io4<bf16_t>::load(p, o); }
 
@@ -57,7 +75,7 @@ __device__ __forceinline__ int next_tok(int t, int n, int T)
     return n < T ? n : -1;                               // token 0 closes the reversed span
 }
 
-template <int NS, bool HAS_M>
+template <int NS, bool HAS_M, bool VARLEN = false>
 __global__ void ddlerp_fwd_kernel(const LerpArgs a)
 {
     const long row = blockIdx.x;                         // b*T + t
@@ -65,10 +83,17 @@ __global__ void ddlerp_fwd_kernel(const LerpArgs a)
     const int c = 4 * threadIdx.x;
     float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f};
     ld4(a.x + row * a.C + c, x);
-    const int nrev = a.rev_n ? min(max(a.rev_n[b], 0), a.T) : 0;
-    const int tp = prev_tok(t, nrev);
-    if (tp >= 0) ld4(a.x + ((long)b * a.T + tp) * a.C + c, xp);
-    else if (a.shifted0) ld4(a.shifted0 + (long)b * a.C + c, xp);
+    if constexpr (VARLEN) {
+        const int sq = seq_of_row(a.cu, a.n_seq, row);
+        const bool first = sq >= 0 && (long)a.cu[sq] == row;
+        if (!first) { if (row > 0) ld4(a.x + (row - 1) * a.C + c, xp); }
+        else if (a.shifted0) ld4(a.shifted0 + (long)sq * a.C + c, xp);
+    } else {
+        const int nrev = a.rev_n ? min(max(a.rev_n[b], 0), a.T) : 0;
+        const int tp = prev_tok(t, nrev);
+        if (tp >= 0) ld4(a.x + ((long)b * a.T + tp) * a.C + c, xp);
+        else if (a.shifted0) ld4(a.shifted0 + (long)b * a.C + c, xp);
+    }
     const long plane = (long)a.B * a.T * a.C;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -84,7 +109,9 @@ __global__ void ddlerp_fwd_kernel(const LerpArgs a)
 // Backward: dx_t = sum_s dout_{s,t} (1 - c_{s,t}) + sum_s dout_{s,t+1} c_{s,t+1}  (c = maa + m; the second term is the adjoint
 // of the token shift), dm_{s,t} = dout_{s,t} xx_t, dmaa_s = sum_rows dout_s xx.  Plain stream: workgroup p walks the contiguous
 // rows [p per, (p + 1) per), per = ceil(rows / nparts), backwards; reversed-span streams: workgroup p handles rows p, p + nparts, ...
-template <int NS, bool HAS_M>
+// (VARLEN: the plain walk, with "first token of a sequence" and "nothing behind this token" taken from cu_seqlens: one bisection per
+// workgroup for the sequence of its last row and one for the row behind it, then the boundaries are walked downwards with the rows)
+template <int NS, bool HAS_M, bool VARLEN = false>
 __global__ void ddlerp_bwd_kernel(const LerpArgs a)
 {
     const int c = 4 * threadIdx.x;
@@ -96,13 +123,26 @@ __global__ void ddlerp_bwd_kernel(const LerpArgs a)
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[s][q] = 0.f;
     }
-    if (!a.rev_n) {
+    if (VARLEN || !a.rev_n) {
         // Plain stream: a workgroup walks a contiguous run of rows backwards, so what token t+1 hands to token t -- the part of
         // its blends that came from x_t:  sum_s dout[s][t+1] (maa_s + m_s[t+1])  -- is four floats carried in registers
         // instead of a second read of dout and m (54 -> 34 bytes per token-channel at NS = 5).
         const long per = (rows + gridDim.x - 1) / gridDim.x, r0 = (long)blockIdx.x * per, r1 = min(rows, r0 + per);
         float carry[4] = {0.f, 0.f, 0.f, 0.f};
-        if (r1 > r0 && r1 < rows && r1 % a.T != 0) {          // the run ends inside a sequence: fetch the next row's hand-over once
+        [[maybe_unused]] int sq = -1;                             // VARLEN: sequence of the row at hand, its first row,
+        [[maybe_unused]] long sq_row0 = -1;
+        [[maybe_unused]] bool next_opens = true;                  //         and whether the row behind it opens a sequence
+        if constexpr (VARLEN) {
+            if (r1 > r0) {
+                sq = seq_of_row(a.cu, a.n_seq, r1 - 1);
+                sq_row0 = sq >= 0 ? (long)a.cu[sq] : -1;
+                if (r1 < rows) {
+                    const int sn = seq_of_row(a.cu, a.n_seq, r1);
+                    next_opens = sn >= 0 && (long)a.cu[sn] == r1;
+                }
+            }
+        }
+        if (r1 > r0 && r1 < rows && (VARLEN ? !next_opens : r1 % a.T != 0)) {          // the run ends inside a sequence: fetch the next row's hand-over once
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 float dn[4], mn[4] = {0.f, 0.f, 0.f, 0.f};
@@ -116,9 +156,19 @@ __global__ void ddlerp_bwd_kernel(const LerpArgs a)
             const int t = (int)(row % a.T), b = (int)(row / a.T);
             float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f}, g[4], own[4] = {0.f, 0.f, 0.f, 0.f};
             ld4(a.x + row * a.C + c, x);
-            if (t > 0) ld4(a.x + (row - 1) * a.C + c, xp);
-            else if (a.shifted0) ld4(a.shifted0 + (long)b * a.C + c, xp);
-            const bool last = t == a.T - 1;                       // nothing behind the last token of a sequence
+            bool last;
+            if constexpr (VARLEN) {
+                while (sq >= 0 && row < sq_row0) { --sq; sq_row0 = sq >= 0 ? (long)a.cu[sq] : -1; }
+                const bool first = sq >= 0 && row == sq_row0;
+                if (!first) { if (row > 0) ld4(a.x + (row - 1) * a.C + c, xp); }
+                else if (a.shifted0) ld4(a.shifted0 + (long)sq * a.C + c, xp);
+                last = next_opens;
+                next_opens = first;
+            } else {
+                if (t > 0) ld4(a.x + (row - 1) * a.C + c, xp);
+                else if (a.shifted0) ld4(a.shifted0 + (long)b * a.C + c, xp);
+                last = t == a.T - 1;                              // nothing behind the last token of a sequence
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) g[q] = last ? 0.f : carry[q];
 #pragma unroll
@@ -333,6 +383,11 @@ int check_rows(long rows, int C)
 
 template <int NS, bool HAS_M> void launch_lerp(const LerpArgs& a, bool bwd, hipStream_t st)
 {
+    if (a.cu) {
+        if (bwd) hipLaunchKernelGGL((ddlerp_bwd_kernel<NS, HAS_M, true>), dim3(a.nparts), dim3(a.C / 4), 0, st, a);
+        else hipLaunchKernelGGL((ddlerp_fwd_kernel<NS, HAS_M, true>), dim3((unsigned)((long)a.B * a.T)), dim3(a.C / 4), 0, st, a);
+        return;
+    }
     if (bwd) hipLaunchKernelGGL((ddlerp_bwd_kernel<NS, HAS_M>), dim3(a.nparts), dim3(a.C / 4), 0, st, a);
     else hipLaunchKernelGGL((ddlerp_fwd_kernel<NS, HAS_M>), dim3((unsigned)((long)a.B * a.T)), dim3(a.C / 4), 0, st, a);
 }
@@ -389,6 +444,36 @@ int wkv6_ddlerp_rev_backward(int B, int T, int C, int NS, const void* x, const v
     a.B = B; a.T = T; a.C = C; a.NS = NS;
     a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
     a.rev_n = rev_n;
+    a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
+    return dispatch_lerp(a, true, (hipStream_t)stream);
+}
+
+int wkv6_ddlerp_varlen_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                               const void* m, const void* maa, void* out, void* stream)
+{
+    if (total_T < 1 || n_seq < 1) return WKV6_EINVAL;
+    if (int rc = check_rows(total_T, C)) return rc;
+    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;          // cu_seqlens is int32
+    if (!cu_seqlens || !x || !maa || !out) return WKV6_ENULL;
+    LerpArgs a = {};
+    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
+    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    a.cu = cu_seqlens; a.n_seq = n_seq;
+    a.out = (bf16_t*)out;
+    return dispatch_lerp(a, false, (hipStream_t)stream);
+}
+int wkv6_ddlerp_varlen_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                                const void* m, const void* maa, const void* dout, void* dx, void* dm, float* dmaa_part, int nparts,
+                                void* stream)
+{
+    if (total_T < 1 || n_seq < 1 || nparts < 1) return WKV6_EINVAL;
+    if (int rc = check_rows(total_T, C)) return rc;
+    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;
+    if (!cu_seqlens || !x || !maa || !dout || !dx || !dmaa_part || (m && !dm)) return WKV6_ENULL;
+    LerpArgs a = {};
+    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
+    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    a.cu = cu_seqlens; a.n_seq = n_seq;
     a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
     return dispatch_lerp(a, true, (hipStream_t)stream);
 }

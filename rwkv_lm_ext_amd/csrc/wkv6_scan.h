@@ -95,6 +95,12 @@ struct ScanArgs {
     int clk_slots;                    //   and end: wkv6_set_clock_ring, include/wkv6_amd.h), or null (the default: no stamp executes)
     int split;                        // chunked kernels, set by the launcher when B*H leaves half the chip idle: two workgroups per
                                       // (batch, head), each with its own producers and half of the consuming waves
+    // Packed variable-length batches (the *_varlen launchers; null / 0 everywhere else; kept at the end: the dense kernels' kernarg offsets
+    // stay where they were).  Row b is sequence b of [total_T, C] tensors: B = number of sequences, T = the longest length allowed,
+    // lens / order always set; all three arrays are written (and clamped) on the device by the API's preparation kernel.
+    const int* tok_off;               // [B] first token of the sequence
+    const int* ck_off;                // [B] first checkpoint slot of the sequence within its head: exclusive prefix sum of ceil(len / CKPT_TOK)
+    long ck_stride;                   // checkpoint slots per head: a.ckpt is [H][ck_stride][4096]
 };
 
 enum { REV_R = 1, REV_K = 2, REV_V = 4, REV_W = 8, REV_Y = 16, REV_ALL = 31 };   // REV_Y: y in the forward, gy in the backward;
@@ -164,6 +170,11 @@ hipError_t launch_chunk_bwd_bi(const ScanArgs& a1, const ScanArgs& a2, int* slot
 int bi_slots(int BH);                        // workgroup slots such a launch uses (0: does not apply)
 hipError_t launch_chunk_bwd12k(const ScanArgs& a, hipStream_t st);    // reverse pass over 64-token row-order checkpoints, a.split as given (wkv6_chunk_bwd12k.hip)
 size_t chunk_ckpt_floats(int B, int T, int H);
+// packed variable-length rows (ScanArgs: tok_off, ck_off, ck_stride), one workgroup per (sequence, head); bf16 I/O
+hipError_t launch_chunk_fwd_varlen(const ScanArgs& a, bool state_only, hipStream_t st);
+hipError_t launch_chunk_bwd_varlen(const ScanArgs& a, hipStream_t st);   // a.ckpt_valid == 0: runs the state pass first
+hipError_t launch_scan_fwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st);
+hipError_t launch_scan_bwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st);
 hipError_t launch_chunk_state_pass(const ScanArgs& a, hipStream_t st);   // state recurrence only (s_out, ckpt, dsum)
 // In-run clock probe (wkv6_set_clock_ring, wkv6_api.hip): where launch number n of kind (0: chunked forward, 1: chunked backward) stamps,
 // or null; takes the launch's place in the ring (host side, one atomic increment per launch)

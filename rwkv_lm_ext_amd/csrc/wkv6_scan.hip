@@ -115,7 +115,8 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
     float* const ys = coef + 64;                      // [2][TB][ROW]
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
+    // (packed variable-length batch, a.tok_off set: sequence a.order[slot], longest first, tokens from a.tok_off[b] of [total_T, C])
+    const int b = a.tok_off ? a.order[blockIdx.x / a.H] : blockIdx.x / a.H, h = blockIdx.x % a.H;
     const T* const gr_ = reinterpret_cast<const T*>(a.r);
     const T* const gk_ = reinterpret_cast<const T*>(a.k);
     const T* const gv_ = reinterpret_cast<const T*>(a.v);
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
     int ntok = a.T;
     if (a.lens) ntok = min(max(a.lens[b], 0), a.T);
     const RevMap tokmap = make_revmap(a, b, ntok);      // token each tensor holds at scan position p (wkv6_scan.h)
-    const long base = (long)b * a.T * a.C + (long)h * HEAD;
+    const long base = (a.tok_off ? (long)a.tok_off[b] : (long)b * a.T) * a.C + (long)h * HEAD;
 
     // staging role
     const int spp = tid / TPT, sc0 = (tid % TPT) * CPT;
@@ -274,7 +275,8 @@ __global__ __launch_bounds__(NW * 64) void scan_bwd_s_kernel(const ScanArgs a)
     float* const dqs = smem + 2 * 4 * TB * ROW;       // [2][TB][ROW]
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
+    // (packed variable-length batch, a.tok_off set: sequence a.order[slot], longest first, tokens from a.tok_off[b] of [total_T, C])
+    const int b = a.tok_off ? a.order[blockIdx.x / a.H] : blockIdx.x / a.H, h = blockIdx.x % a.H;
     const T* const gr_ = reinterpret_cast<const T*>(a.r);
     const T* const gk_ = reinterpret_cast<const T*>(a.k);
     const T* const gv_ = reinterpret_cast<const T*>(a.v);
@@ -283,7 +285,7 @@ __global__ __launch_bounds__(NW * 64) void scan_bwd_s_kernel(const ScanArgs a)
     int ntok = a.T;
     if (a.lens) ntok = min(max(a.lens[b], 0), a.T);
     const RevMap tokmap = make_revmap(a, b, ntok);      // token each tensor holds at scan position p (wkv6_scan.h)
-    const long base = (long)b * a.T * a.C + (long)h * HEAD;
+    const long base = (a.tok_off ? (long)a.tok_off[b] : (long)b * a.T) * a.C + (long)h * HEAD;
 
     const int spp = tid / TPT, sc0 = (tid % TPT) * CPT;
     float uu[CPT];
@@ -450,7 +452,8 @@ __global__ __launch_bounds__(NW * 64) void scan_bwd_g_kernel(const ScanArgs a)
     float* const dls = gvs + 2 * NW * TB * ROW;               // [2][TB][ROW]
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
+    // (packed variable-length batch, a.tok_off set: sequence a.order[slot], longest first, tokens from a.tok_off[b] of [total_T, C])
+    const int b = a.tok_off ? a.order[blockIdx.x / a.H] : blockIdx.x / a.H, h = blockIdx.x % a.H;
     const T* const gr_ = reinterpret_cast<const T*>(a.r);
     const T* const gk_ = reinterpret_cast<const T*>(a.k);
     const T* const gv_ = reinterpret_cast<const T*>(a.v);
@@ -462,7 +465,7 @@ __global__ __launch_bounds__(NW * 64) void scan_bwd_g_kernel(const ScanArgs a)
     int ntok = a.T;
     if (a.lens) ntok = min(max(a.lens[b], 0), a.T);
     const RevMap tokmap = make_revmap(a, b, ntok);      // token each tensor holds at scan position p (wkv6_scan.h)
-    const long base = (long)b * a.T * a.C + (long)h * HEAD;
+    const long base = (a.tok_off ? (long)a.tok_off[b] : (long)b * a.T) * a.C + (long)h * HEAD;
 
     const int spp = tid / TPT, sc0 = (tid % TPT) * CPT;
     float uu[CPT];
@@ -763,6 +766,22 @@ hipError_t launch_scan_bwd(const ScanArgs& a, bool io_f32, hipStream_t st)
         hipLaunchKernelGGL((scan_bwd_g_kernel<bf16_t, NWAVES>), grid, block, lds_g, st, a);
     }
     return hipGetLastError();
+}
+
+// Packed variable-length rows: the same kernels, addressed through a.tok_off / a.order (one workgroup per (sequence, head))
+static bool varlen_scan_ok(const ScanArgs& a)
+{
+    return a.tok_off && a.lens && a.order && !a.reverse && !a.rev_n && !a.accumulate && !a.zero_tail && !a.y_f32;
+}
+hipError_t launch_scan_fwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st)
+{
+    if (!varlen_scan_ok(a)) return hipErrorInvalidValue;
+    return launch_scan_fwd(a, io_f32 ? IO_F32 : IO_BF16, st);
+}
+hipError_t launch_scan_bwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st)
+{
+    if (!varlen_scan_ok(a) || !a.aux) return hipErrorInvalidValue;
+    return launch_scan_bwd(a, io_f32, st);
 }
 
 hipError_t launch_selftest(int* result, hipStream_t st)

@@ -72,8 +72,72 @@ class _DDLerp(torch.autograd.Function):
         return dx, part.sum(0).to(maa.dtype), dm, dshift, None
 
 
-def ddlerp(x, maa, m=None, shifted0=None, rev_n=None):
-    """maa: [NS,C] (or anything reshapeable to it, e.g. five [1,1,C] parameters stacked)."""
+def _check_cu(cu_seqlens, device):
+    if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2 and cu_seqlens.device == device):
+        raise RuntimeError("cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of x")
+    return cu_seqlens.numel() - 1
+
+
+class _DDLerpVarlen(torch.autograd.Function):
+    """_DDLerp on a packed variable-length batch: x [1,total_T,C] (or [total_T,C]), m [NS,*x.shape] or None, cu_seqlens int32
+    [n_seq + 1]; the token in front of sequence s is shifted0[s] ([n_seq,C], None: zero), never the last token of sequence s - 1."""
+
+    @staticmethod
+    def forward(ctx, x, maa, m, shifted0, cu_seqlens):
+        x, maa = _require(x, "x"), _require(maa, "maa")
+        m = None if m is None else _require(m, "m")
+        shifted0 = None if shifted0 is None else _require(shifted0, "shifted0")
+        n_seq = _check_cu(cu_seqlens, x.device)
+        C = x.shape[-1]
+        total = x.numel() // C
+        if x.dim() == 3 and x.shape[0] != 1:
+            raise RuntimeError("a packed batch is [1, total_T, C] (or [total_T, C])")
+        if shifted0 is not None and tuple(shifted0.shape) != (n_seq, C):
+            raise RuntimeError(f"shifted0 must be [n_seq, C] = {(n_seq, C)}")
+        NS = maa.shape[0]
+        out = torch.empty((NS,) + tuple(x.shape), device=x.device, dtype=x.dtype)
+        with torch.cuda.device(x.device):
+            rc = _lib.load().wkv6_ddlerp_varlen_forward(total, n_seq, C, NS, _ptr(cu_seqlens), _ptr(x), _ptr(shifted0), _ptr(m),
+                                                        _ptr(maa), _ptr(out), _stream_ptr())
+        _lib.check(rc, "ddlerp varlen forward")
+        ctx.save_for_backward(x, maa, m, shifted0, cu_seqlens)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, maa, m, shifted0, cu = ctx.saved_tensors
+        dout = _require(dout, "dout")
+        C = x.shape[-1]
+        total = x.numel() // C
+        n_seq = cu.numel() - 1
+        NS = maa.shape[0]
+        nparts = min(_NPARTS, total)
+        dx = torch.empty_like(x)
+        dm = None if m is None else torch.empty_like(m)
+        part = torch.empty((nparts, NS, C), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            rc = _lib.load().wkv6_ddlerp_varlen_backward(total, n_seq, C, NS, _ptr(cu), _ptr(x), _ptr(shifted0), _ptr(m), _ptr(maa),
+                                                         _ptr(dout), _ptr(dx), _ptr(dm), _ptr(part), nparts, _stream_ptr())
+        _lib.check(rc, "ddlerp varlen backward")
+        dshift = None
+        if shifted0 is not None and ctx.needs_input_grad[3]:
+            # shifted0[s] enters only the first token of a non-empty sequence s (no host read of cu_seqlens: index arithmetic on the device)
+            first = cu[:-1].long().clamp(0, total - 1)
+            alive = (cu[1:] > cu[:-1]).view(1, n_seq, 1).float()
+            d0 = dout.reshape(NS, total, C)[:, first].float()
+            wgt = maa.float().view(NS, 1, C) + (0.0 if m is None else m.reshape(NS, total, C)[:, first].float())
+            dshift = ((d0 * wgt) * alive).sum(0).to(shifted0.dtype)
+        return dx, part.sum(0).to(maa.dtype), dm, dshift, None
+
+
+def ddlerp(x, maa, m=None, shifted0=None, rev_n=None, cu_seqlens=None):
+    """maa: [NS,C] (or anything reshapeable to it, e.g. five [1,1,C] parameters stacked).  cu_seqlens (int32 [n_seq + 1]): x is a packed
+    variable-length batch [1,total_T,C] and the shift does not cross a sequence boundary (shifted0 is then [n_seq,C])."""
+    if cu_seqlens is not None:
+        if rev_n is not None:
+            raise RuntimeError("ddlerp: reversal maps are not available on a packed batch")
+        return _DDLerpVarlen.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, cu_seqlens)
     return _DDLerp.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, rev_n)
 
 

@@ -9,6 +9,8 @@ Mirrors, argument for argument:
                                                                   src/model.py:130-132 (infctx -> (y, s))
   WKV_6_BI.apply(B, T, C, H, mask, r, k, v, w, u) -> y            cuda/wkv6_bi.py:13-60
   WKV_5.apply(B, T, C, H, r, k, v, w, u) -> y, RUN_CUDA_RWKV5     src/model.py:241-288  (w, u: [H,N] parameters)
+and, with no counterpart in the reference, the packed variable-length forms WKV_6_VARLEN / WKV_6STATE_VARLEN
+(total_T, C, H, r, k, v, w, u[, s], cu_seqlens, max_seqlen) on [total_T,C] tensors without padding.
 
 Same dtype/contiguity asserts and the same gradient tuples.  Differences, all deliberate:
   * the raw bf16 decay `w` goes straight to the kernel (no fp32 `ew = -exp(w.float())` pass, no fp32
@@ -231,6 +233,72 @@ class WKV_6STATE(torch.autograd.Function):
             gr, gk, gv, gw, gu, gs = wkv6_op.backward_ex(r, k, v, w, u, gy, H, s0=s, want_gs=True, ckpt=ctx.ckpt)
             ctx.ckpt = None
             return (None, None, None, None, gr, gk, gv, gw, _sum_bf16(gu, (H, N)), _sum_bf16(gs, (H, N, N)))
+
+
+class WKV_6_VARLEN(torch.autograd.Function):
+    """WKV_6 on a packed variable-length batch: r, k, v, w are [total_T,C] (or [1,total_T,C]), sequence s is rows cu_seqlens[s] ..
+    cu_seqlens[s+1]-1 (int32 [n_seq + 1] on the device) and starts from a zero state.  No token of padding is scanned; the forward
+    keeps its state checkpoints for the backward like WKV_6."""
+
+    @staticmethod
+    def forward(ctx, total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen):
+        with torch.no_grad():
+            _assert_inputs(C, H, r, k, v, w, u)
+            ctx.C, ctx.H, ctx.max_seqlen, ctx.shape = C, H, int(max_seqlen), r.shape
+            r, k, v, w = (t.view(total_T, C) for t in (r, k, v, w))
+            ctx.save_for_backward(r, k, v, w, u, cu_seqlens)
+            n_seq = cu_seqlens.numel() - 1
+            ctx.ws = wkv6_op.new_varlen_workspace(total_T, n_seq, C, H, r.device) if _keep_ckpt(ctx) else None
+            return wkv6_op.forward_varlen_ex(r, k, v, w, u, H, cu_seqlens, ctx.max_seqlen, ws=ctx.ws).view(ctx.shape)
+
+    @staticmethod
+    def backward(ctx, gy):
+        with torch.no_grad():
+            assert gy.dtype == torch.bfloat16
+            r, k, v, w, u, cu = ctx.saved_tensors
+            gy = gy.contiguous().view(r.shape)
+            gr, gk, gv, gw, gu, _ = wkv6_op.backward_varlen_ex(r, k, v, w, u, gy, ctx.H, cu, ctx.max_seqlen, ws=ctx.ws,
+                                                               ckpt_valid=ctx.ws is not None)
+            ctx.ws = None
+            gr, gk, gv, gw = (t.view(ctx.shape) for t in (gr, gk, gv, gw))
+            return (None, None, None, gr, gk, gv, gw, _sum_bf16(gu, (ctx.H, ctx.C // ctx.H)), None, None)
+
+
+def RUN_CUDA_RWKV6_VARLEN(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen):
+    return WKV_6_VARLEN.apply(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen)
+
+
+class WKV_6STATE_VARLEN(torch.autograd.Function):
+    """WKV_6STATE on a packed variable-length batch: every sequence starts from the learnable state s [H,N,N]; gs is summed over the
+    sequences."""
+
+    @staticmethod
+    def forward(ctx, total_T, C, H, r, k, v, w, u, s, cu_seqlens, max_seqlen):
+        with torch.no_grad():
+            _assert_inputs(C, H, r, k, v, w, u, s)
+            ctx.C, ctx.H, ctx.max_seqlen, ctx.shape = C, H, int(max_seqlen), r.shape
+            r, k, v, w = (t.view(total_T, C) for t in (r, k, v, w))
+            ctx.save_for_backward(r, k, v, w, u, s, cu_seqlens)
+            n_seq = cu_seqlens.numel() - 1
+            ctx.ws = wkv6_op.new_varlen_workspace(total_T, n_seq, C, H, r.device) if _keep_ckpt(ctx) else None
+            return wkv6_op.forward_varlen_ex(r, k, v, w, u, H, cu_seqlens, ctx.max_seqlen, s0=s, ws=ctx.ws).view(ctx.shape)
+
+    @staticmethod
+    def backward(ctx, gy):
+        with torch.no_grad():
+            assert gy.dtype == torch.bfloat16
+            r, k, v, w, u, s, cu = ctx.saved_tensors
+            gy = gy.contiguous().view(r.shape)
+            H, N = ctx.H, ctx.C // ctx.H
+            gr, gk, gv, gw, gu, gs = wkv6_op.backward_varlen_ex(r, k, v, w, u, gy, H, cu, ctx.max_seqlen, s0=s, want_gs=True,
+                                                                ws=ctx.ws, ckpt_valid=ctx.ws is not None)
+            ctx.ws = None
+            gr, gk, gv, gw = (t.view(ctx.shape) for t in (gr, gk, gv, gw))
+            return (None, None, None, gr, gk, gv, gw, _sum_bf16(gu, (H, N)), _sum_bf16(gs, (H, N, N)), None, None)
+
+
+def RUN_CUDA_RWKV6_STATE_VARLEN(total_T, C, H, r, k, v, w, u, s, cu_seqlens, max_seqlen):
+    return WKV_6STATE_VARLEN.apply(total_T, C, H, r, k, v, w, u, s, cu_seqlens, max_seqlen)
 
 
 class WKV_6STATE_INFCTX(torch.autograd.Function):

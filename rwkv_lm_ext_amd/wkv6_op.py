@@ -326,6 +326,90 @@ def backward_ex(r, k, v, w, u, gy, H, s0=None, w_is_ew=False, want_gs=False, alg
     return gr, gk, gv, gw, gu, gs
 
 
+# ---- packed variable-length batches (include/wkv6_amd.h: wkv6_*_varlen_ex) ----
+def _check_cu_seqlens(cu_seqlens, dev):
+    if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2 and cu_seqlens.device == dev):
+        raise RuntimeError("cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of r")
+    return cu_seqlens.numel() - 1
+
+
+def new_varlen_workspace(total_T, n_seq, C, H, device):
+    """Workspace of the packed pair: the per-sequence int arrays and the state checkpoints that `forward_varlen_ex(..., ws=)` fills and
+    `backward_varlen_ex(..., ws=, ckpt_valid=True)` consumes.  Sized from the host-side bound, no device data needed."""
+    n = _lib.load().wkv6_varlen_workspace_bytes(total_T, n_seq, C, H)
+    if n == 0:
+        raise RuntimeError(f"bad packed shape: total_T {total_T}, n_seq {n_seq}, C {C}, H {H}")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo, extra):
+    if r.dim() != 2:
+        raise RuntimeError("packed tensors are [total_T, C]")
+    total, C = r.shape
+    io = r.dtype
+    if io not in (torch.bfloat16, torch.float32):
+        raise RuntimeError(f"unsupported I/O dtype {io}")
+    tc = (total, C)
+    wdt = torch.float32 if w_is_ew else io
+    named = dict(r=(r, tc, io), k=(k, tc, io), v=(v, tc, io), w=(w, tc, wdt), u=(u, (H, HEAD_SIZE), io))
+    for name, t in extra.items():
+        named[name] = (t, tc, io)
+    flags = (_lib.W_EW_F32 if w_is_ew else _lib.W_RAW) | (_lib.IO_F32 if io == torch.float32 else 0)
+    flags |= _lib.ALGO_SCAN if algo == "scan" else 0
+    n_seq = _check_cu_seqlens(cu_seqlens, r.device)
+    if s0 is not None:
+        per_seq = s0.dim() == 4
+        named["s0"] = (s0, (n_seq, H, HEAD_SIZE, HEAD_SIZE) if per_seq else (H, HEAD_SIZE, HEAD_SIZE), io)
+        flags |= _lib.S0_PER_BATCH if per_seq else 0
+    if int(max_seqlen) < 1:
+        raise RuntimeError("max_seqlen must be >= 1")
+    return total, C, io, n_seq, named, flags
+
+
+def forward_varlen_ex(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0=None, s_out=None, w_is_ew=False, y=None, algo=None, ws=None):
+    """y [total_T,C] = WKV6 of every sequence of a packed batch on its own (sequence s = rows cu_seqlens[s] .. cu_seqlens[s+1]-1, each
+    from s0).  ws: a new_varlen_workspace() buffer that keeps the state checkpoints for backward_varlen_ex(..., ws=ws, ckpt_valid=True)."""
+    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo, {})
+    if s_out is not None:
+        named["s_out"] = (s_out, (n_seq, H, HEAD_SIZE, HEAD_SIZE), io)
+    if y is None:
+        y = torch.empty((total, C), device=r.device, dtype=io)
+    named["y"] = (y, (total, C), io)
+    dev = _check_tensors(n_seq, total, C, H, named, dtype=io)
+    with torch.cuda.device(dev):
+        rc = _lib.load().wkv6_forward_varlen_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(r), _ptr(k), _ptr(v),
+                                                _ptr(w), _ptr(u), _ptr(s0), _ptr(s_out), _ptr(y), _ptr(ws),
+                                                0 if ws is None else ws.numel(), flags, _stream_ptr())
+    _lib.check(rc, "wkv6 forward_varlen_ex")
+    return y
+
+
+def backward_varlen_ex(r, k, v, w, u, gy, H, cu_seqlens, max_seqlen, s0=None, w_is_ew=False, want_gs=False, algo=None, ws=None,
+                       ckpt_valid=False):
+    """Returns (gr, gk, gv, gw [total_T,C], gu [n_seq,C], gs [n_seq,H,N,N] or None); gu / gs are fp32 per-sequence partials
+    (WKV6_PARTIALS_F32) for the caller to sum.  ckpt_valid: `ws` was filled by forward_varlen_ex(..., ws=ws) on the same inputs."""
+    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo, {"gy": gy})
+    dev = _check_tensors(n_seq, total, C, H, named, dtype=io)
+    gr, gk, gv, gw = (torch.empty((total, C), device=dev, dtype=io) for _ in range(4))
+    flags |= _lib.PARTIALS_F32
+    gu = torch.empty((n_seq, C), device=dev, dtype=torch.float32)
+    gs = torch.empty((n_seq, H, HEAD_SIZE, HEAD_SIZE), device=dev, dtype=torch.float32) if want_gs else None
+    if ckpt_valid:
+        if ws is None:
+            raise RuntimeError("ckpt_valid needs the workspace the forward filled")
+        if io == torch.bfloat16 and algo != "scan":
+            flags |= _lib.CKPT_VALID
+    if ws is None:
+        ws = new_varlen_workspace(total, n_seq, C, H, dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().wkv6_backward_varlen_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(r), _ptr(k), _ptr(v),
+                                                 _ptr(w), _ptr(u), _ptr(s0), _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw),
+                                                 _ptr(gu), _ptr(gs), _ptr(ws), ws.numel(), flags, _stream_ptr())
+    _lib.check(rc, "wkv6 backward_varlen_ex")
+    return gr, gk, gv, gw, gu, gs
+
+
 def wkv5_forward_ex(r, k, v, w, u, H, y=None):
     """y = WKV5(r,k,v,w,u): w, u [H,N] raw parameters in the I/O type of `r` (bf16, or fp32 for numerics tests)."""
     B, T, C = r.shape
@@ -655,6 +739,26 @@ class ClockProbe:
         self.buf = None
 
 
+class _Wkv6Varlen:
+    """torch.ops.wkv6.forward_varlen / backward_varlen: the packed operator with the in-place output convention of the ops above."""
+
+    @staticmethod
+    def forward(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen, y):
+        if tuple(r.shape) != (total_T, C):
+            raise RuntimeError(f"r has shape {tuple(r.shape)}, expected {(total_T, C)}")
+        forward_varlen_ex(r, k, v, w, u, H, cu_seqlens, max_seqlen, y=y)
+
+    @staticmethod
+    def backward(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen, gy, gr, gk, gv, gw, gu):
+        if tuple(r.shape) != (total_T, C):
+            raise RuntimeError(f"r has shape {tuple(r.shape)}, expected {(total_T, C)}")
+        res = backward_varlen_ex(r, k, v, w, u, gy, H, cu_seqlens, max_seqlen)
+        for dst, src in zip((gr, gk, gv, gw, gu), res):
+            if dst.shape != src.shape:
+                raise RuntimeError(f"gradient buffer has shape {tuple(dst.shape)}, expected {tuple(src.shape)}")
+            dst.copy_(src)
+
+
 # ---- torch.ops registration: the TORCH_LIBRARY(wkv6|wkv6bi|wkv6state|wkv6infctx, m) blocks ------------
 def _register():
     T9 = "Tensor r, Tensor k, Tensor v, Tensor w, Tensor u"
@@ -686,6 +790,15 @@ def _register():
         lib.impl("forward", impl.forward, "CUDA")
         lib.impl("backward", impl.backward, "CUDA")
         libs.append(lib)
+    # packed variable-length batches (no counterpart in the reference): r, k, v, w [total_T,C] bf16 with the raw decay, caller-allocated
+    # outputs like the ops above; gu [n_seq,C] fp32 per-sequence partials
+    vl = torch.library.Library("wkv6", "FRAGMENT")
+    vl.define(f"forward_varlen(int total_T, int C, int H, {T9}, Tensor cu_seqlens, int max_seqlen, Tensor(a!) y) -> ()")
+    vl.define(f"backward_varlen(int total_T, int C, int H, {T9}, Tensor cu_seqlens, int max_seqlen, Tensor gy, Tensor(a!) gr, Tensor(b!) gk, "
+              f"Tensor(c!) gv, Tensor(d!) gw, Tensor(e!) gu) -> ()")
+    vl.impl("forward_varlen", _Wkv6Varlen.forward, "CUDA")
+    vl.impl("backward_varlen", _Wkv6Varlen.backward, "CUDA")
+    libs.append(vl)
     w5 = torch.library.Library("wkv5", "DEF")           # TORCH_LIBRARY(wkv5, m), cuda/wkv5_op.cpp:19-22
     w5.define("forward(int B, int T, int C, int H, Tensor r, Tensor k, Tensor v, Tensor w, Tensor u, Tensor(a!) y) -> ()")
     w5.define("backward(int B, int T, int C, int H, Tensor r, Tensor k, Tensor v, Tensor w, Tensor ww, Tensor u, Tensor gy, "
