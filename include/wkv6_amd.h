@@ -150,6 +150,14 @@ size_t wkv6bi_kept_bytes(int B, int T, int C, int H);
  *   r,k,v,w,y,gy,gr,gk,gv,gw : [total_T,C]     u : [H,N]
  *   s0 : [H,N,N] shared, or [n_seq,H,N,N] with WKV6_S0_PER_BATCH     s_out, gs : [n_seq,H,N,N]     gu : [n_seq,C]
  * (gu, gs are per-SEQUENCE partials that the caller sums, as over the batch elsewhere; s_out of an empty sequence is s0, its gu / gs are 0).
+ * Rows outside every sequence: for a non-decreasing cu_seqlens, every row of y, gr, gk, gv, gw that lies in no served sequence -- the rows
+ * before cu[0], the rows from cu[n_seq] on, and the part of a sequence that max_seqlen cuts off -- is written as +0, and the inputs on
+ * those rows are never read (a fixed-capacity buffer that is filled differently every step needs no clearing by the caller, and what
+ * lies in its unused rows, NaN included, reaches nothing).  Only these gaps are zeroed, by the preparation launch; a batch that covers
+ * every row pays no memset (the chunked backward under WKV6_CKPT_VALID, which otherwise has no preparation launch, runs it for the
+ * gaps alone: 2-4 us per call on an MI355X, profiles/varlen_time.txt).  The gaps are zeroed with 16-byte stores: y, gr, gk, gv, gw must
+ * be 16-byte aligned, else WKV6_EINVAL (every row then is: a row is a multiple of 128 bytes).  A cu_seqlens that decreases somewhere is out of contract: the calls stay memory-safe (next paragraph),
+ * what the rows hold is unspecified.
  * One workgroup per (sequence, head), longest sequences first.  Per-lane offsets are 32-bit within a sequence:
  * (max_seqlen + 64) * C < 2^31 (2^30 with the fp32 ew decay on the chunked kernels), else WKV6_EUNSUPPORTED; the sequence origin is
  * 64-bit, so total_T * C may pass 2^31.

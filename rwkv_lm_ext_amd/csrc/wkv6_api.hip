@@ -3,9 +3,12 @@
 #include "wkv6_scan.h"
 #include "wkv5_scan.h"
 
+#include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
+#include <cstdint>
 #include <cstring>
 #include <cmath>
 
@@ -163,18 +166,68 @@ __global__ void length_order_kernel(const int* __restrict__ lens, int* __restric
 //   ck_off  = exclusive prefix sum of ceil(lens / 64): the sequence's first checkpoint slot within its head (a sequence whose slots would
 //             pass ck_stride -- only a cu_seqlens that is not a partition of [0, total_T) can do that -- is given length 0),
 //   order   = the sequences by decreasing length (as length_order_kernel).
-// One workgroup; everything the kernels index with is clamped here, on the device: the host never reads cu_seqlens.
+// Everything the kernels index with is clamped here, on the device: the host never reads cu_seqlens.
+__device__ __forceinline__ void varlen_span(const int* __restrict__ cu, int s, long total_T, int max_seqlen, long& t0, long& len)
+{
+    const long c0 = cu[s], c1 = cu[s + 1];
+    t0 = min(max(c0, 0L), total_T);
+    len = min(min(max(c1 - c0, 0L), (long)max_seqlen), total_T - t0);
+}
+
+// Rows of the [total_T, C] outputs that no sequence serves -- gap j, j = 0 .. n_seq, lies between the end of sequence j - 1 (row 0 for
+// j = 0) and the first row of sequence j (total_T for j = n_seq): the rows before cu[0], from cu[n_seq] on, and what max_seqlen cuts off a
+// sequence -- are zeroed, nothing else is written: a batch that covers every row costs each workgroup one look at n_seq + 1 boundaries.
+struct VarlenFill {
+    void* out[4];                   // y, or gr, gk, gv, gw
+    int n_out;
+    long row_bytes;                 // C * element size: a multiple of 128
+};
+
+// Workgroup 0 prepares (one workgroup: `prepare` = 0 skips it, the arrays are already there); workgroups 1 .. gridDim.x - 1 zero the
+// gaps, which they take from cu_seqlens by the same rule, so that they need not wait for workgroup 0.
 __global__ __launch_bounds__(256) void varlen_prepare_kernel(const int* __restrict__ cu, int n_seq, long total_T, int max_seqlen, long ck_stride,
-                                                             int* lens, int* __restrict__ tok_off, int* __restrict__ ck_off, int* __restrict__ order)
+                                                             int* lens, int* __restrict__ tok_off, int* __restrict__ ck_off, int* __restrict__ order,
+                                                             int prepare, const VarlenFill fill)
 {
     __shared__ long part[256];
-    const int tid = threadIdx.x, per = (n_seq + 255) / 256;
+    const int tid = threadIdx.x;
+    if (blockIdx.x != 0) {
+        __shared__ long g0[256], g1[256];
+        __shared__ int n_gaps;
+        const long nfill = gridDim.x - 1, me = (long)(blockIdx.x - 1) * 256 + tid;
+        for (long jb = 0; jb <= n_seq; jb += 256) {
+            if (tid == 0) n_gaps = 0;
+            __syncthreads();
+            const long j = jb + tid;
+            if (j <= n_seq) {
+                long start = 0, end = total_T, t0, len;
+                if (j > 0) { varlen_span(cu, (int)j - 1, total_T, max_seqlen, t0, len); start = t0 + len; }
+                if (j < n_seq) { varlen_span(cu, (int)j, total_T, max_seqlen, t0, len); end = t0; }
+                if (end > start) {
+                    const int i = atomicAdd(&n_gaps, 1);
+                    g0[i] = start; g1[i] = end;
+                }
+            }
+            __syncthreads();
+            const int n = n_gaps;
+            for (int i = 0; i < n; ++i) {
+                const long first = g0[i] * fill.row_bytes, n16 = (g1[i] - g0[i]) * fill.row_bytes / 16;
+                for (int o = 0; o < fill.n_out; ++o) {
+                    uint4* const p = reinterpret_cast<uint4*>(reinterpret_cast<char*>(fill.out[o]) + first);
+                    for (long q = me; q < n16; q += nfill * 256) p[q] = make_uint4(0u, 0u, 0u, 0u);
+                }
+            }
+            __syncthreads();
+        }
+        return;
+    }
+    if (!prepare) return;
+    const int per = (n_seq + 255) / 256;
     const int s_begin = min(tid * per, n_seq), s_end = min(s_begin + per, n_seq);
     long slots = 0;
     for (int s = s_begin; s < s_end; ++s) {
-        const long c0 = cu[s], c1 = cu[s + 1];
-        const long t0 = min(max(c0, 0L), total_T);
-        const long len = min(min(max(c1 - c0, 0L), (long)max_seqlen), total_T - t0);
+        long t0, len;
+        varlen_span(cu, s, total_T, max_seqlen, t0, len);
         lens[s] = (int)len;
         tok_off[s] = (int)t0;
         slots += (len + 63) / 64;
@@ -623,6 +676,13 @@ static int varlen_check(long total_T, int n_seq, int max_seqlen, int C, int H, u
     if (((long)max_seqlen + 64) * C >= lim) return WKV6_EUNSUPPORTED;
     return WKV6_OK;
 }
+// the gaps are zeroed with 16-byte stores (every row is a multiple of 128 bytes, so the base decides)
+static bool varlen_aligned(std::initializer_list<const void*> out)
+{
+    for (const void* p : out)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+    return true;
+}
 static void varlen_carve(ScanArgs& a, void* workspace, long total_T, int n_seq, float** area)
 {
     int* const ints = reinterpret_cast<int*>(workspace);
@@ -630,10 +690,19 @@ static void varlen_carve(ScanArgs& a, void* workspace, long total_T, int n_seq, 
     a.ck_stride = varlen_ck_stride(total_T, n_seq);
     *area = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + varlen_int_bytes(n_seq));
 }
-static hipError_t varlen_prepare(const ScanArgs& a, const int* cu, long total_T, int max_seqlen, hipStream_t st)
+// One launch: workgroup 0 derives the int arrays (prepare), the others zero the rows of `out` that lie in no sequence -- as many workgroups
+// as would zero the whole tensors with eight 16-byte stores per lane and tensor (nobody reads cu_seqlens here, so the launch cannot know
+// how much there is to zero), 1024 at the most.
+static hipError_t varlen_prepare(const ScanArgs& a, const int* cu, long total_T, int max_seqlen, bool prepare, unsigned flags,
+                                 std::initializer_list<void*> out, hipStream_t st)
 {
-    hipLaunchKernelGGL(varlen_prepare_kernel, dim3(1), dim3(256), 0, st, cu, a.B, total_T, max_seqlen, a.ck_stride, const_cast<int*>(a.lens),
-                       const_cast<int*>(a.tok_off), const_cast<int*>(a.ck_off), const_cast<int*>(a.order));
+    VarlenFill fill = {};
+    for (void* p : out) fill.out[fill.n_out++] = p;
+    fill.row_bytes = (long)a.C * ((flags & WKV6_IO_F32) ? 4 : 2);
+    const long per_wg = 256L * 16 * 8;
+    const unsigned nfill = (unsigned)std::min<long>(1024, (total_T * fill.row_bytes + per_wg - 1) / per_wg);
+    hipLaunchKernelGGL(varlen_prepare_kernel, dim3(1 + nfill), dim3(256), 0, st, cu, a.B, total_T, max_seqlen, a.ck_stride, const_cast<int*>(a.lens),
+                       const_cast<int*>(a.tok_off), const_cast<int*>(a.ck_off), const_cast<int*>(a.order), prepare ? 1 : 0, fill);
     return hipGetLastError();
 }
 
@@ -652,6 +721,7 @@ int wkv6_forward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H
         workspace = scratch.get(varlen_int_bytes(n_seq), st);       // the int arrays only: no checkpoints are kept
         if (!workspace) return WKV6_EWORKSPACE;
     }
+    if (!varlen_aligned({y})) return WKV6_EINVAL;
     ScanArgs a = base_args(n_seq, max_seqlen, C, H, r, k, v, w, u, flags);
     float* area = nullptr;
     varlen_carve(a, workspace, total_T, n_seq, &area);
@@ -659,7 +729,7 @@ int wkv6_forward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H
     a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
     a.s_out = s_out;
     a.y = y;
-    if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, st)) return to_rc(e);
+    if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, true, flags, {y}, st)) return to_rc(e);
     if (flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN)) return to_rc(launch_scan_fwd_varlen(a, flags & WKV6_IO_F32, st));
     a.ckpt = keep ? area : nullptr;
     return to_rc(launch_chunk_fwd_varlen(a, false, st));
@@ -681,6 +751,7 @@ int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int 
     } else if (workspace_bytes < need) {
         return WKV6_EWORKSPACE;
     }
+    if (!varlen_aligned({gr, gk, gv, gw})) return WKV6_EINVAL;
     ScanArgs a = base_args(n_seq, max_seqlen, C, H, r, k, v, w, u, flags);
     float* area = nullptr;
     varlen_carve(a, workspace, total_T, n_seq, &area);
@@ -688,9 +759,9 @@ int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int 
     a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
     a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu; a.gs = gs;
     const bool scan = flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN);
-    // (WKV6_CKPT_VALID on the chunked path: the forward left the int arrays beside its checkpoints)
-    if (scan || !(flags & WKV6_CKPT_VALID))
-        if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, st)) return to_rc(e);
+    // (WKV6_CKPT_VALID on the chunked path: the forward left the int arrays beside its checkpoints; the launch only zeroes the gaps)
+    if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, scan || !(flags & WKV6_CKPT_VALID), flags, {gr, gk, gv, gw}, st))
+        return to_rc(e);
     if (scan) {
         a.aux = area;
         return to_rc(launch_scan_bwd_varlen(a, flags & WKV6_IO_F32, st));

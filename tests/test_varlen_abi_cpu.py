@@ -61,6 +61,18 @@ def test_operator_entry_points_reject_a_short_workspace(lib, name):
 
 
 @pytest.mark.parametrize("name", sorted(OPS))
+def test_operator_entry_points_reject_misaligned_outputs(lib, name):
+    """y, gr, gk, gv, gw are zeroed outside the sequences with 16-byte stores: a base that is not 16-byte aligned is refused, after the
+    shape, pointer and workspace checks and before anything is launched (every other pointer here is an aligned dummy)."""
+    fn, bwd = getattr(lib, name), OPS[name]
+    names = BWD_PTRS if bwd else FWD_PTRS
+    aligned = {n: 64 for n in names if n not in OPTIONAL}
+    for out in (("gr", "gk", "gv", "gw") if bwd else ("y",)):
+        for bad in (65, 66, 72):
+            assert fn(*op_args(bwd, ws=64, **(aligned | {out: bad}))) == EINVAL, (out, bad)
+
+
+@pytest.mark.parametrize("name", sorted(OPS))
 def test_row_addressing_limit_is_per_sequence_not_per_batch(lib, name):
     """(max_seqlen + 64) * C must stay below 2^31 (2^30 with the fp32 ew decay on the chunked kernels); total_T * C may pass it.  The
     accepted case cannot be launched with dummy pointers, so it is probed through the check that follows the shape checks: a NULL
@@ -145,3 +157,49 @@ def test_python_wrappers_refuse_what_a_packed_call_cannot_express():
     with pytest.raises(RuntimeError):                                          # no CPU path, and cu_seqlens must be int32
         wkv6_op.forward_varlen_ex(t, t, t, t, torch.zeros(2, 64, dtype=torch.bfloat16), 2, torch.tensor([0, 8]), 8)
     assert hasattr(torch.ops.wkv6, "forward_varlen") and hasattr(torch.ops.wkv6, "backward_varlen")
+
+
+# ---- the preparation rules on the many-sequence sets (the GPU tier holds the device's arrays to this model) ---------------------------
+def test_many_sequence_sets_are_what_the_gpu_tier_expects():
+    from varlen_common import MANY_SETS, TIE_LENS
+    n600, n257 = MANY_SETS["600"], MANY_SETS["257"]
+    slots = lambda lens: sum((n + 63) // 64 for n in lens)
+    assert (len(n600), sum(n600), n600.count(0), slots(n600), sum(n600) // 64 + 600) == (600, 22041, 56, 723, 944)
+    assert (len(n257), sum(n257), n257.count(0), slots(n257), sum(n257) // 64 + 257) == (257, 9112, 26, 304, 399)
+    assert MANY_SETS["256"] == n600[:256] and len(MANY_SETS["513"]) == 513          # one stream of draws
+    assert len(TIE_LENS) == 300 and sorted(set(TIE_LENS)) == [0, 64] and TIE_LENS[:100] == TIE_LENS[200:] == [0] * 100
+
+
+@pytest.mark.parametrize("cut", [None, 64], ids=["whole", "cut64"])
+@pytest.mark.parametrize("name", ["256", "257", "513", "600", "ties"])
+def test_preparation_model_invariants(name, cut):
+    import numpy as np
+    from varlen_common import MANY_SETS, cu_of, prepare_model
+    given = MANY_SETS[name]
+    n_seq, total = len(given), sum(given)
+    max_seqlen = cut or max(given)
+    ck_stride = total // 64 + n_seq
+    lens, tok_off, ck_off, order = prepare_model(cu_of(given), total, max_seqlen, ck_stride)
+    assert lens.tolist() == [min(n, max_seqlen) for n in given] and tok_off.tolist() == cu_of(given)[:-1].tolist()
+    # the rows are inside the tensors and do not overlap
+    assert (tok_off >= 0).all() and (tok_off + lens <= total).all() and (tok_off[1:] >= tok_off[:-1] + lens[:-1]).all()
+    # checkpoint slots: back to back in sequence order, none shared, all below the host-side bound
+    n_slots = (lens.astype(np.int64) + 63) // 64
+    assert ck_off[0] == 0 and (ck_off[1:] == ck_off[:-1] + n_slots[:-1]).all()
+    assert ck_off[-1] + n_slots[-1] == n_slots.sum() <= ck_stride
+    # dispatch order: a permutation, longest first, ties by index
+    assert sorted(order.tolist()) == list(range(n_seq))
+    ranked = lens[order]
+    assert (ranked[:-1] >= ranked[1:]).all()
+    assert all(order[i] < order[i + 1] for i in range(n_seq - 1) if ranked[i] == ranked[i + 1])
+
+
+def test_preparation_model_clamps_what_lies_outside():
+    from varlen_common import prepare_model
+    lens, tok_off, ck_off, order = prepare_model([37, 137, 437, 9999], 551, 128, 551 // 64 + 3)
+    assert lens.tolist() == [100, 128, 114] and tok_off.tolist() == [37, 137, 437] and ck_off.tolist() == [0, 2, 4]
+    assert order.tolist() == [1, 2, 0]
+    lens, tok_off, ck_off, order = prepare_model([0, 0, 0, 0], 450, 450, 450 // 64 + 3)
+    assert lens.tolist() == [0, 0, 0] and ck_off.tolist() == [0, 0, 0] and order.tolist() == [0, 1, 2]
+    lens, *_ = prepare_model([0, 640, 1280], 1280, 640, 10)                  # a bound that is too small: the row that passes it gets length 0
+    assert lens.tolist() == [640, 0]

@@ -257,6 +257,8 @@ def test_clamping_and_garbage_boundaries_are_safe(ops):
     cut = dict(d, max_seqlen=128)
     got = run(ops, cut)                                              # sequence 1 is served for its first 128 tokens only
     assert same(got["y"][:100], full["y"][:100]) and same(got["y"][100:228], full["y"][100:228]) and same(got["y"][400:], full["y"][400:])
+    for n in ("y",) + GRADS:                                         # what max_seqlen cut off belongs to no sequence: +0 (include/wkv6_amd.h)
+        assert not bool(bits(got[n][228:400]).any()), n
     over = dict(d, cu=torch.tensor([0, 100, 400, 9999], dtype=torch.int32, device="cuda"), max_seqlen=20000)
     got = run(ops, over)                                             # the last boundary lies past total_T: clamped to it
     for n in ("y",) + GRADS:

@@ -67,3 +67,40 @@ def oracle_packed(oracle, r, k, v, w, u, gy, lens, s0=None, heads=None):
             out["gs"][s] = og["gs_b"][0]
         t0 += n
     return out
+
+
+# ---- many sequences: past the 256 threads of the one-workgroup preparation kernel, where a thread owns more than one sequence ----------
+MANY_N_SEQ = (256, 257, 513, 600)
+MANY_CHOICES = [0, 1, 2, 15, 16, 17, 63, 64, 65, 130]
+
+
+def many_lens(n_seq):
+    """n_seq lengths around the 16-token block and the 64-token checkpoint spacing, about a tenth of them empty."""
+    return [int(x) for x in np.random.default_rng(20).choice(MANY_CHOICES, n_seq)]
+
+
+# every non-empty length equal (the ranking's tie-break `o < s` alone decides the order), a run of empty sequences at either end
+TIE_LENS = [0] * 100 + [64] * 100 + [0] * 100
+MANY_SETS = {**{str(n): many_lens(n) for n in MANY_N_SEQ}, "ties": TIE_LENS}
+
+
+def prepare_model(cu, total_T, max_seqlen, ck_stride):
+    """What the device-side preparation derives from cu_seqlens (include/wkv6_amd.h), restated in numpy:
+    tok_off = clamp(cu[s], 0, total_T); lens = clamp(cu[s+1] - cu[s], 0, max_seqlen), cut so that the row ends at or before total_T;
+    ck_off = exclusive prefix sum of ceil(lens / 64) (a sequence whose slots would pass ck_stride gets length 0 -- never for a
+    non-decreasing cu_seqlens); order = the sequences by decreasing length, ties by index (a stable sort).
+    Returns int32 arrays lens, tok_off, ck_off, order."""
+    cu = np.asarray(cu, np.int64)
+    n_seq = len(cu) - 1
+    tok_off = np.clip(cu[:-1], 0, total_T)
+    lens = np.minimum(np.clip(cu[1:] - cu[:-1], 0, max_seqlen), total_T - tok_off)
+    ck_off = np.zeros(n_seq, np.int64)
+    off = 0
+    for s in range(n_seq):
+        n = (int(lens[s]) + 63) // 64
+        if off + n > ck_stride:
+            lens[s], n = 0, 0
+        ck_off[s] = off
+        off += n
+    order = np.argsort(-lens, kind="stable")
+    return tuple(a.astype(np.int32) for a in (lens, tok_off, ck_off, order))
