@@ -169,8 +169,9 @@ size_t wkv6bi_kept_bytes(int B, int T, int C, int H);
  * without that flag the backward runs its own state pass.  Forward: workspace NULL = keep no checkpoints (the int arrays are a
  * stream-ordered allocation of the call).  Backward: NULL = stream-ordered allocation of the whole workspace (WKV6_ENULL together with
  * WKV6_CKPT_VALID).  A non-NULL workspace shorter than the bound is refused with WKV6_EWORKSPACE.
- * Not available packed (out of scope, not half-supported): two workgroups per head, the two-level scan over T, reversal maps, the pair
- * launch, the GroupNorm epilogue, wkv6_bi. */
+ * Reversal maps and the pair launch on packed rows: wkv6_*_varlen_rev_ex / wkv6_*_varlen_pair_ex below.
+ * Not available packed (out of scope, not half-supported): two workgroups per head, the two-level scan over T, the GroupNorm epilogue,
+ * wkv6_bi. */
 size_t wkv6_varlen_workspace_bytes(long total_T, int n_seq, int C, int H);
 int wkv6_forward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
                            const void* v, const void* w, const void* u, const void* s0, void* s_out, void* y, void* workspace,
@@ -241,6 +242,33 @@ typedef struct wkv6_seq_set {
 int wkv6_forward_pair_ex(int B, int T, int C, int H, const void* u, const wkv6_seq_set* s, unsigned flags, void* stream);
 int wkv6_backward_pair_ex(int B, int T, int C, int H, const void* u, const wkv6_seq_set* s, unsigned flags, void* stream);
 
+/* ---- reversal maps and the pair launch on packed variable-length batches: the bidirectional compositions without padding.
+ * wkv6_*_varlen_rev_ex = wkv6_*_varlen_ex (same tensors, cu_seqlens, clamping, gap rows, alignment, row limit and workspace rules)
+ * with the map of wkv6_*_rev_ex applied WITHIN every sequence: rev_n is int32 [n_seq] on the device (never read by the host), clamped
+ * there to [0, len_s] with len_s taken after the max_seqlen clamp; scan position p < rev_n[s] of a tensor named in rev_mask is token
+ * cu[s] + rev_n[s] - 1 - p, positions from rev_n[s] on keep their place and are scanned.  rev_n NULL = no map: the plain packed results,
+ * bit for bit.  rev_mask bits outside WKV6_REV_* return WKV6_EINVAL.  There is no initial state (as in wkv6_*_rev_ex): every sequence
+ * starts from zero, gu is [n_seq,C].
+ * flags: WKV6_W_RAW, WKV6_IO_F32, WKV6_ALGO_SCAN (the last two: the exact scan kernels with the same maps), WKV6_PARTIALS_F32,
+ * WKV6_CKPT_VALID; any other bit -- WKV6_S0_PER_BATCH included -- returns WKV6_EINVAL. */
+int wkv6_forward_varlen_rev_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                               const void* v, const void* w, const void* u, void* y, void* workspace, size_t workspace_bytes,
+                               const int* rev_n, unsigned rev_mask, unsigned flags, void* stream);
+int wkv6_backward_varlen_rev_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                                const void* v, const void* w, const void* u, const void* gy, void* gr, void* gk, void* gv, void* gw,
+                                void* gu, void* workspace, size_t workspace_bytes, const int* rev_n, unsigned rev_mask, unsigned flags,
+                                void* stream);
+/* Two such problems over the SAME sequences in one grid of 2 n_seq H workgroups (slots [0, n_seq H) serve s[0], the rest s[1]), behind the
+ * one preparation launch, which zeroes the gap rows of both problems' outputs.  Tensors of a set are [total_T,C], s[i].gu is [n_seq,C],
+ * s[i].rev_n int32 [n_seq] or NULL.  s[i].ckpt / ckpt_bytes is one wkv6_varlen_workspace_bytes() workspace per problem; the prepared int
+ * arrays, which both problems read, live in s[0]'s.  The backward needs both workspaces as wkv6_forward_varlen_pair_ex left them; a
+ * forward nobody differentiates may pass NULL for either.  flags: WKV6_W_RAW, WKV6_PARTIALS_F32; WKV6_IO_F32 / WKV6_ALGO_SCAN return
+ * WKV6_EUNSUPPORTED, any other bit WKV6_EINVAL.  Results (checkpoints included) are bit-identical to two wkv6_*_varlen_rev_ex calls. */
+int wkv6_forward_varlen_pair_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* u,
+                                const wkv6_seq_set* s, unsigned flags, void* stream);
+int wkv6_backward_varlen_pair_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* u,
+                                 const wkv6_seq_set* s, unsigned flags, void* stream);
+
 /* ---- elementwise neighbours of the operator in the RWKV-6 time-mix block; bf16 only ----
  * ddlerp (src/model.py:435-448): xx = shift(x) - x; out[s] = x + xx * (maa[s] + m[s]), s < NS.
  *   x [B,T,C]; shifted0 [B,C] = token in front of each row (NULL: zero, nn.ZeroPad2d((0,0,1,-1))); m [NS,B,T,C] or NULL;
@@ -266,6 +294,14 @@ int wkv6_ddlerp_varlen_forward(long total_T, int n_seq, int C, int NS, const int
 int wkv6_ddlerp_varlen_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
                                 const void* m, const void* maa, const void* dout, void* dx, void* dm, float* dmaa_part, int nparts,
                                 void* stream);
+/* ... with the shift of sequence s taken over the stream "its first rev_n[s] tokens reversed, the rest in place" (rev_n int32 [n_seq] on
+ * the device, clamped to the sequence's length; NULL = the plain packed shift).  The token in front of the stream's first token is
+ * shifted0[s], never a token of another sequence. */
+int wkv6_ddlerp_varlen_rev_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                                   const void* m, const void* maa, const int* rev_n, void* out, void* stream);
+int wkv6_ddlerp_varlen_rev_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                                    const void* m, const void* maa, const int* rev_n, const void* dout, void* dx, void* dm,
+                                    float* dmaa_part, int nparts, void* stream);
 /* gn_gate (src/model.py:462-468): out = GroupNorm_H(y; gamma, beta, eps) * g on rows of C = 64 H channels (nn.GroupNorm(H, C)
  * applied to [rows, C]); stats fp32 [rows,H,2] (mean, rstd) is written for the backward (may be NULL in inference).
  * backward: dy, dg [rows,C]; dgamma_part, dbeta_part fp32 [nparts,C] partial sums. */

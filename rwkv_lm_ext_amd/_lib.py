@@ -51,6 +51,12 @@ SIGNATURES = {
     "wkv6_varlen_workspace_bytes": (_SZ, [_L, _I, _I, _I]),
     "wkv6_forward_varlen_ex": (_I, [_L] + [_I] * 4 + [_VP] * 10 + [_SZ, _U, _VP]),
     "wkv6_backward_varlen_ex": (_I, [_L] + [_I] * 4 + [_VP] * 15 + [_SZ, _U, _VP]),
+    "wkv6_forward_varlen_rev_ex": (_I, [_L] + [_I] * 4 + [_VP] * 8 + [_SZ, _VP, _U, _U, _VP]),
+    "wkv6_backward_varlen_rev_ex": (_I, [_L] + [_I] * 4 + [_VP] * 13 + [_SZ, _VP, _U, _U, _VP]),
+    "wkv6_forward_varlen_pair_ex": (_I, [_L] + [_I] * 4 + [_VP, _VP, ctypes.POINTER(SeqSet), _U, _VP]),
+    "wkv6_backward_varlen_pair_ex": (_I, [_L] + [_I] * 4 + [_VP, _VP, ctypes.POINTER(SeqSet), _U, _VP]),
+    "wkv6_ddlerp_varlen_rev_forward": (_I, [_L] + [_I] * 3 + [_VP] * 8),
+    "wkv6_ddlerp_varlen_rev_backward": (_I, [_L] + [_I] * 3 + [_VP] * 10 + [_I, _VP]),
     "wkv6_ddlerp_varlen_forward": (_I, [_L] + [_I] * 3 + [_VP] * 7),
     "wkv6_ddlerp_varlen_backward": (_I, [_L] + [_I] * 3 + [_VP] * 9 + [_I, _VP]),
     "wkv6_ddlerp_forward": (_I, [_I] * 4 + [_VP] * 6),

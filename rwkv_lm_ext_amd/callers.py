@@ -38,6 +38,20 @@ def reverse_x(x, rev_idx):
     return torch.gather(x, 1, rev_idx.to(x.device).unsqueeze(-1).expand(-1, -1, x.size(-1)))
 
 
+def packed_reverse_idx(cu_seqlens, rev_n, total_T):
+    """reverse_x_idx on a packed batch: a [total_T] gather index that reverses the first rev_n[s] tokens of sequence s (rows
+    cu_seqlens[s] .. cu_seqlens[s+1]-1; rev_n clamped to the sequence's length) and keeps every other row -- the rows of no sequence
+    included -- in place.  Computed on the device of its arguments, no host read.  The index is its own inverse."""
+    cu = cu_seqlens.long()
+    n_seq = cu.numel() - 1
+    pos = torch.arange(total_T, device=cu.device)
+    seq = torch.searchsorted(cu[1:].contiguous(), pos, right=True).clamp(max=n_seq - 1)      # the last s with cu[s] <= row
+    start = cu[seq]
+    n = torch.minimum(rev_n.long().clamp_min(0)[seq], (cu[seq + 1] - start).clamp_min(0))
+    t = pos - start
+    return torch.where((t >= 0) & (t < n), start + n - 1 - t, pos)
+
+
 def _default_wkv(B, T, C, H, r, k, v, w, u):
     from .wkv import RUN_CUDA_RWKV6
     bf = torch.bfloat16
@@ -127,10 +141,10 @@ class Tmix_x060(nn.Module):
         `rev_n` (fused path only, int32 [B]): the token shift runs over the stream whose first rev_n[b] tokens are reversed
         while every tensor stays in the original token order (row n2).
         `cu_seqlens` (int32 [n_seq + 1]): x is a packed variable-length batch [1,total_T,C]; the shift does not cross a sequence
-        boundary (zero in front of every sequence)."""
+        boundary (zero in front of every sequence); rev_n is then int32 [n_seq]."""
         B, T, C = x.size()
         if cu_seqlens is not None:
-            assert B == 1 and shifted is None and rev_n is None, "a packed batch is [1,total_T,C], zero-padded per sequence"
+            assert B == 1 and shifted is None, "a packed batch is [1,total_T,C], zero-padded per sequence"
         if self._use_fused(x):
             from . import mix_op
             first = None if shifted is None else shifted[:, 0].contiguous()
@@ -209,8 +223,53 @@ class Tmix_x060(nn.Module):
         addressed inside the kernels (wkv6_*_rev_ex, ddlerp rev_n) instead of through torch.gather round trips."""
         return self.wkv is _default_wkv and self._use_fused(x)
 
-    def forward_bi_c(self, x, rev_idx, mask=None):
-        """composition C (src/model_ext.py:421-437): reverse the hidden states, project twice, average."""
+    def _packed_in_kernel(self, x):
+        return self._in_kernel_reversal(x) and self.wkv_varlen is _default_wkv_varlen
+
+    def _packed_bi(self, fwd, rev, cu_seqlens, max_seqlen, rev_n, rev_mask):
+        """Both operator calls of a composition on a packed batch, in-kernel: the pair launch (wkv.WKV_6_VARLEN_PAIR) or, with
+        pair_launch = False, the plain packed call and the packed call under the map."""
+        from .wkv import RUN_CUDA_RWKV6_VARLEN, WKV_6_VARLEN_PAIR, WKV_6_VARLEN_REV
+        _, T, C = fwd[0].shape
+        bf = torch.bfloat16
+        u = self.time_faaaa.to(bf).contiguous()
+        f, r = [t.to(bf).contiguous() for t in fwd], [t.to(bf).contiguous() for t in rev]
+        if self.pair_launch:
+            y, ry = WKV_6_VARLEN_PAIR.apply(T, C, self.n_head, *f, *r, u, cu_seqlens, max_seqlen, rev_n, rev_mask)
+        else:
+            y = RUN_CUDA_RWKV6_VARLEN(T, C, self.n_head, *f, u, cu_seqlens, max_seqlen)
+            ry = WKV_6_VARLEN_REV.apply(T, C, self.n_head, *r, u, cu_seqlens, max_seqlen, rev_n, rev_mask)
+        return y.to(fwd[0].dtype), ry.to(fwd[0].dtype)
+
+    def _run_packed(self, r, k, v, w, cu_seqlens, max_seqlen):
+        _, T, C = r.shape
+        return self.wkv_varlen(T, C, self.n_head, r, k, v, w, self.time_faaaa, cu_seqlens, max_seqlen)
+
+    @staticmethod
+    def _packed_defaults(x, cu_seqlens, max_seqlen, rev_n):
+        """max_seqlen: total_T is always safe; rev_n: every sequence's full length."""
+        if rev_n is None:
+            rev_n = (cu_seqlens[1:] - cu_seqlens[:-1]).to(torch.int32)
+        return (x.shape[1] if max_seqlen is None else max_seqlen), rev_n.contiguous()
+
+    def forward_bi_c(self, x, rev_idx, mask=None, cu_seqlens=None, max_seqlen=None, rev_n=None):
+        """composition C (src/model_ext.py:421-437): reverse the hidden states, project twice, average.
+        cu_seqlens (int32 [n_seq + 1]): x is a packed batch [1,total_T,C]; the first rev_n[s] tokens (int32 [n_seq], default: all) of
+        every sequence are reversed, rev_idx and mask are not used.  bf16 GPU tensors with the default operator run the reversal
+        inside the kernels; everything else gathers through packed_reverse_idx around the wkv_varlen hook."""
+        if cu_seqlens is not None:
+            max_seqlen, rev_n = self._packed_defaults(x, cu_seqlens, max_seqlen, rev_n)
+            r, k, v, g, w = self.jit_func(x, cu_seqlens=cu_seqlens)
+            if self._packed_in_kernel(x):
+                from .wkv6_op import REV_ALL
+                rr, rk, rv, _, rw = self.jit_func(x, rev_n=rev_n, cu_seqlens=cu_seqlens)
+                y, ry = self._packed_bi((r, k, v, w), (rr, rk, rv, rw), cu_seqlens, max_seqlen, rev_n, REV_ALL)
+            else:
+                idx = packed_reverse_idx(cu_seqlens, rev_n, x.shape[1])
+                y = self._run_packed(r, k, v, w, cu_seqlens, max_seqlen)
+                rr, rk, rv, _, rw = self.jit_func(x[:, idx], cu_seqlens=cu_seqlens)
+                ry = self._run_packed(rr, rk, rv, rw, cu_seqlens, max_seqlen)[:, idx]
+            return self.jit_func_2((y + ry) / 2, g)
         r, k, v, g, w = self.jit_func(x)
         if mask is not None and self._in_kernel_reversal(x):
             from .wkv6_op import REV_ALL
@@ -226,8 +285,21 @@ class Tmix_x060(nn.Module):
             ry = reverse_x(self._run(rr, rk, rv, rw), rev_idx)
         return self.jit_func_2((y + ry) / 2, g)
 
-    def forward_bi_b(self, x, mask=None):
-        """composition B (src/model_bi.py:325-350): only k and v are reversed, outputs are added."""
+    def forward_bi_b(self, x, mask=None, cu_seqlens=None, max_seqlen=None, rev_n=None):
+        """composition B (src/model_bi.py:325-350): only k and v are reversed, outputs are added.
+        cu_seqlens (int32 [n_seq + 1]): x is a packed batch [1,total_T,C]; rev_n (int32 [n_seq]) defaults to every sequence's full
+        length, mask is not used."""
+        if cu_seqlens is not None:
+            max_seqlen, rev_n = self._packed_defaults(x, cu_seqlens, max_seqlen, rev_n)
+            r, k, v, g, w = self.jit_func(x, cu_seqlens=cu_seqlens)
+            if self._packed_in_kernel(x):
+                from .wkv6_op import REV_K, REV_V, REV_Y
+                y, ry = self._packed_bi((r, k, v, w), (r, k, v, w), cu_seqlens, max_seqlen, rev_n, REV_K | REV_V | REV_Y)
+            else:
+                idx = packed_reverse_idx(cu_seqlens, rev_n, x.shape[1])
+                y = self._run_packed(r, k, v, w, cu_seqlens, max_seqlen)
+                ry = self._run_packed(r, k[:, idx], v[:, idx], w, cu_seqlens, max_seqlen)[:, idx]
+            return self.jit_func_2(y + ry, g)
         B, T, C = x.size()
         if mask is None:
             mask = torch.ones(B, T, device=x.device)
@@ -284,19 +356,23 @@ class CMix_x060(nn.Module):
 class BiBlock(nn.Module):
     """src/model_encoder_run.py:222-259 (pre-LN residual block, ln0 on the first layer)."""
 
-    def __init__(self, n_embd, dim_att, dim_ffn, layer_id, wkv=None):
+    def __init__(self, n_embd, dim_att, dim_ffn, layer_id, wkv=None, wkv_varlen=None):
         super().__init__()
         self.layer_id = layer_id
         self.ln1 = nn.LayerNorm(n_embd)
         self.ln2 = nn.LayerNorm(n_embd)
         if layer_id == 0:
             self.ln0 = nn.LayerNorm(n_embd)
-        self.att = Tmix_x060(n_embd, dim_att, wkv=wkv)
+        self.att = Tmix_x060(n_embd, dim_att, wkv=wkv, wkv_varlen=wkv_varlen)
         self.ffn = CMix_x060(n_embd, dim_ffn)
 
-    def forward(self, x, rev_idx, mask):
+    def forward(self, x, rev_idx, mask, cu_seqlens=None, max_seqlen=None, rev_n=None):
+        """cu_seqlens / max_seqlen / rev_n: x is a packed batch [1,total_T,C] (Tmix_x060.forward_bi_c); rev_idx and mask are not used."""
         if self.layer_id == 0:
             x = self.ln0(x)
+        if cu_seqlens is not None:
+            x = x + self.att.forward_bi_c(self.ln1(x), None, None, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen, rev_n=rev_n)
+            return x + self.ffn(self.ln2(x), cu_seqlens=cu_seqlens)
         x = x + self.att.forward_bi_c(self.ln1(x), rev_idx, mask)
         return x + self.ffn(self.ln2(x))
 
@@ -304,26 +380,47 @@ class BiBlock(nn.Module):
 class RwkvEncoder(nn.Module):
     """Bidirectional RWKV-6 encoder (src/model_encoder_run.py:262-348, share_emb, no head_qk, no dropout)."""
 
-    def __init__(self, vocab_size, n_embd, n_layer, dim_att=None, dim_ffn=None, emb_id=1, pad_id=0, wkv=None):
+    def __init__(self, vocab_size, n_embd, n_layer, dim_att=None, dim_ffn=None, emb_id=1, pad_id=0, wkv=None, wkv_varlen=None):
         super().__init__()
         self.emb_id, self.pad_id = emb_id, pad_id
         self.emb = nn.Embedding(vocab_size, n_embd)
-        self.blocks = nn.ModuleList([BiBlock(n_embd, dim_att or n_embd, dim_ffn or 4 * n_embd, i, wkv=wkv)
+        self.blocks = nn.ModuleList([BiBlock(n_embd, dim_att or n_embd, dim_ffn or 4 * n_embd, i, wkv=wkv, wkv_varlen=wkv_varlen)
                                      for i in range(n_layer)])
         self.ln_out = nn.LayerNorm(n_embd)
 
-    def forward(self, idx, return_logits=False):
+    def forward(self, idx, return_logits=False, cu_seqlens=None, max_seqlen=None):
+        """cu_seqlens (int32 [n_seq + 1] on the device of idx): idx is a packed batch [1,total_T], the sequences back to back without
+        pad tokens; rev_n[s] = the number of ordinary tokens of sequence s (a segment sum of create_mask, on the device)."""
         B, T = idx.size()
         mask = create_mask(idx, emb_id=self.emb_id, pad_id=self.pad_id)
-        rev_idx = reverse_x_idx(mask, T)
         x = self.emb(idx)
-        for block in self.blocks:
-            x = block(x, rev_idx, mask)
+        if cu_seqlens is not None:
+            assert B == 1, "a packed batch is [1,total_T]"
+            csum = F.pad(mask[0].cumsum(0), (1, 0))
+            cu = cu_seqlens.long().clamp(0, T)
+            rev_n = (csum[cu[1:]] - csum[cu[:-1]]).to(torch.int32)
+            for block in self.blocks:
+                x = block(x, None, None, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen, rev_n=rev_n)
+        else:
+            rev_idx = reverse_x_idx(mask, T)
+            for block in self.blocks:
+                x = block(x, rev_idx, mask)
         hidden = self.ln_out(x)
         logits = torch.matmul(hidden, self.emb.weight.t())
         return (logits, hidden) if return_logits else logits
 
-    def encode_sentence(self, idx):
+    def encode_sentence(self, idx, cu_seqlens=None, max_seqlen=None):
+        """With cu_seqlens: one vector per sequence of the packed idx [1,total_T], taken at the sequence's first emb_id token (its first
+        token when it has none, as argmax gives on a padded row)."""
+        if cu_seqlens is not None:
+            _, hidden = self.forward(idx, True, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+            T = idx.size(1)
+            count = torch.eq(idx[0], self.emb_id).long().cumsum(0)                   # emb_id tokens up to and including each row
+            cu = cu_seqlens.long().clamp(0, T)
+            before = F.pad(count, (1, 0))[cu[:-1]]
+            position = torch.searchsorted(count, before + 1)                          # the first row whose count reaches before + 1
+            position = torch.where(position < cu[1:], position, cu[:-1]).clamp(max=T - 1)
+            return hidden[0, position]
         _, hidden = self.forward(idx, True)
         position = torch.eq(idx, self.emb_id).int().argmax(-1)
         return hidden[torch.arange(hidden.size(0)), position]

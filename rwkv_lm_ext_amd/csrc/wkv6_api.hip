@@ -178,7 +178,7 @@ __device__ __forceinline__ void varlen_span(const int* __restrict__ cu, int s, l
 // j = 0) and the first row of sequence j (total_T for j = n_seq): the rows before cu[0], from cu[n_seq] on, and what max_seqlen cuts off a
 // sequence -- are zeroed, nothing else is written: a batch that covers every row costs each workgroup one look at n_seq + 1 boundaries.
 struct VarlenFill {
-    void* out[4];                   // y, or gr, gk, gv, gw
+    void* out[8];                   // y, or gr, gk, gv, gw (of both problems of a pair call)
     int n_out;
     long row_bytes;                 // C * element size: a multiple of 128
 };
@@ -663,11 +663,14 @@ size_t wkv6_varlen_workspace_bytes(long total_T, int n_seq, int C, int H)
     return varlen_int_bytes(n_seq) + align_up((size_t)H * (size_t)varlen_ck_stride(total_T, n_seq) * HEAD * HEAD * sizeof(float));
 }
 constexpr unsigned VARLEN_FLAGS = WKV6_W_RAW | WKV6_IO_F32 | WKV6_S0_PER_BATCH | WKV6_ALGO_SCAN | WKV6_CKPT_VALID | WKV6_PARTIALS_F32;
-static int varlen_check(long total_T, int n_seq, int max_seqlen, int C, int H, unsigned flags)
+// (the rev / pair calls have no initial state: WKV6_S0_PER_BATCH is an unknown bit there)
+constexpr unsigned VARLEN_REV_FLAGS = VARLEN_FLAGS & ~(unsigned)WKV6_S0_PER_BATCH;
+constexpr unsigned VARLEN_PAIR_FLAGS = WKV6_W_RAW | WKV6_PARTIALS_F32 | WKV6_IO_F32 | WKV6_ALGO_SCAN;     // (the last two: known, refused)
+static int varlen_check(long total_T, int n_seq, int max_seqlen, int C, int H, unsigned flags, unsigned known = VARLEN_FLAGS)
 {
     if (total_T < 1 || n_seq < 1 || max_seqlen < 1 || C < 1 || H < 1) return WKV6_EINVAL;
     if ((long)H * HEAD != (long)C) return WKV6_EINVAL;
-    if (flags & ~VARLEN_FLAGS) return WKV6_EINVAL;
+    if (flags & ~known) return WKV6_EINVAL;
     if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;                 // cu_seqlens is int32
     // one ROW must stay 32-bit addressable (per-lane byte offsets; half of that with the fp32 ew decay of the chunked kernels); the row
     // origin is 64-bit, so total_T * C may pass 2^31
@@ -706,11 +709,13 @@ static hipError_t varlen_prepare(const ScanArgs& a, const int* cu, long total_T,
     return hipGetLastError();
 }
 
-int wkv6_forward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
-                           const void* v, const void* w, const void* u, const void* s0, void* s_out, void* y, void* workspace,
-                           size_t workspace_bytes, unsigned flags, void* stream)
+// rev_n (device int32 [n_seq], null: no map) / rev_mask: the per-tensor reversal map within every sequence (the *_varlen_rev_ex calls)
+static int varlen_forward(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                          const void* v, const void* w, const void* u, const void* s0, void* s_out, void* y, void* workspace,
+                          size_t workspace_bytes, const int* rev_n, unsigned rev_mask, unsigned flags, unsigned known, void* stream)
 {
-    if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, flags)) return rc;
+    if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, flags, known)) return rc;
+    if (rev_mask & ~(unsigned)REV_ALL) return WKV6_EINVAL;
     if (!cu_seqlens || !r || !k || !v || !w || !u || !y) return WKV6_ENULL;
     hipStream_t st = (hipStream_t)stream;
     StreamScratch scratch;
@@ -729,17 +734,21 @@ int wkv6_forward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H
     a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
     a.s_out = s_out;
     a.y = y;
+    a.rev_n = rev_n;
+    a.rev_mask = rev_n ? rev_mask : 0u;
     if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, true, flags, {y}, st)) return to_rc(e);
     if (flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN)) return to_rc(launch_scan_fwd_varlen(a, flags & WKV6_IO_F32, st));
     a.ckpt = keep ? area : nullptr;
     return to_rc(launch_chunk_fwd_varlen(a, false, st));
 }
 
-int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
-                            const void* v, const void* w, const void* u, const void* s0, const void* gy, void* gr, void* gk, void* gv,
-                            void* gw, void* gu, void* gs, void* workspace, size_t workspace_bytes, unsigned flags, void* stream)
+static int varlen_backward(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                           const void* v, const void* w, const void* u, const void* s0, const void* gy, void* gr, void* gk, void* gv,
+                           void* gw, void* gu, void* gs, void* workspace, size_t workspace_bytes, const int* rev_n, unsigned rev_mask,
+                           unsigned flags, unsigned known, void* stream)
 {
-    if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, flags)) return rc;
+    if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, flags, known)) return rc;
+    if (rev_mask & ~(unsigned)REV_ALL) return WKV6_EINVAL;
     if (!cu_seqlens || !r || !k || !v || !w || !u || !gy || !gr || !gk || !gv || !gw) return WKV6_ENULL;
     hipStream_t st = (hipStream_t)stream;
     const size_t need = wkv6_varlen_workspace_bytes(total_T, n_seq, C, H);
@@ -758,6 +767,8 @@ int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int 
     a.s0 = s0;
     a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
     a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu; a.gs = gs;
+    a.rev_n = rev_n;
+    a.rev_mask = rev_n ? rev_mask : 0u;
     const bool scan = flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN);
     // (WKV6_CKPT_VALID on the chunked path: the forward left the int arrays beside its checkpoints; the launch only zeroes the gaps)
     if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, scan || !(flags & WKV6_CKPT_VALID), flags, {gr, gk, gv, gw}, st))
@@ -769,6 +780,111 @@ int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int 
     a.ckpt = area;
     a.ckpt_valid = (flags & WKV6_CKPT_VALID) ? 1 : 0;
     return to_rc(launch_chunk_bwd_varlen(a, st));
+}
+
+int wkv6_forward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                           const void* v, const void* w, const void* u, const void* s0, void* s_out, void* y, void* workspace,
+                           size_t workspace_bytes, unsigned flags, void* stream)
+{
+    return varlen_forward(total_T, n_seq, max_seqlen, C, H, cu_seqlens, r, k, v, w, u, s0, s_out, y, workspace, workspace_bytes, nullptr, 0u,
+                          flags, VARLEN_FLAGS, stream);
+}
+
+int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                            const void* v, const void* w, const void* u, const void* s0, const void* gy, void* gr, void* gk, void* gv,
+                            void* gw, void* gu, void* gs, void* workspace, size_t workspace_bytes, unsigned flags, void* stream)
+{
+    return varlen_backward(total_T, n_seq, max_seqlen, C, H, cu_seqlens, r, k, v, w, u, s0, gy, gr, gk, gv, gw, gu, gs, workspace,
+                           workspace_bytes, nullptr, 0u, flags, VARLEN_FLAGS, stream);
+}
+
+int wkv6_forward_varlen_rev_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                               const void* v, const void* w, const void* u, void* y, void* workspace, size_t workspace_bytes,
+                               const int* rev_n, unsigned rev_mask, unsigned flags, void* stream)
+{
+    return varlen_forward(total_T, n_seq, max_seqlen, C, H, cu_seqlens, r, k, v, w, u, nullptr, nullptr, y, workspace, workspace_bytes, rev_n,
+                          rev_mask, flags, VARLEN_REV_FLAGS, stream);
+}
+
+int wkv6_backward_varlen_rev_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* r, const void* k,
+                                const void* v, const void* w, const void* u, const void* gy, void* gr, void* gk, void* gv, void* gw,
+                                void* gu, void* workspace, size_t workspace_bytes, const int* rev_n, unsigned rev_mask, unsigned flags,
+                                void* stream)
+{
+    return varlen_backward(total_T, n_seq, max_seqlen, C, H, cu_seqlens, r, k, v, w, u, nullptr, gy, gr, gk, gv, gw, gu, nullptr, workspace,
+                           workspace_bytes, rev_n, rev_mask, flags, VARLEN_REV_FLAGS, stream);
+}
+
+// The packed pair: both problems over the same sequences.  s[i].ckpt / ckpt_bytes is one wkv6_varlen_workspace_bytes() workspace per
+// problem; the prepared int arrays (which both problems read) live in s[0]'s.  The forward may keep no checkpoints (either ckpt null; the
+// int arrays then live in stream-ordered scratch when s[0].ckpt is null); the backward needs both, as the forward left them.
+static int varlen_pair_args(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu, const void* u, const wkv6_seq_set* s,
+                            unsigned flags, bool bwd, ScanArgs (&a)[2], float* (&area)[2])
+{
+    if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, flags, VARLEN_PAIR_FLAGS)) return rc;
+    if (flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN)) return WKV6_EUNSUPPORTED;
+    if (!cu || !u || !s) return WKV6_ENULL;
+    const size_t need = wkv6_varlen_workspace_bytes(total_T, n_seq, C, H);
+    for (int i = 0; i < 2; ++i) {
+        const wkv6_seq_set& q = s[i];
+        if (q.rev_mask & ~(unsigned)REV_ALL) return WKV6_EINVAL;
+        if (!q.r || !q.k || !q.v || !q.w) return WKV6_ENULL;
+        if (bwd ? (!q.gy || !q.gr || !q.gk || !q.gv || !q.gw || !q.ckpt) : !q.y) return WKV6_ENULL;
+        if (q.ckpt && q.ckpt_bytes < need) return WKV6_EWORKSPACE;
+        if (bwd ? !varlen_aligned({q.gr, q.gk, q.gv, q.gw}) : !varlen_aligned({q.y})) return WKV6_EINVAL;
+    }
+    for (int i = 0; i < 2; ++i) {
+        const wkv6_seq_set& q = s[i];
+        a[i] = base_args(n_seq, max_seqlen, C, H, q.r, q.k, q.v, q.w, u, flags);
+        a[i].rev_n = q.rev_n;
+        a[i].rev_mask = q.rev_n ? q.rev_mask : 0u;
+        area[i] = q.ckpt ? reinterpret_cast<float*>(reinterpret_cast<char*>(q.ckpt) + varlen_int_bytes(n_seq)) : nullptr;
+        if (bwd) { a[i].gy = q.gy; a[i].gr = q.gr; a[i].gk = q.gk; a[i].gv = q.gv; a[i].gw = q.gw; a[i].gu = q.gu; }
+        else a[i].y = q.y;
+    }
+    return WKV6_OK;
+}
+
+int wkv6_forward_varlen_pair_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* u,
+                                const wkv6_seq_set* s, unsigned flags, void* stream)
+{
+    ScanArgs a[2];
+    float* area[2];
+    if (int rc = varlen_pair_args(total_T, n_seq, max_seqlen, C, H, cu_seqlens, u, s, flags, false, a, area)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    StreamScratch scratch;
+    void* ints = s[0].ckpt;
+    if (!ints) {
+        ints = scratch.get(varlen_int_bytes(n_seq), st);
+        if (!ints) return WKV6_EWORKSPACE;
+    }
+    float* unused = nullptr;
+    for (int i = 0; i < 2; ++i) {
+        varlen_carve(a[i], ints, total_T, n_seq, &unused);
+        a[i].ckpt = area[i];
+    }
+    if (hipError_t e = varlen_prepare(a[0], cu_seqlens, total_T, max_seqlen, true, flags, {s[0].y, s[1].y}, st)) return to_rc(e);
+    return to_rc(launch_chunk_fwd_varlen_pair(a[0], a[1], st));
+}
+
+int wkv6_backward_varlen_pair_ex(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const void* u,
+                                 const wkv6_seq_set* s, unsigned flags, void* stream)
+{
+    ScanArgs a[2];
+    float* area[2];
+    if (int rc = varlen_pair_args(total_T, n_seq, max_seqlen, C, H, cu_seqlens, u, s, flags, true, a, area)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    float* unused = nullptr;
+    for (int i = 0; i < 2; ++i) {
+        varlen_carve(a[i], s[0].ckpt, total_T, n_seq, &unused);
+        a[i].ckpt = area[i];
+        a[i].ckpt_valid = 1;
+    }
+    // (the forward left the int arrays beside s[0]'s checkpoints: the one preparation launch only zeroes the gaps of all eight outputs)
+    if (hipError_t e = varlen_prepare(a[0], cu_seqlens, total_T, max_seqlen, false, flags,
+                                      {s[0].gr, s[0].gk, s[0].gv, s[0].gw, s[1].gr, s[1].gk, s[1].gv, s[1].gw}, st))
+        return to_rc(e);
+    return to_rc(launch_chunk_bwd_varlen_pair(a[0], a[1], st));
 }
 
 int wkv6_forward_rev_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v, const void* w,

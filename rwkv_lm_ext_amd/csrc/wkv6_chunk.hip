@@ -709,6 +709,26 @@ __global__ __launch_bounds__(512) void chunk_fwd_varlen_kernel(const ScanArgs a)
     chunk_fwd_body<W_RAW, STATE_ONLY, false, false, true, false, false, true>(a, blockIdx.x, 0u, raw);
 }
 
+// Packed rows under a per-tensor reversal map (a.rev_n, indexed by the sequence): general token addressing from the sequence's first token --
+// scan position p < rev_n[b] of a tensor named in a.rev_mask is token tok_off[b] + rev_n[b] - 1 - p.  Kernels of their own again: the
+// plain packed instantiations above keep their instruction streams.
+template <bool W_RAW, bool STATE_ONLY>
+__global__ __launch_bounds__(512) void chunk_fwd_varlen_rev_kernel(const ScanArgs a)
+{
+    FwdRaw raw;
+    chunk_fwd_body<W_RAW, STATE_ONLY, false, false, false, false, false, true>(a, blockIdx.x, 0u, raw);
+}
+
+// chunk_fwd_pair_kernel on packed rows: slots [0, n_seq H) serve a0, the rest a1; both problems share lens / tok_off / ck_off / order
+template <bool W_RAW>
+__global__ __launch_bounds__(512) void chunk_fwd_varlen_pair_kernel(const ScanArgs a0, const ScanArgs a1)
+{
+    const unsigned n = (unsigned)(a0.B * a0.H);
+    const bool second = blockIdx.x >= n;
+    FwdRaw raw;
+    chunk_fwd_body<W_RAW, false, false, false, false, false, false, true>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, 0u, raw);
+}
+
 // Two problems of the same shape in one grid of 2 B H workgroups: slots [0, B H) serve a0, the rest a1 (src/model_bi.py:331-348,
 // src/model_ext.py:421-437: the forward-direction and the reversed-direction operator calls of a bidirectional time-mix layer).
 template <bool W_RAW>
@@ -874,21 +894,30 @@ hipError_t launch_chunk_fwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* sl
 }
 
 // Packed rows (a.tok_off / a.ck_off / a.lens / a.order set by the API's preparation kernel; a.B = sequences, a.T = longest length allowed).
-// One workgroup per (sequence, head) only: no split, no reversal maps, no accumulation, no GroupNorm epilogue, no two-level scan.
+// One workgroup per (sequence, head) only: no split, no whole-row `reverse`, no accumulation, no GroupNorm epilogue, no two-level scan.
+// a.rev_n (per-tensor reversal maps, indexed by the sequence) selects the general-addressing instantiations.
 template <bool W_RAW, bool STATE_ONLY> static hipError_t launch_fwd_varlen_inst(const ScanArgs& a, hipStream_t st)
 {
     constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr;
+    static LdsAttrOnce attr, attr_rev;
+    if (a.rev_n) {
+        if (hipError_t e = attr_rev.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_rev_kernel<W_RAW, STATE_ONLY>), lds)) return e;
+        hipLaunchKernelGGL((chunk_fwd_varlen_rev_kernel<W_RAW, STATE_ONLY>), dim3(a.B * a.H), dim3(512), lds, st, a);
+        return hipGetLastError();
+    }
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_kernel<W_RAW, STATE_ONLY>), lds)) return e;
     hipLaunchKernelGGL((chunk_fwd_varlen_kernel<W_RAW, STATE_ONLY>), dim3(a.B * a.H), dim3(512), lds, st, a);
     return hipGetLastError();
+}
+static bool varlen_fwd_plain(const ScanArgs& a)
+{
+    return !(a.reverse || a.accumulate || a.y_f32 || a.zero_tail || a.gn_out || a.dsum || a.ckpt_segs > 1 || a.side_compact);
 }
 hipError_t launch_chunk_fwd_varlen(const ScanArgs& a_, bool state_only, hipStream_t st)
 {
     if (!offsets_fit(a_)) return hipErrorInvalidValue;
     if (!a_.tok_off || !a_.ck_off || !a_.lens || !a_.order) return hipErrorInvalidValue;
-    if (a_.reverse || a_.rev_n || a_.accumulate || a_.y_f32 || a_.zero_tail || a_.gn_out || a_.dsum || a_.ckpt_segs > 1 || a_.side_compact)
-        return hipErrorNotSupported;
+    if (!varlen_fwd_plain(a_)) return hipErrorNotSupported;
     ScanArgs a = a_;
     a.split = 0;
     a.clk = nullptr; a.clk_slots = 0;
@@ -896,6 +925,34 @@ hipError_t launch_chunk_fwd_varlen(const ScanArgs& a_, bool state_only, hipStrea
     const bool raw = a.wkind == 1;
     if (state_only) return raw ? launch_fwd_varlen_inst<true, true>(a, st) : launch_fwd_varlen_inst<false, true>(a, st);
     return raw ? launch_fwd_varlen_inst<true, false>(a, st) : launch_fwd_varlen_inst<false, false>(a, st);
+}
+
+// Both problems of a bidirectional composition on packed rows in one launch: the same sequences (one set of prepared int arrays), each
+// problem with its own tensors, reversal map and checkpoint area (either may keep none)
+hipError_t launch_chunk_fwd_varlen_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipStream_t st)
+{
+    if (!offsets_fit(a0_) || !offsets_fit(a1_)) return hipErrorInvalidValue;
+    if (a0_.B != a1_.B || a0_.T != a1_.T || a0_.C != a1_.C || a0_.H != a1_.H || a0_.wkind != a1_.wkind) return hipErrorInvalidValue;
+    if (!a0_.tok_off || !a0_.ck_off || !a0_.lens || !a0_.order) return hipErrorInvalidValue;
+    if (a0_.tok_off != a1_.tok_off || a0_.ck_off != a1_.ck_off || a0_.lens != a1_.lens || a0_.order != a1_.order || a0_.ck_stride != a1_.ck_stride)
+        return hipErrorInvalidValue;
+    if (!varlen_fwd_plain(a0_) || !varlen_fwd_plain(a1_)) return hipErrorNotSupported;
+    ScanArgs a0 = a0_, a1 = a1_;
+    for (ScanArgs* a : {&a0, &a1}) {
+        a->split = 0;
+        a->clk = nullptr; a->clk_slots = 0;
+        attach_debug_buffer(*a);
+    }
+    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
+    static LdsAttrOnce attr_raw, attr_ew;
+    if (a0.wkind == 1) {
+        if (hipError_t e = attr_raw.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_pair_kernel<true>), lds)) return e;
+        hipLaunchKernelGGL((chunk_fwd_varlen_pair_kernel<true>), dim3(2 * a0.B * a0.H), dim3(512), lds, st, a0, a1);
+    } else {
+        if (hipError_t e = attr_ew.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_pair_kernel<false>), lds)) return e;
+        hipLaunchKernelGGL((chunk_fwd_varlen_pair_kernel<false>), dim3(2 * a0.B * a0.H), dim3(512), lds, st, a0, a1);
+    }
+    return hipGetLastError();
 }
 
 // state recurrence only, dumping the stage-entry states into a.ckpt (first half of the self-contained backward)

@@ -1346,6 +1346,24 @@ __global__ __launch_bounds__(768) void chunk_bwd12k_varlen_kernel(const ScanArgs
     chunk_bwd12k_body<W_RAW, 0, false, true, false, false, 0, true>(a, blockIdx.x, cy);
 }
 
+// ... under a per-tensor reversal map (a.rev_n, indexed by the sequence): general token addressing, kernels of their own (wkv6_chunk.hip)
+template <bool W_RAW>
+__global__ __launch_bounds__(768) void chunk_bwd12k_varlen_rev_kernel(const ScanArgs a)
+{
+    BwdCarry cy;
+    chunk_bwd12k_body<W_RAW, 0, false, false, false, false, 0, true>(a, blockIdx.x, cy);
+}
+
+// the backward of chunk_fwd_varlen_pair_kernel: slots [0, n_seq H) serve a0, the rest a1
+template <bool W_RAW>
+__global__ __launch_bounds__(768) void chunk_bwd12k_varlen_pair_kernel(const ScanArgs a0, const ScanArgs a1)
+{
+    const unsigned n = (unsigned)(a0.B * a0.H);
+    const bool second = blockIdx.x >= n;
+    BwdCarry cy;
+    chunk_bwd12k_body<W_RAW, 0, false, false, false, false, 0, true>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, cy);
+}
+
 // the backward of chunk_fwd_pair_kernel (wkv6_chunk.hip): two problems of one shape, slots [0, B H) serve a0, the rest a1
 template <bool W_RAW>
 __global__ __launch_bounds__(768) void chunk_bwd12k_pair_kernel(const ScanArgs a0, const ScanArgs a1)
@@ -1496,21 +1514,29 @@ hipError_t launch_chunk_bwd(const ScanArgs& a_, hipStream_t st)
 }
 
 // Packed rows: state pass (unless the forward left the checkpoints) + reverse pass, one workgroup per (sequence, head).  No split, no
-// reversal maps, no wkv6_bi halves, no two-level scan over T.
+// whole-row `reverse`, no wkv6_bi halves, no two-level scan over T; a.rev_n selects the general-addressing instantiations.
 template <bool W_RAW> static hipError_t launch_bwd12k_varlen_inst(const ScanArgs& a, hipStream_t st)
 {
-    static LdsAttrOnce attr;
+    static LdsAttrOnce attr, attr_rev;
+    if (a.rev_n) {
+        if (hipError_t e = attr_rev.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_rev_kernel<W_RAW>), BWD12K_LDS)) return e;
+        hipLaunchKernelGGL((chunk_bwd12k_varlen_rev_kernel<W_RAW>), dim3(a.B * a.H), dim3(768), BWD12K_LDS, st, a);
+        return hipGetLastError();
+    }
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_kernel<W_RAW>), BWD12K_LDS)) return e;
     hipLaunchKernelGGL((chunk_bwd12k_varlen_kernel<W_RAW>), dim3(a.B * a.H), dim3(768), BWD12K_LDS, st, a);
     return hipGetLastError();
+}
+static bool varlen_bwd_plain(const ScanArgs& a)
+{
+    return !(a.reverse || a.accumulate || a.zero_tail || a.g_f32[0] || a.g_f32[1] || a.g_f32[2] || a.g_f32[3] || a.g_in || a.rc_in || a.ckpt_segs > 1 ||
+             a.side_compact);
 }
 hipError_t launch_chunk_bwd_varlen(const ScanArgs& a_, hipStream_t st)
 {
     if (!a_.ckpt || !a_.tok_off || !a_.ck_off || !a_.lens || !a_.order) return hipErrorInvalidValue;
     if (a_.wkind != 1 && ((long)a_.T + 64) * a_.C >= (1L << 30)) return hipErrorInvalidValue;
-    if (a_.reverse || a_.rev_n || a_.accumulate || a_.zero_tail || a_.g_f32[0] || a_.g_f32[1] || a_.g_f32[2] || a_.g_f32[3] || a_.g_in || a_.rc_in ||
-        a_.ckpt_segs > 1 || a_.side_compact)
-        return hipErrorNotSupported;
+    if (!varlen_bwd_plain(a_)) return hipErrorNotSupported;
     ScanArgs a = a_;
     a.split = 0;
     a.clk = nullptr; a.clk_slots = 0;
@@ -1521,6 +1547,34 @@ hipError_t launch_chunk_bwd_varlen(const ScanArgs& a_, hipStream_t st)
     }
     attach_debug_buffer(a);
     return a.wkind ? launch_bwd12k_varlen_inst<true>(a, st) : launch_bwd12k_varlen_inst<false>(a, st);
+}
+
+// Backward of both problems of a packed pair in one launch; both checkpoint sets must come from the forward (ckpt_valid), and with them
+// the prepared int arrays the two problems share
+hipError_t launch_chunk_bwd_varlen_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipStream_t st)
+{
+    if (a0_.B != a1_.B || a0_.T != a1_.T || a0_.C != a1_.C || a0_.H != a1_.H || a0_.wkind != a1_.wkind) return hipErrorInvalidValue;
+    if (!a0_.tok_off || !a0_.ck_off || !a0_.lens || !a0_.order) return hipErrorInvalidValue;
+    if (a0_.tok_off != a1_.tok_off || a0_.ck_off != a1_.ck_off || a0_.lens != a1_.lens || a0_.order != a1_.order || a0_.ck_stride != a1_.ck_stride)
+        return hipErrorInvalidValue;
+    if (a0_.wkind != 1 && ((long)a0_.T + 64) * a0_.C >= (1L << 30)) return hipErrorInvalidValue;
+    const auto plain = [](const ScanArgs& a) { return varlen_bwd_plain(a) && a.ckpt && a.ckpt_valid; };
+    if (!plain(a0_) || !plain(a1_)) return hipErrorNotSupported;
+    ScanArgs a0 = a0_, a1 = a1_;
+    for (ScanArgs* a : {&a0, &a1}) {
+        a->split = 0;
+        a->clk = nullptr; a->clk_slots = 0;
+        attach_debug_buffer(*a);
+    }
+    static LdsAttrOnce attr_raw, attr_ew;
+    if (a0.wkind == 1) {
+        if (hipError_t e = attr_raw.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_pair_kernel<true>), BWD12K_LDS)) return e;
+        hipLaunchKernelGGL((chunk_bwd12k_varlen_pair_kernel<true>), dim3(2 * a0.B * a0.H), dim3(768), BWD12K_LDS, st, a0, a1);
+    } else {
+        if (hipError_t e = attr_ew.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_pair_kernel<false>), BWD12K_LDS)) return e;
+        hipLaunchKernelGGL((chunk_bwd12k_varlen_pair_kernel<false>), dim3(2 * a0.B * a0.H), dim3(768), BWD12K_LDS, st, a0, a1);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_chunk_bwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* slots, hipStream_t st)

@@ -232,6 +232,106 @@ __global__ void ddlerp_bwd_kernel(const LerpArgs a)
             make_float4(acc[s][0], acc[s][1], acc[s][2], acc[s][3]);
 }
 
+// Packed batch under a reversal map (a.cu and a.rev_n, [n_seq]): the stream of sequence s is "its first rev_n[s] tokens reversed, the rest in
+// place" (rev_n clamped to the sequence's length), and the token in front of the stream's first token is shifted0[s] (null: zero), never a
+// token of another sequence.  A row's sequence comes from the bisection of the plain packed kernels; the neighbours are prev_tok / next_tok
+// within the sequence, so the backward walks rows p, p + nparts, ... as the dense reversed-stream branch does, with the same summation
+// order.  Rows in front of cu[0] belong to no sequence and take the plain neighbour; rows from cu[n_seq] on continue the last sequence
+// in place, as in the plain packed kernels.
+struct SeqSpan {
+    long start;               // first row of the sequence (clamped to [0, rows])
+    int slen, nrev;           // rows the stream walks; reversed span
+    int sq;                   // sequence, -1: none
+};
+__device__ __forceinline__ SeqSpan seq_span(const LerpArgs& a, long row)
+{
+    const long rows = (long)a.B * a.T;
+    SeqSpan p;
+    p.sq = seq_of_row(a.cu, a.n_seq, row);
+    if (p.sq < 0) { p.start = 0; p.slen = (int)min((long)a.cu[0], rows); p.nrev = 0; return p; }      // (row < cu[0])
+    p.start = max((long)a.cu[p.sq], 0L);
+    const long end = min(max((long)a.cu[p.sq + 1], p.start), rows);                  // (row >= cu[sq], so start <= row < rows)
+    p.slen = (int)((p.sq + 1 < a.n_seq ? end : rows) - p.start);
+    p.nrev = (int)min((long)max(a.rev_n[p.sq], 0), end - p.start);
+    return p;
+}
+
+template <int NS, bool HAS_M>
+__global__ void ddlerp_fwd_varlen_rev_kernel(const LerpArgs a)
+{
+    const long row = blockIdx.x;
+    const int c = 4 * threadIdx.x;
+    float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f};
+    ld4(a.x + row * a.C + c, x);
+    const SeqSpan sp = seq_span(a, row);
+    const int tp = prev_tok((int)(row - sp.start), sp.nrev);
+    if (tp >= 0) ld4(a.x + (sp.start + tp) * a.C + c, xp);
+    else if (a.shifted0 && sp.sq >= 0) ld4(a.shifted0 + (long)sp.sq * a.C + c, xp);
+    const long plane = (long)a.B * a.T * a.C;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float maa[4], m[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
+        ld4(a.maa + (long)s * a.C + c, maa);
+        if constexpr (HAS_M) ld4(a.m + s * plane + row * a.C + c, m);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = fmaf(xp[q] - x[q], maa[q] + m[q], x[q]);
+        io4<bf16_t>::store(a.out + s * plane + row * a.C + c, o);
+    }
+}
+
+template <int NS, bool HAS_M>
+__global__ void ddlerp_bwd_varlen_rev_kernel(const LerpArgs a)
+{
+    const int c = 4 * threadIdx.x;
+    const long plane = (long)a.B * a.T * a.C, rows = (long)a.B * a.T;
+    float maa[NS][4], acc[NS][4];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        ld4(a.maa + (long)s * a.C + c, maa[s]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[s][q] = 0.f;
+    }
+    for (long row = blockIdx.x; row < rows; row += gridDim.x) {
+        float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
+        ld4(a.x + row * a.C + c, x);
+        const SeqSpan sp = seq_span(a, row);
+        const int t = (int)(row - sp.start);
+        const int tp = prev_tok(t, sp.nrev), tn = next_tok(t, sp.nrev, sp.slen);
+        if (tp >= 0) ld4(a.x + (sp.start + tp) * a.C + c, xp);
+        else if (a.shifted0 && sp.sq >= 0) ld4(a.shifted0 + (long)sp.sq * a.C + c, xp);
+        if (tn >= 0) {                                        // (summed in the order of the dense kernel: the two agree bit for bit)
+            const long rown = sp.start + tn;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                float dn[4], mn[4] = {0.f, 0.f, 0.f, 0.f};
+                ld4(a.dout + s * plane + rown * a.C + c, dn);
+                if constexpr (HAS_M) ld4(a.m + s * plane + rown * a.C + c, mn);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) g[q] = fmaf(dn[q], maa[s][q] + mn[q], g[q]);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            float d[4], m[4] = {0.f, 0.f, 0.f, 0.f};
+            ld4(a.dout + s * plane + row * a.C + c, d);
+            if constexpr (HAS_M) ld4(a.m + s * plane + row * a.C + c, m);
+            float dm[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                g[q] = fmaf(d[q], 1.f - (maa[s][q] + m[q]), g[q]);
+                dm[q] = d[q] * (xp[q] - x[q]);
+                acc[s][q] += dm[q];
+            }
+            if constexpr (HAS_M) io4<bf16_t>::store(a.dm + s * plane + row * a.C + c, dm);
+        }
+        io4<bf16_t>::store(a.dx + row * a.C + c, g);
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        *reinterpret_cast<float4*>(a.dmaa_part + ((long)blockIdx.x * NS + s) * a.C + c) =
+            make_float4(acc[s][0], acc[s][1], acc[s][2], acc[s][3]);
+}
+
 struct GnArgs {
     long rows;
     int C, H;
@@ -383,6 +483,11 @@ int check_rows(long rows, int C)
 
 template <int NS, bool HAS_M> void launch_lerp(const LerpArgs& a, bool bwd, hipStream_t st)
 {
+    if (a.cu && a.rev_n) {
+        if (bwd) hipLaunchKernelGGL((ddlerp_bwd_varlen_rev_kernel<NS, HAS_M>), dim3(a.nparts), dim3(a.C / 4), 0, st, a);
+        else hipLaunchKernelGGL((ddlerp_fwd_varlen_rev_kernel<NS, HAS_M>), dim3((unsigned)((long)a.B * a.T)), dim3(a.C / 4), 0, st, a);
+        return;
+    }
     if (a.cu) {
         if (bwd) hipLaunchKernelGGL((ddlerp_bwd_kernel<NS, HAS_M, true>), dim3(a.nparts), dim3(a.C / 4), 0, st, a);
         else hipLaunchKernelGGL((ddlerp_fwd_kernel<NS, HAS_M, true>), dim3((unsigned)((long)a.B * a.T)), dim3(a.C / 4), 0, st, a);
@@ -474,6 +579,39 @@ int wkv6_ddlerp_varlen_backward(long total_T, int n_seq, int C, int NS, const in
     a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
     a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
     a.cu = cu_seqlens; a.n_seq = n_seq;
+    a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
+    return dispatch_lerp(a, true, (hipStream_t)stream);
+}
+
+// rev_n == null: the plain packed shift
+int wkv6_ddlerp_varlen_rev_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                                   const void* m, const void* maa, const int* rev_n, void* out, void* stream)
+{
+    if (!rev_n) return wkv6_ddlerp_varlen_forward(total_T, n_seq, C, NS, cu_seqlens, x, shifted0, m, maa, out, stream);
+    if (total_T < 1 || n_seq < 1) return WKV6_EINVAL;
+    if (int rc = check_rows(total_T, C)) return rc;
+    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;
+    if (!cu_seqlens || !x || !maa || !out) return WKV6_ENULL;
+    LerpArgs a = {};
+    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
+    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    a.cu = cu_seqlens; a.n_seq = n_seq; a.rev_n = rev_n;
+    a.out = (bf16_t*)out;
+    return dispatch_lerp(a, false, (hipStream_t)stream);
+}
+int wkv6_ddlerp_varlen_rev_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                                    const void* m, const void* maa, const int* rev_n, const void* dout, void* dx, void* dm,
+                                    float* dmaa_part, int nparts, void* stream)
+{
+    if (!rev_n) return wkv6_ddlerp_varlen_backward(total_T, n_seq, C, NS, cu_seqlens, x, shifted0, m, maa, dout, dx, dm, dmaa_part, nparts, stream);
+    if (total_T < 1 || n_seq < 1 || nparts < 1) return WKV6_EINVAL;
+    if (int rc = check_rows(total_T, C)) return rc;
+    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;
+    if (!cu_seqlens || !x || !maa || !dout || !dx || !dmaa_part || (m && !dm)) return WKV6_ENULL;
+    LerpArgs a = {};
+    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
+    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    a.cu = cu_seqlens; a.n_seq = n_seq; a.rev_n = rev_n;
     a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
     return dispatch_lerp(a, true, (hipStream_t)stream);
 }

@@ -170,9 +170,13 @@ hipError_t launch_chunk_bwd_bi(const ScanArgs& a1, const ScanArgs& a2, int* slot
 int bi_slots(int BH);                        // workgroup slots such a launch uses (0: does not apply)
 hipError_t launch_chunk_bwd12k(const ScanArgs& a, hipStream_t st);    // reverse pass over 64-token row-order checkpoints, a.split as given (wkv6_chunk_bwd12k.hip)
 size_t chunk_ckpt_floats(int B, int T, int H);
-// packed variable-length rows (ScanArgs: tok_off, ck_off, ck_stride), one workgroup per (sequence, head); bf16 I/O
+// packed variable-length rows (ScanArgs: tok_off, ck_off, ck_stride), one workgroup per (sequence, head); bf16 I/O; a.rev_n ([B], indexed
+// by the sequence) applies the per-tensor reversal map within each sequence
 hipError_t launch_chunk_fwd_varlen(const ScanArgs& a, bool state_only, hipStream_t st);
 hipError_t launch_chunk_bwd_varlen(const ScanArgs& a, hipStream_t st);   // a.ckpt_valid == 0: runs the state pass first
+// two packed problems over the same sequences (shared lens / tok_off / ck_off / order) in one launch of 2 B H workgroups
+hipError_t launch_chunk_fwd_varlen_pair(const ScanArgs& a0, const ScanArgs& a1, hipStream_t st);
+hipError_t launch_chunk_bwd_varlen_pair(const ScanArgs& a0, const ScanArgs& a1, hipStream_t st);   // both with ckpt_valid
 hipError_t launch_scan_fwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st);
 hipError_t launch_scan_bwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st);
 hipError_t launch_chunk_state_pass(const ScanArgs& a, hipStream_t st);   // state recurrence only (s_out, ckpt, dsum)

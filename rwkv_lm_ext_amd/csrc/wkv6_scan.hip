@@ -768,10 +768,11 @@ hipError_t launch_scan_bwd(const ScanArgs& a, bool io_f32, hipStream_t st)
     return hipGetLastError();
 }
 
-// Packed variable-length rows: the same kernels, addressed through a.tok_off / a.order (one workgroup per (sequence, head))
+// Packed variable-length rows: the same kernels, addressed through a.tok_off / a.order (one workgroup per (sequence, head)); a reversal
+// map (a.rev_n, a.reverse) is read by the sequence index b = a.order[slot] in all three kernels and applies within the sequence
 static bool varlen_scan_ok(const ScanArgs& a)
 {
-    return a.tok_off && a.lens && a.order && !a.reverse && !a.rev_n && !a.accumulate && !a.zero_tail && !a.y_f32;
+    return a.tok_off && a.lens && a.order && !a.accumulate && !a.zero_tail && !a.y_f32;
 }
 hipError_t launch_scan_fwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st)
 {

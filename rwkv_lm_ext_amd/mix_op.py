@@ -131,12 +131,73 @@ class _DDLerpVarlen(torch.autograd.Function):
         return dx, part.sum(0).to(maa.dtype), dm, dshift, None
 
 
+class _DDLerpVarlenRev(torch.autograd.Function):
+    """_DDLerpVarlen with the shift of sequence s taken over the stream "its first rev_n[s] tokens reversed, the rest in place"
+    (rev_n int32 [n_seq], clamped to the sequence's length on the device)."""
+
+    @staticmethod
+    def forward(ctx, x, maa, m, shifted0, cu_seqlens, rev_n):
+        x, maa = _require(x, "x"), _require(maa, "maa")
+        m = None if m is None else _require(m, "m")
+        shifted0 = None if shifted0 is None else _require(shifted0, "shifted0")
+        n_seq = _check_cu(cu_seqlens, x.device)
+        C = x.shape[-1]
+        total = x.numel() // C
+        if x.dim() == 3 and x.shape[0] != 1:
+            raise RuntimeError("a packed batch is [1, total_T, C] (or [total_T, C])")
+        if shifted0 is not None and tuple(shifted0.shape) != (n_seq, C):
+            raise RuntimeError(f"shifted0 must be [n_seq, C] = {(n_seq, C)}")
+        if not (isinstance(rev_n, torch.Tensor) and rev_n.dtype == torch.int32 and rev_n.is_contiguous()
+                and tuple(rev_n.shape) == (n_seq,) and rev_n.device == x.device):
+            raise RuntimeError("rev_n must be a contiguous int32 [n_seq] tensor on the device of x")
+        NS = maa.shape[0]
+        out = torch.empty((NS,) + tuple(x.shape), device=x.device, dtype=x.dtype)
+        with torch.cuda.device(x.device):
+            rc = _lib.load().wkv6_ddlerp_varlen_rev_forward(total, n_seq, C, NS, _ptr(cu_seqlens), _ptr(x), _ptr(shifted0), _ptr(m),
+                                                            _ptr(maa), _ptr(rev_n), _ptr(out), _stream_ptr())
+        _lib.check(rc, "ddlerp varlen rev forward")
+        ctx.save_for_backward(x, maa, m, shifted0, cu_seqlens, rev_n)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, maa, m, shifted0, cu, rev_n = ctx.saved_tensors
+        dout = _require(dout, "dout")
+        C = x.shape[-1]
+        total = x.numel() // C
+        n_seq = cu.numel() - 1
+        NS = maa.shape[0]
+        nparts = min(_NPARTS, total)
+        dx = torch.empty_like(x)
+        dm = None if m is None else torch.empty_like(m)
+        part = torch.empty((nparts, NS, C), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            rc = _lib.load().wkv6_ddlerp_varlen_rev_backward(total, n_seq, C, NS, _ptr(cu), _ptr(x), _ptr(shifted0), _ptr(m), _ptr(maa),
+                                                             _ptr(rev_n), _ptr(dout), _ptr(dx), _ptr(dm), _ptr(part), nparts,
+                                                             _stream_ptr())
+        _lib.check(rc, "ddlerp varlen rev backward")
+        dshift = None
+        if shifted0 is not None and ctx.needs_input_grad[3]:
+            # shifted0[s] enters only the stream's first token of a non-empty sequence s: cu[s] + rev_n[s] - 1 where a reversed span opens
+            # the stream, else cu[s] (device index arithmetic only: nobody reads cu_seqlens or rev_n on the host)
+            start = cu[:-1].long().clamp(0, total)
+            length = (cu[1:].long().clamp(0, total) - start).clamp_min(0)
+            nrev = torch.minimum(rev_n.long().clamp_min(0), length)
+            first = (start + (nrev - 1).clamp_min(0)).clamp(0, total - 1)
+            alive = (length > 0).view(1, n_seq, 1).float()
+            d0 = dout.reshape(NS, total, C)[:, first].float()
+            wgt = maa.float().view(NS, 1, C) + (0.0 if m is None else m.reshape(NS, total, C)[:, first].float())
+            dshift = ((d0 * wgt) * alive).sum(0).to(shifted0.dtype)
+        return dx, part.sum(0).to(maa.dtype), dm, dshift, None, None
+
+
 def ddlerp(x, maa, m=None, shifted0=None, rev_n=None, cu_seqlens=None):
     """maa: [NS,C] (or anything reshapeable to it, e.g. five [1,1,C] parameters stacked).  cu_seqlens (int32 [n_seq + 1]): x is a packed
-    variable-length batch [1,total_T,C] and the shift does not cross a sequence boundary (shifted0 is then [n_seq,C])."""
+    variable-length batch [1,total_T,C] and the shift does not cross a sequence boundary (shifted0 is then [n_seq,C]); rev_n is then
+    int32 [n_seq]: the reversed span of every sequence's stream."""
     if cu_seqlens is not None:
         if rev_n is not None:
-            raise RuntimeError("ddlerp: reversal maps are not available on a packed batch")
+            return _DDLerpVarlenRev.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, cu_seqlens, rev_n)
         return _DDLerpVarlen.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, cu_seqlens)
     return _DDLerp.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, rev_n)
 

@@ -268,6 +268,73 @@ def RUN_CUDA_RWKV6_VARLEN(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen):
     return WKV_6_VARLEN.apply(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen)
 
 
+class WKV_6_VARLEN_REV(torch.autograd.Function):
+    """WKV_6_REV on a packed variable-length batch: rev_n int32 [n_seq] = the number of leading tokens of every sequence that the tensors
+    named in rev_mask hold in reverse order.  Every sequence starts from a zero state; the forward keeps its workspace (state
+    checkpoints and the prepared per-sequence arrays) for the backward like WKV_6_VARLEN."""
+
+    @staticmethod
+    def forward(ctx, total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen, rev_n, rev_mask):
+        with torch.no_grad():
+            _assert_inputs(C, H, r, k, v, w, u)
+            ctx.C, ctx.H, ctx.max_seqlen, ctx.shape, ctx.rev_mask = C, H, int(max_seqlen), r.shape, rev_mask
+            r, k, v, w = (t.view(total_T, C) for t in (r, k, v, w))
+            ctx.save_for_backward(r, k, v, w, u, cu_seqlens, rev_n)
+            n_seq = cu_seqlens.numel() - 1
+            ctx.ws = wkv6_op.new_varlen_workspace(total_T, n_seq, C, H, r.device) if _keep_ckpt(ctx) else None
+            return wkv6_op.forward_varlen_rev_ex(r, k, v, w, u, H, cu_seqlens, ctx.max_seqlen, rev_n, rev_mask, ws=ctx.ws).view(ctx.shape)
+
+    @staticmethod
+    def backward(ctx, gy):
+        with torch.no_grad():
+            assert gy.dtype == torch.bfloat16
+            r, k, v, w, u, cu, rev_n = ctx.saved_tensors
+            gy = gy.contiguous().view(r.shape)
+            gr, gk, gv, gw, gu = wkv6_op.backward_varlen_rev_ex(r, k, v, w, u, gy, ctx.H, cu, ctx.max_seqlen, rev_n, ctx.rev_mask,
+                                                                ws=ctx.ws, ckpt_valid=ctx.ws is not None)
+            ctx.ws = None                              # (a second backward through this node, retain_graph=True, runs self-contained)
+            gr, gk, gv, gw = (t.view(ctx.shape) for t in (gr, gk, gv, gw))
+            return (None, None, None, gr, gk, gv, gw, _sum_bf16(gu, (ctx.H, ctx.C // ctx.H)), None, None, None, None)
+
+
+class WKV_6_VARLEN_PAIR(torch.autograd.Function):
+    """WKV_6_PAIR on a packed variable-length batch, one launch per pass: problem 0 = the plain packed call on (r0, k0, v0, w0), problem 1 =
+    the packed call on (r1, k1, v1, w1) under the map (rev_n [n_seq], rev_mask).  Returns (y0, y1), bit-identical to the two calls."""
+
+    @staticmethod
+    def forward(ctx, total_T, C, H, r0, k0, v0, w0, r1, k1, v1, w1, u, cu_seqlens, max_seqlen, rev_n, rev_mask):
+        with torch.no_grad():
+            _assert_inputs(C, H, r0, k0, v0, w0, u)
+            _assert_inputs(C, H, r1, k1, v1, w1, u)
+            ctx.C, ctx.H, ctx.max_seqlen, ctx.shape, ctx.rev_mask = C, H, int(max_seqlen), r0.shape, rev_mask
+            r0, k0, v0, w0, r1, k1, v1, w1 = (t.view(total_T, C) for t in (r0, k0, v0, w0, r1, k1, v1, w1))
+            ctx.save_for_backward(r0, k0, v0, w0, r1, k1, v1, w1, u, cu_seqlens, rev_n)
+            n_seq = cu_seqlens.numel() - 1
+            ctx.wss = [wkv6_op.new_varlen_workspace(total_T, n_seq, C, H, r0.device) if _keep_ckpt(ctx) else None for _ in range(2)]
+            sets = [dict(r=r0, k=k0, v=v0, w=w0, ckpt=ctx.wss[0]),
+                    dict(r=r1, k=k1, v=v1, w=w1, ckpt=ctx.wss[1], rev_n=rev_n, rev_mask=rev_mask)]
+            y0, y1 = wkv6_op.forward_varlen_pair_ex(H, u, sets, cu_seqlens, ctx.max_seqlen)
+            return y0.view(ctx.shape), y1.view(ctx.shape)
+
+    @staticmethod
+    def backward(ctx, gy0, gy1):
+        with torch.no_grad():
+            r0, k0, v0, w0, r1, k1, v1, w1, u, cu, rev_n = ctx.saved_tensors
+            shape = (ctx.H, ctx.C // ctx.H)
+            gy0, gy1 = gy0.contiguous().view(r0.shape), gy1.contiguous().view(r0.shape)
+            if ctx.wss[0] is None:                         # nothing was kept (or a second backward): each problem runs self-contained
+                g0 = wkv6_op.backward_varlen_rev_ex(r0, k0, v0, w0, u, gy0, ctx.H, cu, ctx.max_seqlen, None, 0)
+                g1 = wkv6_op.backward_varlen_rev_ex(r1, k1, v1, w1, u, gy1, ctx.H, cu, ctx.max_seqlen, rev_n, ctx.rev_mask)
+            else:
+                sets = [dict(r=r0, k=k0, v=v0, w=w0, gy=gy0, ckpt=ctx.wss[0]),
+                        dict(r=r1, k=k1, v=v1, w=w1, gy=gy1, ckpt=ctx.wss[1], rev_n=rev_n, rev_mask=ctx.rev_mask)]
+                g0, g1 = wkv6_op.backward_varlen_pair_ex(ctx.H, u, sets, cu, ctx.max_seqlen)
+                ctx.wss = [None, None]
+            gu = _sum_bf16(g0[4], shape) + _sum_bf16(g1[4], shape)     # as autograd adds the two calls' bf16 gu
+            grads = [t.view(ctx.shape) for t in (*g0[:4], *g1[:4])]
+            return (None, None, None, *grads, gu, None, None, None, None)
+
+
 class WKV_6STATE_VARLEN(torch.autograd.Function):
     """WKV_6STATE on a packed variable-length batch: every sequence starts from the learnable state s [H,N,N]; gs is summed over the
     sequences."""

@@ -560,6 +560,124 @@ def backward_rev_ex(r, k, v, w, u, gy, H, rev_n, rev_mask, ckpt=None, algo=None)
     return gr, gk, gv, gw, gu
 
 
+# ---- reversal maps and the pair launch on packed batches (include/wkv6_amd.h: wkv6_*_varlen_rev_ex, wkv6_*_varlen_pair_ex) ----
+def _check_rev_varlen(n_seq, rev_n, rev_mask, dev):
+    if rev_n is not None and not (isinstance(rev_n, torch.Tensor) and rev_n.dtype == torch.int32 and rev_n.is_contiguous() and
+                                  tuple(rev_n.shape) == (n_seq,) and rev_n.device == dev):
+        raise RuntimeError("rev_n must be a contiguous int32 [n_seq] tensor on the device of r")
+    if rev_mask & ~REV_ALL:
+        raise RuntimeError(f"rev_mask {rev_mask} has unknown bits")
+
+
+def forward_varlen_rev_ex(r, k, v, w, u, H, cu_seqlens, max_seqlen, rev_n, rev_mask, y=None, algo=None, ws=None, w_is_ew=False):
+    """forward_varlen_ex with the per-tensor reversal map of forward_rev_ex applied within every sequence: rev_n int32 [n_seq] (clamped to
+    the sequence's length on the device; None: no map).  No initial state.  ws: a new_varlen_workspace() buffer that keeps the checkpoints
+    for backward_varlen_rev_ex(..., ws=ws, ckpt_valid=True)."""
+    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, None, w_is_ew, algo, {})
+    if y is None:
+        y = torch.empty((total, C), device=r.device, dtype=io)
+    named["y"] = (y, (total, C), io)
+    dev = _check_tensors(n_seq, total, C, H, named, dtype=io)
+    _check_rev_varlen(n_seq, rev_n, rev_mask, dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().wkv6_forward_varlen_rev_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(r), _ptr(k), _ptr(v),
+                                                    _ptr(w), _ptr(u), _ptr(y), _ptr(ws), 0 if ws is None else ws.numel(),
+                                                    _ptr(rev_n), rev_mask, flags, _stream_ptr())
+    _lib.check(rc, "wkv6 forward_varlen_rev_ex")
+    return y
+
+
+def backward_varlen_rev_ex(r, k, v, w, u, gy, H, cu_seqlens, max_seqlen, rev_n, rev_mask, algo=None, ws=None, ckpt_valid=False,
+                           w_is_ew=False):
+    """Gradients of forward_varlen_rev_ex: (gr, gk, gv, gw [total_T,C], gu [n_seq,C] fp32 per-sequence partials); each gradient is laid
+    out like its tensor.  ckpt_valid: `ws` was filled by forward_varlen_rev_ex(..., ws=ws) on the same inputs."""
+    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, None, w_is_ew, algo, {"gy": gy})
+    dev = _check_tensors(n_seq, total, C, H, named, dtype=io)
+    _check_rev_varlen(n_seq, rev_n, rev_mask, dev)
+    gr, gk, gv, gw = (torch.empty((total, C), device=dev, dtype=io) for _ in range(4))
+    flags |= _lib.PARTIALS_F32
+    gu = torch.empty((n_seq, C), device=dev, dtype=torch.float32)
+    if ckpt_valid:
+        if ws is None:
+            raise RuntimeError("ckpt_valid needs the workspace the forward filled")
+        if io == torch.bfloat16 and algo != "scan":
+            flags |= _lib.CKPT_VALID
+    if ws is None:
+        ws = new_varlen_workspace(total, n_seq, C, H, dev)
+    with torch.cuda.device(dev):
+        rc = _lib.load().wkv6_backward_varlen_rev_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(r), _ptr(k), _ptr(v),
+                                                     _ptr(w), _ptr(u), _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu),
+                                                     _ptr(ws), ws.numel(), _ptr(rev_n), rev_mask, flags, _stream_ptr())
+    _lib.check(rc, "wkv6 backward_varlen_rev_ex")
+    return gr, gk, gv, gw, gu
+
+
+def _varlen_pair_sets(total, C, H, n_seq, sets, u, bwd):
+    """_pair_sets for packed problems: tensors [total_T, C], rev_n [n_seq], ckpt = a new_varlen_workspace() buffer per problem."""
+    bf = torch.bfloat16
+    tc = (total, C)
+    arr = (_lib.SeqSet * 2)()
+    keep = []
+    dev = None
+    for i, q in enumerate(sets):
+        named = {n: (q[n], tc, bf) for n in ("r", "k", "v", "w") + (("gy",) if bwd else ("y",))}
+        named["u"] = (u, (H, HEAD_SIZE), bf)
+        dev = _check_tensors(n_seq, total, C, H, named, dtype=bf)
+        rev_n, rev_mask = q.get("rev_n"), q.get("rev_mask", 0)
+        _check_rev_varlen(n_seq, rev_n, rev_mask, dev)
+        ckpt = q.get("ckpt")
+        if bwd and ckpt is None:
+            raise RuntimeError("wkv6 packed pair backward: both problems need the workspaces their forward wrote")
+        e = arr[i]
+        e.r, e.k, e.v, e.w = _ptr(q["r"]), _ptr(q["k"]), _ptr(q["v"]), _ptr(q["w"])
+        if bwd:
+            outs = [torch.empty(tc, device=dev, dtype=bf) for _ in range(4)] + [torch.empty((n_seq, C), device=dev, dtype=torch.float32)]
+            e.gy, e.gr, e.gk, e.gv, e.gw, e.gu = (_ptr(t) for t in [q["gy"]] + outs)
+            keep.append(outs)
+        else:
+            e.y = _ptr(q["y"])
+        e.ckpt, e.ckpt_bytes = _ptr(ckpt), 0 if ckpt is None else ckpt.numel()
+        e.rev_n, e.rev_mask = _ptr(rev_n), rev_mask if rev_n is not None else 0
+    return arr, keep, dev
+
+
+def forward_varlen_pair_ex(H, u, sets, cu_seqlens, max_seqlen):
+    """forward_pair_ex on a packed batch: `sets` = two dicts {r, k, v, w [total_T,C], [y], [ckpt], [rev_n [n_seq], rev_mask]} over the
+    same sequences; ckpt is one new_varlen_workspace() buffer per problem.  Returns (y0, y1)."""
+    if sets[0]["r"].dim() != 2:
+        raise RuntimeError("packed tensors are [total_T, C]")
+    total, C = sets[0]["r"].shape
+    n_seq = _check_cu_seqlens(cu_seqlens, sets[0]["r"].device)
+    if int(max_seqlen) < 1:
+        raise RuntimeError("max_seqlen must be >= 1")
+    for q in sets:
+        if q.get("y") is None:
+            q["y"] = torch.empty((total, C), device=q["r"].device, dtype=torch.bfloat16)
+    arr, _, dev = _varlen_pair_sets(total, C, H, n_seq, sets, u, bwd=False)
+    with torch.cuda.device(dev):
+        rc = _lib.load().wkv6_forward_varlen_pair_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(u), arr, _lib.W_RAW,
+                                                     _stream_ptr())
+    _lib.check(rc, "wkv6 forward_varlen_pair_ex")
+    return sets[0]["y"], sets[1]["y"]
+
+
+def backward_varlen_pair_ex(H, u, sets, cu_seqlens, max_seqlen):
+    """Gradients of forward_varlen_pair_ex: two tuples (gr, gk, gv, gw, gu [n_seq,C] fp32), one per problem; `sets` as in the forward
+    (with the workspaces it filled) plus gy."""
+    if sets[0]["r"].dim() != 2:
+        raise RuntimeError("packed tensors are [total_T, C]")
+    total, C = sets[0]["r"].shape
+    n_seq = _check_cu_seqlens(cu_seqlens, sets[0]["r"].device)
+    if int(max_seqlen) < 1:
+        raise RuntimeError("max_seqlen must be >= 1")
+    arr, keep, dev = _varlen_pair_sets(total, C, H, n_seq, sets, u, bwd=True)
+    with torch.cuda.device(dev):
+        rc = _lib.load().wkv6_backward_varlen_pair_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(u), arr,
+                                                      _lib.W_RAW | _lib.PARTIALS_F32, _stream_ptr())
+    _lib.check(rc, "wkv6 backward_varlen_pair_ex")
+    return tuple(keep[0]), tuple(keep[1])
+
+
 def bi_new_workspace(B, T, C, H, device):
     """Workspace of the wkv6_bi pair: the forward's fp32 y side buffer, the state checkpoints of both scans (kept from
     forward to backward when `ws` is passed to both calls) and the backward's four fp32 gradient side buffers."""
