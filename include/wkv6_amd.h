@@ -180,6 +180,43 @@ int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int 
                             const void* v, const void* w, const void* u, const void* s0, const void* gy, void* gr, void* gk, void* gv,
                             void* gw, void* gu, void* gs, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
 
+/* ---- rwkv6 on packed batches (stateful forward-only inference for a serving loop): rwkv6_cuda_forward_* over the sequences of one
+ * [total_T, C] buffer -- prompts of any mix of lengths, prefill next to one-token decode steps -- each with its state in a slot of a
+ * caller-owned pool.  Padding a stateful operator is wrong, not just wasteful: the state would scan the pad tokens.
+ *   r,k,v,y : [total_T,C] in the I/O type (bf16 / fp16 / fp32)     w : fp32 [total_T,C], the DECAY exp(-exp(w_raw)) as above     u : [H,N]
+ *   state_pool : fp32 [n_slots,H,N,N], value-major as above        state_slot : int32 [n_seq] on the device, or NULL: slot = sequence
+ *                                                                  index (n_slots >= n_seq then, else WKV6_EINVAL)
+ * Sequence s reads its initial state from slot state_slot[s] and leaves its final state there, in place.  A slot outside [0, n_slots)
+ * means "no state": the sequence starts from zero and its final state is not stored (the slot is tested on the device before any
+ * address is formed: a garbage slot touches no memory).  A sequence of (clamped) length 0 neither reads nor writes its slot.  Two
+ * sequences of non-zero length that name one slot in the same call are out of contract: what that slot holds afterwards is unspecified,
+ * the call stays memory-safe.  Slots that no sequence names are not touched.
+ * cu_seqlens follows the wkv6_*_varlen_ex rules above: device-only and clamped on the device, max_seqlen cuts a sequence, empty
+ * sequences are legal, rows of y outside every sequence are written as +0 and the inputs there are never read, y must be 16-byte
+ * aligned (WKV6_EINVAL).
+ * Contract: for every sequence, y and the final state are bit-identical to rwkv6_cuda_forward_<io>(B = 1, T = len, ...) on that sequence
+ * alone with its slot's state (for calls that one takes in one scan level, i.e. below 2048 tokens).
+ * Routing, as that call does it per sequence: bf16 sequences of 32 tokens and more run on the chunked MFMA kernel, shorter ones and every
+ * fp16 / fp32 sequence on the exact scan.  bf16 with max_seqlen < 32 (a decode step) is one scan launch; otherwise the chunked launch
+ * serves the lengths [32, inf) and a scan launch the lengths [0, 32) of the same prepared batch -- the host never reads cu_seqlens.
+ * flags: WKV6_ALGO_SCAN forces the scan for every length; any other bit returns WKV6_EINVAL.
+ * Limits: (max_seqlen + 64) * C < 2^30 on the chunked route, < 2^31 on the scan route, else WKV6_EUNSUPPORTED.  Argument errors return
+ * before anything is launched: WKV6_EINVAL (shapes, n_slots < 1, flags, alignment), WKV6_ENULL (state_pool, cu_seqlens or a tensor).
+ * workspace: rwkv6_varlen_workspace_bytes(n_seq) bytes, the four prepared int32 [n_seq] arrays (no checkpoint is ever kept); NULL: a
+ * stream-ordered allocation of the call (callers that replay graphs pass one); a non-NULL workspace shorter than that: WKV6_EWORKSPACE.
+ * Out of scope, not half-supported: a raw-w decay kind, the GroupNorm epilogue, reversal maps, two workgroups per head, the two-level
+ * scan over T, a backward, the C++ torch shim. */
+size_t rwkv6_varlen_workspace_bytes(int n_seq);
+int rwkv6_forward_varlen_bf16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                              int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                              void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+int rwkv6_forward_varlen_fp16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                              int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                              void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+int rwkv6_forward_varlen_fp32(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                              int n_slots, float* state_pool, const float* r, const float* k, const float* v, const float* w,
+                              const float* u, float* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+
 /* ---- wkv5 (RWKV-5: the decay is a parameter, constant over batch and time): replaces cuda_forward / cuda_backward of
  * cuda/wkv5_op.cpp:5-6 (cuda/wkv5_cuda.cu:190-202).  w, u : [H,N];  gw, gu : [B,C] per-batch partials (the caller sums them over
  * the batch, src/model.py:283-284).  `eew` is the fp32 decay exp(-exp(w_raw)) and `ew` the fp32 -exp(w_raw) that src/model.py:260-261

@@ -35,6 +35,10 @@ SIGNATURES = {
     "rwkv6_cuda_forward_bf16": (_I, [_I] * 4 + [_VP] * 8),
     "rwkv6_cuda_forward_fp16": (_I, [_I] * 4 + [_VP] * 8),
     "rwkv6_cuda_forward_fp32": (_I, [_I] * 4 + [_VP] * 8),
+    "rwkv6_varlen_workspace_bytes": (_SZ, [_I]),
+    "rwkv6_forward_varlen_bf16": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP]),
+    "rwkv6_forward_varlen_fp16": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP]),
+    "rwkv6_forward_varlen_fp32": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP]),
     "wkv6_backward_workspace_bytes": (_SZ, [_I] * 4),
     "wkv6bi_workspace_bytes": (_SZ, [_I] * 4),
     "wkv6bi_kept_bytes": (_SZ, [_I] * 4),

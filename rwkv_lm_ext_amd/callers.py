@@ -66,13 +66,18 @@ def _default_wkv_varlen(total_T, C, H, r, k, v, w, u, cu_seqlens, max_seqlen):
     return y.to(r.dtype)
 
 
-def _packed_prev(x, cu_seqlens):
-    """x delayed by one token on a packed batch [1,total_T,C]: zero in front of every sequence's first token (eager path; the index
-    arithmetic stays on the device of x)."""
+def _packed_prev(x, cu_seqlens, shifted0=None):
+    """x delayed by one token on a packed batch [1,total_T,C]: zero in front of every sequence's first token, or shifted0[s] ([n_seq,C],
+    the token a serving loop carried over) in front of non-empty sequence s (eager path; the index arithmetic stays on the device of x)."""
     T = x.shape[1]
     opens = torch.zeros(T + 1, dtype=torch.bool, device=x.device)
     opens[cu_seqlens[:-1].long().clamp(0, T)] = True
-    return F.pad(x, (0, 0, 1, -1)).masked_fill(opens[:T].view(1, T, 1), 0)
+    prev = F.pad(x, (0, 0, 1, -1)).masked_fill(opens[:T].view(1, T, 1), 0)
+    if shifted0 is None:
+        return prev
+    cu = cu_seqlens.long().clamp(0, T)
+    first = torch.where(cu[1:] > cu[:-1], cu[:-1], torch.full_like(cu[:-1], T))    # an empty sequence has no first token: row T is a dummy
+    return F.pad(prev, (0, 0, 0, 1)).index_copy(1, first, shifted0.to(x.dtype).unsqueeze(0))[:, :T]
 
 
 class Tmix_x060(nn.Module):
@@ -130,7 +135,7 @@ class Tmix_x060(nn.Module):
                     and C % 64 == 0 and C <= 4096)
         return self.fused
 
-    def jit_func(self, x, shifted=None, rev_n=None, cu_seqlens=None):
+    def jit_func(self, x, shifted=None, rev_n=None, cu_seqlens=None, shifted0=None):
         """Inputs of the WKV operator from the block input (src/model.py:435-459): every projection reads its own
         data-dependent blend of x_t and x_{t-1},  x + (x_{t-1} - x) * (maa_s + m_s),  where the five corrections m_s come
         from one shared low-rank pair (tanh(blend_x @ W1) -> per-stream W2).  Then r, k, v = Linear(blend), g = silu(Linear),
@@ -141,13 +146,19 @@ class Tmix_x060(nn.Module):
         `rev_n` (fused path only, int32 [B]): the token shift runs over the stream whose first rev_n[b] tokens are reversed
         while every tensor stays in the original token order (row n2).
         `cu_seqlens` (int32 [n_seq + 1]): x is a packed variable-length batch [1,total_T,C]; the shift does not cross a sequence
-        boundary (zero in front of every sequence); rev_n is then int32 [n_seq]."""
+        boundary (zero in front of every sequence); rev_n is then int32 [n_seq].
+        `shifted0` (packed batches only, [n_seq,C]): the token in front of every sequence -- what a serving loop carried over from the
+        sequence's previous call -- instead of zero."""
         B, T, C = x.size()
         if cu_seqlens is not None:
-            assert B == 1 and shifted is None, "a packed batch is [1,total_T,C], zero-padded per sequence"
+            assert B == 1 and shifted is None, "a packed batch is [1,total_T,C]; the carried tokens go in as shifted0 [n_seq,C]"
+        else:
+            assert shifted0 is None, "shifted0 belongs to a packed batch (cu_seqlens); a dense batch passes `shifted`"
         if self._use_fused(x):
             from . import mix_op
             first = None if shifted is None else shifted[:, 0].contiguous()
+            if shifted0 is not None:
+                first = shifted0.contiguous()
             lead = mix_op.ddlerp(x, self.time_maa_x.view(1, C), None, first, rev_n, cu_seqlens=cu_seqlens)[0]
             low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
             corr = torch.bmm(low, self.time_maa_w2).view(5, B, T, C)
@@ -155,7 +166,7 @@ class Tmix_x060(nn.Module):
         else:
             assert rev_n is None, "the reversed-stream shift exists in the fused (HIP) path only"
             if cu_seqlens is not None:
-                prev = _packed_prev(x, cu_seqlens)
+                prev = _packed_prev(x, cu_seqlens, shifted0)
             else:
                 prev = F.pad(x, (0, 0, 1, -1)) if shifted is None else shifted
             delta = prev - x

@@ -1168,7 +1168,7 @@ static int rwkv6_infer(int B, int T, int C, int H, float* state, const void* r, 
     a.y = y;
     // prefill-sized calls in bf16 go through the chunked MFMA kernel (log of the given decay, fp32 state I/O); decode
     // (a few tokens), fp32 I/O and fp16 I/O (r, k, v are not exact in bf16) use the exact scan
-    if (io == IO_BF16 && T >= 32) return to_rc(chunk_forward(a, (hipStream_t)stream));
+    if (io == IO_BF16 && T >= INFER_CHUNK_MIN_T) return to_rc(chunk_forward(a, (hipStream_t)stream));
     return to_rc(launch_scan_fwd(a, io, (hipStream_t)stream));
 }
 int rwkv6_cuda_forward_bf16(int B, int T, int C, int H, float* state, const void* r, const void* k, const void* v,
@@ -1185,6 +1185,69 @@ int rwkv6_cuda_forward_fp32(int B, int T, int C, int H, float* state, const floa
                             const float* w, const float* u, float* y, void* stream)
 {
     return rwkv6_infer(B, T, C, H, state, r, k, v, w, u, y, IO_F32, stream);
+}
+
+// ---- packed stateful inference: the sequences of one [total_T, C] buffer, each with its state in a slot of the caller's fp32 pool.
+// One preparation launch (lengths, offsets, dispatch order, gap rows of y), then the kernels rwkv6_infer would pick per sequence: bf16
+// sequences of INFER_CHUNK_MIN_T tokens and more on the chunked kernel, everything else on the exact scan -- two launches over the same
+// prepared arrays, each serving its side of the length window (ScanArgs::len_lo / len_hi), so that the host never reads cu_seqlens.
+size_t rwkv6_varlen_workspace_bytes(int n_seq) { return n_seq < 1 ? 0 : varlen_int_bytes(n_seq); }
+
+static int rwkv6_infer_varlen(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                              int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                              void* y, void* workspace, size_t workspace_bytes, unsigned flags, int io, void* stream)
+{
+    if (flags & ~(unsigned)WKV6_ALGO_SCAN) return WKV6_EINVAL;
+    const bool chunked = io == IO_BF16 && !(flags & WKV6_ALGO_SCAN) && max_seqlen >= INFER_CHUNK_MIN_T;
+    // (varlen_check's row limits: 2^30 on the chunked route with the fp32 decay, 2^31 on the scan route)
+    if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, chunked ? 0u : (unsigned)WKV6_ALGO_SCAN, WKV6_ALGO_SCAN)) return rc;
+    if (n_slots < 1 || (!state_slot && n_slots < n_seq)) return WKV6_EINVAL;
+    if (!cu_seqlens || !state_pool || !r || !k || !v || !w || !u || !y) return WKV6_ENULL;
+    hipStream_t st = (hipStream_t)stream;
+    StreamScratch scratch;
+    if (workspace) {
+        if (workspace_bytes < rwkv6_varlen_workspace_bytes(n_seq)) return WKV6_EWORKSPACE;
+    } else {
+        workspace = scratch.get(varlen_int_bytes(n_seq), st);
+        if (!workspace) return WKV6_EWORKSPACE;
+    }
+    if (!varlen_aligned({y})) return WKV6_EINVAL;
+    ScanArgs a = base_args(n_seq, max_seqlen, C, H, r, k, v, w, u, 0);
+    float* area = nullptr;
+    varlen_carve(a, workspace, total_T, n_seq, &area);      // (no checkpoint is kept: the area behind the int arrays is never addressed)
+    a.wkind = 2;                                            // w is the decay itself
+    a.state_f32 = 1;
+    a.s0 = state_pool; a.s_out = state_pool;
+    a.s0_bstride = (long)H * HEAD * HEAD;
+    a.state_slot = state_slot; a.n_slots = n_slots;
+    a.y = y;
+    if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, true, io == IO_F32 ? (unsigned)WKV6_IO_F32 : 0u, {y}, st)) return to_rc(e);
+    if (!chunked) return to_rc(launch_scan_fwd_slots(a, io, st));          // a decode step, fp16 / fp32 I/O, WKV6_ALGO_SCAN: no window
+    a.len_lo = INFER_CHUNK_MIN_T; a.len_hi = 0x7fffffff;
+    if (hipError_t e = launch_chunk_fwd_slots(a, st)) return to_rc(e);
+    a.len_lo = 0; a.len_hi = INFER_CHUNK_MIN_T;
+    return to_rc(launch_scan_fwd_slots(a, io, st));
+}
+int rwkv6_forward_varlen_bf16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                              int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                              void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream)
+{
+    return rwkv6_infer_varlen(total_T, n_seq, max_seqlen, C, H, cu_seqlens, state_slot, n_slots, state_pool, r, k, v, w, u, y, workspace,
+                              workspace_bytes, flags, IO_BF16, stream);
+}
+int rwkv6_forward_varlen_fp16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                              int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                              void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream)
+{
+    return rwkv6_infer_varlen(total_T, n_seq, max_seqlen, C, H, cu_seqlens, state_slot, n_slots, state_pool, r, k, v, w, u, y, workspace,
+                              workspace_bytes, flags, IO_F16, stream);
+}
+int rwkv6_forward_varlen_fp32(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                              int n_slots, float* state_pool, const float* r, const float* k, const float* v, const float* w,
+                              const float* u, float* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream)
+{
+    return rwkv6_infer_varlen(total_T, n_seq, max_seqlen, C, H, cu_seqlens, state_slot, n_slots, state_pool, r, k, v, w, u, y, workspace,
+                              workspace_bytes, flags, IO_F32, stream);
 }
 
 static int selftest_problem(int B, void* stream)

@@ -115,7 +115,10 @@ struct FwdChain {
 __device__ __forceinline__ bool fwd_hw_wave_produces(int hw) { return hw >= 4; }
 // VARLEN (packed batches, chunk_fwd_varlen_kernel): row b is sequence b of a [total_T, C] tensor -- its tokens start at a.tok_off[b], its
 // checkpoints at slot a.ck_off[b] of its head's a.ck_stride slots; a.T is the longest sequence allowed, a.lens / a.order are always set
-template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false, bool VARLEN = false>
+// SLOTS (packed stateful inference, chunk_fwd_varlen_slots_kernel; VARLEN only): the fp32 state of sequence b lives in slot a.state_slot[b]
+// of the pool a.s0 == a.s_out and is updated in place -- the lanes that load an element in the consumer prologue store it in the epilogue --
+// and a.len_lo / a.len_hi select the sequences this launch serves (wkv6_scan.h)
+template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false, bool VARLEN = false, bool SLOTS = false>
 __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned slot, const unsigned sslot, FwdRaw& raw, const FwdChain& ch = FwdChain{})
 {
     [[maybe_unused]] const bool nxvalid = ch.nx_valid, chained_in = ch.chained_in, nx_use_u = ch.nx_use_u;
@@ -152,6 +155,12 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
     int ntok = a.T;
     if constexpr (CHAIN) ntok = ntok_known;
     else if (a.lens) ntok = min(max(a.lens[b], 0), a.T);
+    [[maybe_unused]] int sslot_ = -1;                            // SLOTS: this sequence's state slot, -1: none (zero in, nothing out)
+    if constexpr (SLOTS) {
+        static_assert(VARLEN && !CHAIN && !CLK, "state slots: plain packed rows only");
+        if (outside_len_window(a, ntok)) return;                  // (workgroup-uniform; in front of every barrier and every access)
+        sslot_ = state_slot_of(a, b, ntok);
+    }
     const int ngrp = (ntok + GRP - 1) / GRP;
     const TokAddr<AFF> tok(a, b, ntok);                           // token addressing (wkv6_scan.h): AFF = no per-tensor reversal map
     const int C_ = a.C;
@@ -365,8 +374,8 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             float t4[4] = {0.f, 0.f, 0.f, 0.f};
-            if (a.s0) {
-                const long so_ = (long)b * a.s0_bstride + ((long)h * HEAD + 16 * wv + x) * HEAD + tile_ch(it) + 8 * g;
+            if (SLOTS ? sslot_ >= 0 : a.s0 != nullptr) {
+                const long so_ = (long)(SLOTS ? sslot_ : b) * a.s0_bstride + ((long)h * HEAD + 16 * wv + x) * HEAD + tile_ch(it) + 8 * g;
                 if (a.state_f32) io4<float>::load(reinterpret_cast<const float*>(a.s0) + so_, t4);
                 else io4<bf16_t>::load(reinterpret_cast<const bf16_t*>(a.s0) + so_, t4);
             }
@@ -651,8 +660,8 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
             if constexpr (GN) gn_finish(grp);
         }
         if (staged && ngrp > 0) flush_y(ngrp - 1);                // (the loop's last barrier closed the last group)
-        if (a.s_out) {
-            const long so_ = ((long)b * a.H + h) * HEAD * HEAD + (long)(16 * wv + x) * HEAD + 8 * g;
+        if (SLOTS ? sslot_ >= 0 : a.s_out != nullptr) {
+            const long so_ = ((long)(SLOTS ? sslot_ : b) * a.H + h) * HEAD * HEAD + (long)(16 * wv + x) * HEAD + 8 * g;
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const float t4[4] = {St[it][0], St[it][1], St[it][2], St[it][3]};
@@ -707,6 +716,14 @@ __global__ __launch_bounds__(512) void chunk_fwd_varlen_kernel(const ScanArgs a)
 {
     FwdRaw raw;
     chunk_fwd_body<W_RAW, STATE_ONLY, false, false, true, false, false, true>(a, blockIdx.x, 0u, raw);
+}
+
+// Packed stateful inference (rwkv6_forward_varlen_bf16): the fp32 decay itself as input (a.wkind == 2), the state in a slot of a pool.  A kernel
+// of its own once more: the packed training instantiations above keep their instruction streams.
+__global__ __launch_bounds__(512) void chunk_fwd_varlen_slots_kernel(const ScanArgs a)
+{
+    FwdRaw raw;
+    chunk_fwd_body<false, false, false, false, true, false, false, true, true>(a, blockIdx.x, 0u, raw);
 }
 
 // Packed rows under a per-tensor reversal map (a.rev_n, indexed by the sequence): general token addressing from the sequence's first token --
@@ -925,6 +942,24 @@ hipError_t launch_chunk_fwd_varlen(const ScanArgs& a_, bool state_only, hipStrea
     const bool raw = a.wkind == 1;
     if (state_only) return raw ? launch_fwd_varlen_inst<true, true>(a, st) : launch_fwd_varlen_inst<false, true>(a, st);
     return raw ? launch_fwd_varlen_inst<true, false>(a, st) : launch_fwd_varlen_inst<false, false>(a, st);
+}
+
+// Packed stateful inference: no checkpoints, no reversal map; the state pool a.s0 == a.s_out (fp32, a.n_slots slots) is addressed through
+// a.state_slot; sequences outside [a.len_lo, a.len_hi) are left to another launch
+hipError_t launch_chunk_fwd_slots(const ScanArgs& a_, hipStream_t st)
+{
+    if (!offsets_fit(a_)) return hipErrorInvalidValue;
+    if (!a_.tok_off || !a_.ck_off || !a_.lens || !a_.order || !slots_ok(a_) || a_.wkind != 2) return hipErrorInvalidValue;
+    if (!varlen_fwd_plain(a_) || a_.rev_n || a_.ckpt) return hipErrorNotSupported;
+    ScanArgs a = a_;
+    a.split = 0;
+    a.clk = nullptr; a.clk_slots = 0;
+    attach_debug_buffer(a);
+    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
+    static LdsAttrOnce attr;
+    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_slots_kernel), lds)) return e;
+    hipLaunchKernelGGL(chunk_fwd_varlen_slots_kernel, dim3(a.B * a.H), dim3(512), lds, st, a);
+    return hipGetLastError();
 }
 
 // Both problems of a bidirectional composition on packed rows in one launch: the same sequences (one set of prepared int arrays), each

@@ -101,7 +101,31 @@ struct ScanArgs {
     const int* tok_off;               // [B] first token of the sequence
     const int* ck_off;                // [B] first checkpoint slot of the sequence within its head: exclusive prefix sum of ceil(len / CKPT_TOK)
     long ck_stride;                   // checkpoint slots per head: a.ckpt is [H][ck_stride][4096]
+    // Packed stateful inference (rwkv6_forward_varlen_*: the SLOTS instantiations of the packed forward kernels read these, nobody else
+    // does; at the end again).  The state of sequence b is slot state_slot[b] (null: b) of a caller-owned pool [n_slots,H,N,N] of fp32 states,
+    // s0 == s_out == the pool: the lanes that load an element are the lanes that store it, so the slot is updated in place.  A slot
+    // outside [0, n_slots) is "no state": zero in, nothing out; the array is written on the device and never read by the host.
+    const int* state_slot;
+    int n_slots;
+    int len_lo, len_hi;               // len_hi != 0: a workgroup whose sequence has a (clamped) length outside [len_lo, len_hi) returns
+                                      // before it touches anything -- two launches over one prepared batch share it by length
 };
+
+// Shortest sequence the stateful inference calls (rwkv6_cuda_forward_bf16, rwkv6_forward_varlen_bf16) hand to the chunked kernel; shorter
+// ones (decode steps) take the exact scan
+constexpr int INFER_CHUNK_MIN_T = 32;
+
+// State slot of sequence b of a packed stateful call, or -1: no state.  Decided before any address is formed: a garbage slot touches no memory.
+__device__ __forceinline__ int state_slot_of(const ScanArgs& a, int b, int ntok)
+{
+    const int slot = a.state_slot ? a.state_slot[b] : b;
+    return (ntok > 0 && slot >= 0 && slot < a.n_slots) ? slot : -1;
+}
+// (decided once per workgroup, in front of everything else)
+__device__ __forceinline__ bool outside_len_window(const ScanArgs& a, int ntok)
+{
+    return a.len_hi != 0 && (ntok < a.len_lo || ntok >= a.len_hi);
+}
 
 enum { REV_R = 1, REV_K = 2, REV_V = 4, REV_W = 8, REV_Y = 16, REV_ALL = 31 };   // REV_Y: y in the forward, gy in the backward;
                                                                                 // every gradient follows its tensor's bit
@@ -179,6 +203,14 @@ hipError_t launch_chunk_fwd_varlen_pair(const ScanArgs& a0, const ScanArgs& a1, 
 hipError_t launch_chunk_bwd_varlen_pair(const ScanArgs& a0, const ScanArgs& a1, hipStream_t st);   // both with ckpt_valid
 hipError_t launch_scan_fwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st);
 hipError_t launch_scan_bwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st);
+// packed stateful inference (ScanArgs: state_slot, n_slots, len_lo, len_hi; s0 == s_out == the fp32 pool, wkind == 2): the scan kernel in
+// any I/O type, the chunked kernel in bf16.  Both return before touching anything for a sequence outside the length window.
+inline bool slots_ok(const ScanArgs& a)
+{
+    return a.s0 && a.s0 == a.s_out && a.state_f32 && a.n_slots >= 1 && a.s0_bstride == (long)a.H * HEAD * HEAD && a.len_lo >= 0 && a.len_hi >= 0;
+}
+hipError_t launch_scan_fwd_slots(const ScanArgs& a, int io, hipStream_t st);
+hipError_t launch_chunk_fwd_slots(const ScanArgs& a, hipStream_t st);
 hipError_t launch_chunk_state_pass(const ScanArgs& a, hipStream_t st);   // state recurrence only (s_out, ckpt, dsum)
 // In-run clock probe (wkv6_set_clock_ring, wkv6_api.hip): where launch number n of kind (0: chunked forward, 1: chunked backward) stamps,
 // or null; takes the launch's place in the ring (host side, one atomic increment per launch)

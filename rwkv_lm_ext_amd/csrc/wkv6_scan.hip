@@ -104,7 +104,10 @@ __device__ __forceinline__ void load_ew(const ScanArgs& a, long idx, bool valid,
 // (cuda/wkv6_cuda.cu:44-57).  Wave `wv` owns value columns [wv*JPW, (wv+1)*JPW); lane (jb = lane>>4,
 // ib = lane&15) owns S[4ib..4ib+3][j0..j0+JR-1].
 // =====================================================================================================
-template <typename T, int NW>
+// SLOTS (packed stateful inference, launch_scan_fwd_slots): the fp32 state of sequence b lives in slot a.state_slot[b] of the pool
+// a.s0 == a.s_out and is updated in place; a.len_lo / a.len_hi select the sequences this launch serves (wkv6_scan.h).  Instantiations of
+// their own: the dense and the packed training kernels keep their instruction streams.
+template <typename T, int NW, bool SLOTS = false>
 __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
 {
     using G = Geo<NW>;
@@ -123,6 +126,11 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
     T* const gy_ = reinterpret_cast<T*>(a.y);
     int ntok = a.T;
     if (a.lens) ntok = min(max(a.lens[b], 0), a.T);
+    [[maybe_unused]] int slot = -1;
+    if constexpr (SLOTS) {
+        if (outside_len_window(a, ntok)) return;        // (workgroup-uniform, in front of the first barrier and the first access)
+        slot = state_slot_of(a, b, ntok);
+    }
     const RevMap tokmap = make_revmap(a, b, ntok);      // token each tensor holds at scan position p (wkv6_scan.h)
     const long base = (a.tok_off ? (long)a.tok_off[b] : (long)b * a.T) * a.C + (long)h * HEAD;
 
@@ -140,8 +148,8 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
 #pragma unroll
     for (int jj = 0; jj < JR; ++jj) {
         float t4[4] = {0.f, 0.f, 0.f, 0.f};
-        if (a.s0) {
-            const long so_ = (long)b * a.s0_bstride + ((long)h * HEAD + j0 + jj) * HEAD + i0;
+        if (SLOTS ? slot >= 0 : a.s0 != nullptr) {
+            const long so_ = (long)(SLOTS ? slot : b) * a.s0_bstride + ((long)h * HEAD + j0 + jj) * HEAD + i0;
             if (a.state_f32) io4<float>::load(reinterpret_cast<const float*>(a.s0) + so_, t4);
             else io4<T>::load(reinterpret_cast<const T*>(a.s0) + so_, t4);
         }
@@ -244,8 +252,8 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
             }
         }
     }
-    if (a.s_out) {
-        const long so_ = ((long)b * a.H + h) * HEAD * HEAD;
+    if (SLOTS ? slot >= 0 : a.s_out != nullptr) {
+        const long so_ = ((long)(SLOTS ? slot : b) * a.H + h) * HEAD * HEAD;
 #pragma unroll
         for (int jj = 0; jj < JR; ++jj) {
             const float t4[4] = {S[0][jj], S[1][jj], S[2][jj], S[3][jj]};
@@ -783,6 +791,17 @@ hipError_t launch_scan_bwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st
 {
     if (!varlen_scan_ok(a) || !a.aux) return hipErrorInvalidValue;
     return launch_scan_bwd(a, io_f32, st);
+}
+// Packed stateful inference: the state pool a.s0 == a.s_out (fp32, a.n_slots slots) is addressed through a.state_slot and updated in place
+hipError_t launch_scan_fwd_slots(const ScanArgs& a, int io, hipStream_t st)
+{
+    if (!varlen_scan_ok(a) || !slots_ok(a) || a.reverse || a.rev_n) return hipErrorInvalidValue;
+    constexpr size_t lds = (2 * 4 * TB * ROW + 64 + 2 * TB * ROW) * sizeof(float);
+    const dim3 grid(a.B * a.H), block(NWAVES * 64);
+    if (io == IO_F32) hipLaunchKernelGGL((scan_fwd_kernel<float, NWAVES, true>), grid, block, lds, st, a);
+    else if (io == IO_F16) hipLaunchKernelGGL((scan_fwd_kernel<f16_t, NWAVES, true>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((scan_fwd_kernel<bf16_t, NWAVES, true>), grid, block, lds, st, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_selftest(int* result, hipStream_t st)

@@ -92,3 +92,61 @@ def cmix_forward_infctx(cm, x, last_state):
     xx = torch.cat((last_state.shift_state.unsqueeze(1), x[:, :-1]), dim=1) - x
     k = torch.relu(cm.key(x + xx * cm.time_maa_k)) ** 2
     return torch.sigmoid(cm.receptance(x + xx * cm.time_maa_r)) * cm.value(k), ChannelMixState(x[:, -1])
+
+
+# ---- a serving loop's packed batch: sequences of any lengths back to back in x [1,total_T,C], the carried state of sequence s in slot
+# slots[s] (int32 [n_seq] on the device of x) of caller-owned pools -- shift_pool [n_slots,C] (the last token of the sequence's previous
+# call, one pool per sub-layer) and wkv_pool fp32 [n_slots,H,N,N].  A slot outside the pool means no state: zero in, nothing kept.
+# cu_seqlens and slots are never read on the host.
+def _carried_tokens(shift_pool, slots):
+    """[n_seq,C]: shift_pool[slots[s]], zero where the slot lies outside the pool."""
+    n = shift_pool.shape[0]
+    s = slots.long()
+    ok = (s >= 0) & (s < n)
+    return shift_pool[s.clamp(0, n - 1)].masked_fill(~ok.unsqueeze(1), 0).contiguous()
+
+
+def _keep_last_tokens(shift_pool, slots, x, cu_seqlens, max_seqlen=None):
+    """shift_pool[slots[s]] = the last token of sequence s; empty sequences and slots outside the pool leave the pool alone (their rows go
+    to a dummy slot behind it)."""
+    n, T = shift_pool.shape[0], x.shape[0]
+    cu, s = cu_seqlens.long().clamp(0, T), slots.long()
+    length = cu[1:] - cu[:-1]
+    if max_seqlen is not None:
+        length = length.clamp(max=int(max_seqlen))
+    alive = (length > 0) & (s >= 0) & (s < n)
+    rows = x[(cu[:-1] + length - 1).clamp(0, T - 1)].to(shift_pool.dtype)
+    dest = torch.where(alive, s, torch.full_like(s, n))
+    shift_pool.copy_(torch.cat((shift_pool, shift_pool.new_zeros(1, shift_pool.shape[1]))).index_copy_(0, dest, rows)[:n])
+
+
+def tmix_forward_packed(tm, x, cu_seqlens, max_seqlen, shift_pool, wkv_pool, slots):
+    """tmix_forward_infctx for every sequence of a packed batch x [1,total_T,C] in one pass (a callers.Tmix_x060 `tm`): the token shift
+    starts from shift_pool[slots[s]], the operator (wkv.RUN_RWKV_6_VARLEN) from wkv_pool[slots[s]]; both pools are updated in place."""
+    from .wkv import RUN_RWKV_6_VARLEN
+    B, T, C = x.size()
+    assert B == 1, "a packed batch is [1,total_T,C]"
+    r, k, v, g, w = tm.jit_func(x, cu_seqlens=cu_seqlens, shifted0=_carried_tokens(shift_pool, slots).to(x.dtype))
+    u = tm.time_faaaa.to(r.dtype).contiguous()
+    y, _ = RUN_RWKV_6_VARLEN(T, C, tm.n_head, wkv_pool, slots, *(t.contiguous() for t in (r, k, v, w.to(r.dtype))), u, cu_seqlens, max_seqlen)
+    out = tm.jit_func_2(y, g)
+    _keep_last_tokens(shift_pool, slots, x[0], cu_seqlens, max_seqlen)
+    return out
+
+
+def cmix_forward_packed(cm, x, cu_seqlens, shift_pool, slots):
+    """cmix_forward_infctx for every sequence of a packed batch x [1,total_T,C] (a callers.CMix_x060 `cm`); shift_pool is this sub-layer's."""
+    from .callers import _packed_prev
+    B, T, C = x.size()
+    assert B == 1, "a packed batch is [1,total_T,C]"
+    carried = _carried_tokens(shift_pool, slots).to(x.dtype)
+    if cm._use_fused(x):
+        from . import mix_op
+        xk, xr = mix_op.ddlerp(x, torch.cat([cm.time_maa_k, cm.time_maa_r], 0).view(2, -1), shifted0=carried, cu_seqlens=cu_seqlens)
+        out = mix_op.sigmoid_mul(cm.receptance(xr), cm.value(mix_op.sqrelu(cm.key(xk))))
+    else:
+        xx = _packed_prev(x, cu_seqlens, carried) - x
+        k = torch.relu(cm.key(x + xx * cm.time_maa_k)) ** 2
+        out = torch.sigmoid(cm.receptance(x + xx * cm.time_maa_r)) * cm.value(k)
+    _keep_last_tokens(shift_pool, slots, x[0], cu_seqlens)
+    return out

@@ -475,3 +475,32 @@ class RWKV_6(torch.autograd.Function):
 
 def RUN_RWKV_6(B, T, C, H, state, r, k, v, w, u):
     return RWKV_6.apply(B, T, C, H, state, r, k, v, w, u)
+
+
+class RWKV_6_VARLEN(torch.autograd.Function):
+    """RWKV_6 on a packed batch for a serving loop: the sequences lie back to back in [total_T,C] tensors (sequence s = rows
+    cu_seqlens[s] .. cu_seqlens[s+1]-1: prompts of any lengths, prefill next to one-token decode steps) and sequence s keeps its fp32
+    state in slot state_slot[s] (int32 [n_seq] on the device; None: slot s) of the caller's pool state_pool [n_slots,H,N,N], which is
+    updated in place and returned.  A slot outside the pool means no state: zero in, nothing out.  w is the raw decay parameter."""
+
+    @staticmethod
+    def forward(ctx, total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen):
+        with torch.no_grad():
+            assert HEAD_SIZE == C // H
+            assert state_pool.dtype == torch.float32
+            for t in (r, k, v, w, u):
+                assert t.is_contiguous()
+            shape = r.shape
+            r, k, v, w = (t.view(total_T, C) for t in (r, k, v, w))
+            eew = torch.exp(-torch.exp(w.float())).contiguous()
+            y = torch.empty((total_T, C), device=w.device, dtype=r.dtype)
+            fn = {torch.bfloat16: wkv6_op.rwkv6.forward_varlen_bf16, torch.float32: wkv6_op.rwkv6.forward_varlen_fp32,
+                  torch.float16: wkv6_op.rwkv6.forward_varlen_fp16}.get(r.dtype)
+            if fn is None:
+                raise RuntimeError(f"unsupported dtype {r.dtype}")
+            fn(total_T, C, H, state_pool, state_slot, r, k, v, eew, u, y, cu_seqlens, max_seqlen)
+            return y.view(shape), state_pool
+
+
+def RUN_RWKV_6_VARLEN(total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen):
+    return RWKV_6_VARLEN.apply(total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen)

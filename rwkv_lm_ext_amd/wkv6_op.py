@@ -193,6 +193,60 @@ class _Rwkv6:
         state in fp32 and rounds y to fp16 once (cuda/rwkv6.cu:8-71)."""
         _Rwkv6._call(B, T, C, H, state, r, k, v, w, u, y, torch.float16)
 
+    # ---- packed batches with a state-slot pool (include/wkv6_amd.h: rwkv6_forward_varlen_*) ----
+    @staticmethod
+    def _call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, io):
+        """Every sequence of the packed [total_T,C] tensors (rows cu_seqlens[s] .. cu_seqlens[s+1]-1) from the state in slot state_slot[s]
+        (None: slot s) of state_pool fp32 [n_slots,H,N,N], which is updated in place; y is written, rows outside every sequence as +0.
+        w is the fp32 decay.  algo="scan" forces the exact scan kernel; ws: a new_rwkv6_varlen_workspace() buffer (graph capture)."""
+        tc = (total_T, C)
+        named = dict(state_pool=(state_pool, None, torch.float32), r=(r, tc, io), k=(k, tc, io), v=(v, tc, io),
+                     w=(w, tc, torch.float32), u=(u, (H, HEAD_SIZE), io), y=(y, tc, io))
+        for name, (t, _, dt) in named.items():      # (types first: what is wrong with a tensor is reported whatever device it is on)
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a tensor")
+            if t.dtype != dt:
+                raise RuntimeError(f"{name} must be {dt}, got {t.dtype}")
+        if algo not in (None, "scan"):
+            raise RuntimeError(f"unknown algo {algo!r}")
+        if int(total_T) < 1 or int(max_seqlen) < 1:
+            raise RuntimeError("total_T and max_seqlen must be >= 1")
+        per_slot = H * HEAD_SIZE * HEAD_SIZE
+        if state_pool.dim() != 4 or tuple(state_pool.shape[1:]) != (H, HEAD_SIZE, HEAD_SIZE) or state_pool.shape[0] < 1:
+            raise RuntimeError(f"state_pool has shape {tuple(state_pool.shape)}, expected (n_slots, {H}, {HEAD_SIZE}, {HEAD_SIZE})")
+        n_slots = state_pool.numel() // per_slot
+        n_seq = _check_cu_seqlens(cu_seqlens, r.device)
+        if state_slot is None:
+            if n_slots < n_seq:
+                raise RuntimeError(f"state_slot=None names slot s for sequence s: the pool has {n_slots} slots for {n_seq} sequences")
+        elif not (isinstance(state_slot, torch.Tensor) and state_slot.dtype == torch.int32 and state_slot.is_contiguous()
+                  and tuple(state_slot.shape) == (n_seq,) and state_slot.device == r.device):
+            raise RuntimeError("state_slot must be a contiguous int32 [n_seq] tensor on the device of r, or None")
+        if ws is not None and not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous()
+                                   and ws.device == r.device):
+            raise RuntimeError("ws must be a new_rwkv6_varlen_workspace() buffer on the device of r")
+        dev = _check_tensors(n_seq, total_T, C, H, named, dtype=io)
+        lib = _lib.load()
+        fn = {torch.bfloat16: lib.rwkv6_forward_varlen_bf16, torch.float16: lib.rwkv6_forward_varlen_fp16,
+              torch.float32: lib.rwkv6_forward_varlen_fp32}[io]
+        with torch.cuda.device(dev):
+            rc = fn(int(total_T), n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(state_slot), n_slots, _ptr(state_pool), _ptr(r),
+                    _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _ptr(ws), 0 if ws is None else ws.numel(),
+                    _lib.ALGO_SCAN if algo == "scan" else 0, _stream_ptr())
+        _lib.check(rc, "rwkv6 forward_varlen")
+
+    @staticmethod
+    def forward_varlen_bf16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None):
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.bfloat16)
+
+    @staticmethod
+    def forward_varlen_fp16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None):
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.float16)
+
+    @staticmethod
+    def forward_varlen_fp32(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None):
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.float32)
+
 
 class _Wkv5:
     """Stand-in for the module object of `load(name="wkv5", ...)` (src/model.py:238-239): the RWKV-5 operator, whose decay is an
@@ -340,6 +394,14 @@ def new_varlen_workspace(total_T, n_seq, C, H, device):
     n = _lib.load().wkv6_varlen_workspace_bytes(total_T, n_seq, C, H)
     if n == 0:
         raise RuntimeError(f"bad packed shape: total_T {total_T}, n_seq {n_seq}, C {C}, H {H}")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def new_rwkv6_varlen_workspace(n_seq, device):
+    """Workspace of rwkv6.forward_varlen_*: the four prepared int32 [n_seq] arrays (a caller that replays graphs owns it)."""
+    n = _lib.load().rwkv6_varlen_workspace_bytes(n_seq)
+    if n == 0:
+        raise RuntimeError(f"bad n_seq {n_seq}")
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
@@ -917,6 +979,13 @@ def _register():
     vl.impl("forward_varlen", _Wkv6Varlen.forward, "CUDA")
     vl.impl("backward_varlen", _Wkv6Varlen.backward, "CUDA")
     libs.append(vl)
+    # packed stateful inference: state_pool (fp32 [n_slots,H,N,N]) and y are written; state_slot None = slot s for sequence s
+    rv = torch.library.Library("rwkv6", "FRAGMENT")
+    for name in ("forward_varlen_bf16", "forward_varlen_fp16", "forward_varlen_fp32"):
+        rv.define(name + "(int total_T, int C, int H, Tensor(s!) state_pool, Tensor? state_slot, Tensor r, Tensor k, Tensor v, Tensor w, "
+                         "Tensor u, Tensor(a!) y, Tensor cu_seqlens, int max_seqlen) -> ()")
+        rv.impl(name, getattr(_Rwkv6, name), "CUDA")
+    libs.append(rv)
     w5 = torch.library.Library("wkv5", "DEF")           # TORCH_LIBRARY(wkv5, m), cuda/wkv5_op.cpp:19-22
     w5.define("forward(int B, int T, int C, int H, Tensor r, Tensor k, Tensor v, Tensor w, Tensor u, Tensor(a!) y) -> ()")
     w5.define("backward(int B, int T, int C, int H, Tensor r, Tensor k, Tensor v, Tensor w, Tensor ww, Tensor u, Tensor gy, "
