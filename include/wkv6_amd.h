@@ -205,7 +205,8 @@ int wkv6_backward_varlen_ex(long total_T, int n_seq, int max_seqlen, int C, int 
  * workspace: rwkv6_varlen_workspace_bytes(n_seq) bytes, the four prepared int32 [n_seq] arrays (no checkpoint is ever kept); NULL: a
  * stream-ordered allocation of the call (callers that replay graphs pass one); a non-NULL workspace shorter than that: WKV6_EWORKSPACE.
  * Out of scope, not half-supported: a raw-w decay kind, the GroupNorm epilogue, reversal maps, two workgroups per head, the two-level
- * scan over T, a backward, the C++ torch shim. */
+ * scan over T, a backward, the C++ torch shim, snapshots at positions that are no multiple of 64 tokens of the call (the caller aligns
+ * its chunk boundaries). */
 size_t rwkv6_varlen_workspace_bytes(int n_seq);
 int rwkv6_forward_varlen_bf16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
                               int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
@@ -216,6 +217,43 @@ int rwkv6_forward_varlen_fp16(long total_T, int n_seq, int max_seqlen, int C, in
 int rwkv6_forward_varlen_fp32(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
                               int n_slots, float* state_pool, const float* r, const float* k, const float* v, const float* w,
                               const float* u, float* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream);
+
+/* ---- ... with state snapshots and a separate output slot (prefix caching: the state of a prompt every few hundred tokens, and requests that
+ * start from a cached state without overwriting it).  The argument list of rwkv6_forward_varlen_* and then
+ *   state_slot_out : int32 [n_seq] on the device, or NULL      snap_every : 0, or a multiple of 64
+ *   cu_snap : int32 [n_seq + 1], snap_slot : int32 [n_snap], both on the device (may be NULL when snap_every == 0)
+ * Sequence s reads its initial state from slot state_slot[s] and leaves its final state in slot state_slot_out[s] of the same pool; each
+ * of the two is validated on its own, on the device, before any address is formed: a source outside [0, n_slots) starts the sequence from
+ * zero, a destination outside it stores nothing.  state_slot_out == NULL: the destination is the source, the in-place update of the plain
+ * call.
+ * Snapshots: with len_s the clamped length and cu_snap[s], cu_snap[s+1] clamped into [0, n_snap], sequence s keeps
+ * m_s = min(len_s / snap_every, max(cu_snap[s+1] - cu_snap[s], 0)) snapshots; snapshot j < m_s is the state after the sequence's first
+ * (j + 1) * snap_every tokens in this call and goes to slot snap_slot[cu_snap[s] + j] of the pool, in the pool's layout.  A snapshot slot
+ * outside the pool is skipped.  A snapshot at position len_s is stored as well as the final state.  The host reads none of the arrays: the
+ * call stays stream-ordered and graph-capturable.
+ * Contract:
+ *  - Any number of sequences of one call may name the same source slot (requests that fan out from one cached prefix).
+ *  - Two writers of one slot in the same call are out of contract, and so is a slot that one sequence of non-zero length writes and
+ *    another reads; final states and snapshots both count as writes.  What such slots hold afterwards is unspecified; the call stays
+ *    memory-safe.  The one defined overlap is the in-place use: a sequence's destination is its own source.
+ *  - A sequence of (clamped) length 0 reads nothing, writes nothing and takes no snapshot; it does not copy source to destination.
+ *  - For every sequence, y and the destination slot are bit-identical to what rwkv6_forward_varlen_<io> leaves from the same source
+ *    state, and snapshot j is bit-identical to the final state that call leaves when the sequence is cut to (j + 1) * snap_every tokens.
+ * Routing, the length window, the limits and the workspace are those of rwkv6_forward_varlen_<io>.  Refused before anything is launched, in
+ * addition to what that call refuses: snap_every < 0 or no multiple of 64, n_snap < 0 (WKV6_EINVAL); snap_every > 0 with a NULL cu_snap or
+ * snap_slot (WKV6_ENULL). */
+int rwkv6_forward_varlen_snap_bf16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                                   int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                                   void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream, const int* state_slot_out,
+                                   int snap_every, const int* cu_snap, const int* snap_slot, int n_snap);
+int rwkv6_forward_varlen_snap_fp16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                                   int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                                   void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream, const int* state_slot_out,
+                                   int snap_every, const int* cu_snap, const int* snap_slot, int n_snap);
+int rwkv6_forward_varlen_snap_fp32(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                                   int n_slots, float* state_pool, const float* r, const float* k, const float* v, const float* w,
+                                   const float* u, float* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream,
+                                   const int* state_slot_out, int snap_every, const int* cu_snap, const int* snap_slot, int n_snap);
 
 /* ---- wkv5 (RWKV-5: the decay is a parameter, constant over batch and time): replaces cuda_forward / cuda_backward of
  * cuda/wkv5_op.cpp:5-6 (cuda/wkv5_cuda.cu:190-202).  w, u : [H,N];  gw, gu : [B,C] per-batch partials (the caller sums them over

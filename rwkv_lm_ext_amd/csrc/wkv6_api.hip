@@ -1193,11 +1193,25 @@ int rwkv6_cuda_forward_fp32(int B, int T, int C, int H, float* state, const floa
 // prepared arrays, each serving its side of the length window (ScanArgs::len_lo / len_hi), so that the host never reads cu_seqlens.
 size_t rwkv6_varlen_workspace_bytes(int n_seq) { return n_seq < 1 ? 0 : varlen_int_bytes(n_seq); }
 
+// rwkv6_forward_varlen_snap_*: the final state goes to slot state_slot_out[s] (NULL: the source slot), and the state after every snap_every
+// tokens to a slot of its own -- the SNAP instantiations of the two kernels; everything else as the plain call
+struct SnapArgs {
+    const int* state_slot_out;
+    int snap_every;
+    const int *cu_snap, *snap_slot;
+    int n_snap;
+};
+
 static int rwkv6_infer_varlen(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
                               int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
-                              void* y, void* workspace, size_t workspace_bytes, unsigned flags, int io, void* stream)
+                              void* y, void* workspace, size_t workspace_bytes, unsigned flags, int io, void* stream,
+                              const SnapArgs* snap = nullptr)
 {
     if (flags & ~(unsigned)WKV6_ALGO_SCAN) return WKV6_EINVAL;
+    if (snap) {
+        if (snap->snap_every < 0 || snap->snap_every % 64 != 0 || snap->n_snap < 0) return WKV6_EINVAL;
+        if (snap->snap_every > 0 && (!snap->cu_snap || !snap->snap_slot)) return WKV6_ENULL;
+    }
     const bool chunked = io == IO_BF16 && !(flags & WKV6_ALGO_SCAN) && max_seqlen >= INFER_CHUNK_MIN_T;
     // (varlen_check's row limits: 2^30 on the chunked route with the fp32 decay, 2^31 on the scan route)
     if (int rc = varlen_check(total_T, n_seq, max_seqlen, C, H, chunked ? 0u : (unsigned)WKV6_ALGO_SCAN, WKV6_ALGO_SCAN)) return rc;
@@ -1222,11 +1236,16 @@ static int rwkv6_infer_varlen(long total_T, int n_seq, int max_seqlen, int C, in
     a.state_slot = state_slot; a.n_slots = n_slots;
     a.y = y;
     if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, true, io == IO_F32 ? (unsigned)WKV6_IO_F32 : 0u, {y}, st)) return to_rc(e);
-    if (!chunked) return to_rc(launch_scan_fwd_slots(a, io, st));          // a decode step, fp16 / fp32 I/O, WKV6_ALGO_SCAN: no window
+    if (snap) {
+        a.state_slot_out = snap->state_slot_out;
+        a.snap_every = snap->snap_every; a.cu_snap = snap->cu_snap; a.snap_slot = snap->snap_slot; a.n_snap = snap->n_snap;
+    }
+    if (!chunked) return to_rc(snap ? launch_scan_fwd_snap(a, io, st) : launch_scan_fwd_slots(a, io, st));   // a decode step, fp16 / fp32 I/O, WKV6_ALGO_SCAN: no window
     a.len_lo = INFER_CHUNK_MIN_T; a.len_hi = 0x7fffffff;
-    if (hipError_t e = launch_chunk_fwd_slots(a, st)) return to_rc(e);
+    if (hipError_t e = snap ? launch_chunk_fwd_snap(a, st) : launch_chunk_fwd_slots(a, st)) return to_rc(e);
     a.len_lo = 0; a.len_hi = INFER_CHUNK_MIN_T;
-    return to_rc(launch_scan_fwd_slots(a, io, st));
+    // (SNAP below the window too: no sequence that short has a snapshot, but its final state goes to state_slot_out)
+    return to_rc(snap ? launch_scan_fwd_snap(a, io, st) : launch_scan_fwd_slots(a, io, st));
 }
 int rwkv6_forward_varlen_bf16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
                               int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
@@ -1248,6 +1267,34 @@ int rwkv6_forward_varlen_fp32(long total_T, int n_seq, int max_seqlen, int C, in
 {
     return rwkv6_infer_varlen(total_T, n_seq, max_seqlen, C, H, cu_seqlens, state_slot, n_slots, state_pool, r, k, v, w, u, y, workspace,
                               workspace_bytes, flags, IO_F32, stream);
+}
+
+int rwkv6_forward_varlen_snap_bf16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                                   int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                                   void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream, const int* state_slot_out,
+                                   int snap_every, const int* cu_snap, const int* snap_slot, int n_snap)
+{
+    const SnapArgs sn{state_slot_out, snap_every, cu_snap, snap_slot, n_snap};
+    return rwkv6_infer_varlen(total_T, n_seq, max_seqlen, C, H, cu_seqlens, state_slot, n_slots, state_pool, r, k, v, w, u, y, workspace,
+                              workspace_bytes, flags, IO_BF16, stream, &sn);
+}
+int rwkv6_forward_varlen_snap_fp16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                                   int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                                   void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream, const int* state_slot_out,
+                                   int snap_every, const int* cu_snap, const int* snap_slot, int n_snap)
+{
+    const SnapArgs sn{state_slot_out, snap_every, cu_snap, snap_slot, n_snap};
+    return rwkv6_infer_varlen(total_T, n_seq, max_seqlen, C, H, cu_seqlens, state_slot, n_slots, state_pool, r, k, v, w, u, y, workspace,
+                              workspace_bytes, flags, IO_F16, stream, &sn);
+}
+int rwkv6_forward_varlen_snap_fp32(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                                   int n_slots, float* state_pool, const float* r, const float* k, const float* v, const float* w,
+                                   const float* u, float* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream,
+                                   const int* state_slot_out, int snap_every, const int* cu_snap, const int* snap_slot, int n_snap)
+{
+    const SnapArgs sn{state_slot_out, snap_every, cu_snap, snap_slot, n_snap};
+    return rwkv6_infer_varlen(total_T, n_seq, max_seqlen, C, H, cu_seqlens, state_slot, n_slots, state_pool, r, k, v, w, u, y, workspace,
+                              workspace_bytes, flags, IO_F32, stream, &sn);
 }
 
 static int selftest_problem(int B, void* stream)

@@ -118,7 +118,11 @@ __device__ __forceinline__ bool fwd_hw_wave_produces(int hw) { return hw >= 4; }
 // SLOTS (packed stateful inference, chunk_fwd_varlen_slots_kernel; VARLEN only): the fp32 state of sequence b lives in slot a.state_slot[b]
 // of the pool a.s0 == a.s_out and is updated in place -- the lanes that load an element in the consumer prologue store it in the epilogue --
 // and a.len_lo / a.len_hi select the sequences this launch serves (wkv6_scan.h)
-template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false, bool VARLEN = false, bool SLOTS = false>
+// SNAP (chunk_fwd_varlen_snap_kernel; SLOTS only): the final state goes to slot a.state_slot_out[b] instead, and the state after every
+// a.snap_every tokens (a whole number of groups) to a slot of its own (wkv6_scan.h: SnapPlan) -- the consumers' registers St behind a group's
+// last block, through the epilogue's per-lane store: a wave-uniform test per group, no barrier and no LDS of its own
+template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false, bool VARLEN = false, bool SLOTS = false,
+          bool SNAP = false>
 __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned slot, const unsigned sslot, FwdRaw& raw, const FwdChain& ch = FwdChain{})
 {
     [[maybe_unused]] const bool nxvalid = ch.nx_valid, chained_in = ch.chained_in, nx_use_u = ch.nx_use_u;
@@ -160,6 +164,11 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
         static_assert(VARLEN && !CHAIN && !CLK, "state slots: plain packed rows only");
         if (outside_len_window(a, ntok)) return;                  // (workgroup-uniform; in front of every barrier and every access)
         sslot_ = state_slot_of(a, b, ntok);
+    }
+    [[maybe_unused]] int dslot_ = sslot_;                         // SNAP: where the final state goes, -1: nowhere
+    if constexpr (SNAP) {
+        static_assert(SLOTS && !STATE_ONLY && !ACC && !GN, "snapshots: packed stateful inference only");
+        dslot_ = state_slot_out_of(a, b, ntok, sslot_);
     }
     const int ngrp = (ntok + GRP - 1) / GRP;
     const TokAddr<AFF> tok(a, b, ntok);                           // token addressing (wkv6_scan.h): AFF = no per-tensor reversal map
@@ -494,6 +503,12 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
                 }
             }
         };
+        [[maybe_unused]] SnapPlan snaps{0, 0};
+        [[maybe_unused]] int snap_j = 0, snap_at = 0;             // SNAP: the next snapshot and the number of groups that completes it
+        if constexpr (SNAP) {
+            snaps = snap_plan(a, b, ntok);
+            snap_at = a.snap_every / GRP;
+        }
         if (!(CHAIN && chained_in)) __syncthreads();            // (a call that was prepared for: the barriers that closed the call before it)
         constexpr bool STAGE_Y = !STATE_ONLY && !GN;              // (bf16 y of this launch goes through the staged rows; a y_f32 first half stores directly)
         const bool staged = STAGE_Y && (ACC || !a.y_f32);
@@ -658,10 +673,27 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
             WKV6_T(ts2);
             WKV6_ACC(0, ts1, ts0); WKV6_ACC(1, ts2, ts1);
             if constexpr (GN) gn_finish(grp);
+            if constexpr (SNAP) {
+                // (snap_j < count: (snap_j + 1) * snap_every <= ntok, so every group up to here was a full one.  Behind the barrier: the
+                // stores are in flight under the next group, nobody waits for them)
+                if (snap_j < snaps.count && grp + 1 == snap_at) {
+                    const int ss = snap_slot_of(a, snaps, snap_j);
+                    if (ss >= 0) {
+                        const long so_ = ((long)ss * a.H + h) * HEAD * HEAD + (long)(16 * wv + x) * HEAD + 8 * g;
+#pragma unroll
+                        for (int it = 0; it < 4; ++it) {
+                            const float t4[4] = {St[it][0], St[it][1], St[it][2], St[it][3]};
+                            io4<float>::store(reinterpret_cast<float*>(a.s_out) + so_ + tile_ch(it), t4);
+                        }
+                    }
+                    ++snap_j;
+                    snap_at += a.snap_every / GRP;
+                }
+            }
         }
         if (staged && ngrp > 0) flush_y(ngrp - 1);                // (the loop's last barrier closed the last group)
-        if (SLOTS ? sslot_ >= 0 : a.s_out != nullptr) {
-            const long so_ = ((long)(SLOTS ? sslot_ : b) * a.H + h) * HEAD * HEAD + (long)(16 * wv + x) * HEAD + 8 * g;
+        if (SLOTS ? (SNAP ? dslot_ : sslot_) >= 0 : a.s_out != nullptr) {
+            const long so_ = ((long)(SLOTS ? (SNAP ? dslot_ : sslot_) : b) * a.H + h) * HEAD * HEAD + (long)(16 * wv + x) * HEAD + 8 * g;
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const float t4[4] = {St[it][0], St[it][1], St[it][2], St[it][3]};
@@ -724,6 +756,14 @@ __global__ __launch_bounds__(512) void chunk_fwd_varlen_slots_kernel(const ScanA
 {
     FwdRaw raw;
     chunk_fwd_body<false, false, false, false, true, false, false, true, true>(a, blockIdx.x, 0u, raw);
+}
+
+// ... with a separate output slot and state snapshots (rwkv6_forward_varlen_snap_bf16).  A kernel of its own: the one above keeps its
+// instruction stream.
+__global__ __launch_bounds__(512) void chunk_fwd_varlen_snap_kernel(const ScanArgs a)
+{
+    FwdRaw raw;
+    chunk_fwd_body<false, false, false, false, true, false, false, true, true, true>(a, blockIdx.x, 0u, raw);
 }
 
 // Packed rows under a per-tensor reversal map (a.rev_n, indexed by the sequence): general token addressing from the sequence's first token --
@@ -959,6 +999,23 @@ hipError_t launch_chunk_fwd_slots(const ScanArgs& a_, hipStream_t st)
     static LdsAttrOnce attr;
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_slots_kernel), lds)) return e;
     hipLaunchKernelGGL(chunk_fwd_varlen_slots_kernel, dim3(a.B * a.H), dim3(512), lds, st, a);
+    return hipGetLastError();
+}
+
+// ... with the final state in slot a.state_slot_out and the snapshots of wkv6_scan.h: SnapPlan
+hipError_t launch_chunk_fwd_snap(const ScanArgs& a_, hipStream_t st)
+{
+    if (!offsets_fit(a_)) return hipErrorInvalidValue;
+    if (!a_.tok_off || !a_.ck_off || !a_.lens || !a_.order || !slots_ok(a_) || !snap_ok(a_) || a_.wkind != 2) return hipErrorInvalidValue;
+    if (!varlen_fwd_plain(a_) || a_.rev_n || a_.ckpt) return hipErrorNotSupported;
+    ScanArgs a = a_;
+    a.split = 0;
+    a.clk = nullptr; a.clk_slots = 0;
+    attach_debug_buffer(a);
+    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
+    static LdsAttrOnce attr;
+    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_snap_kernel), lds)) return e;
+    hipLaunchKernelGGL(chunk_fwd_varlen_snap_kernel, dim3(a.B * a.H), dim3(512), lds, st, a);
     return hipGetLastError();
 }
 

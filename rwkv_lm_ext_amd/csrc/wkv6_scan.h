@@ -109,6 +109,16 @@ struct ScanArgs {
     int n_slots;
     int len_lo, len_hi;               // len_hi != 0: a workgroup whose sequence has a (clamped) length outside [len_lo, len_hi) returns
                                       // before it touches anything -- two launches over one prepared batch share it by length
+    // State snapshots and a separate output slot (rwkv6_forward_varlen_snap_*: the SNAP instantiations read these, nobody else does; at the
+    // end once more).  The final state of sequence b goes to slot state_slot_out[b] (null: its source slot, the in-place update above),
+    // validated like the source.  Sequence b keeps m = min(len / snap_every, cu_snap[b+1] - cu_snap[b]) snapshots: the state after its
+    // first (j + 1) * snap_every tokens goes to slot snap_slot[cu_snap[b] + j] of the same pool, j < m; a slot outside the pool is skipped.
+    // cu_snap is clamped into [0, n_snap] on the device; none of the arrays is read by the host.
+    const int* state_slot_out;
+    int snap_every;                   // 0: no snapshots (cu_snap / snap_slot may be null), else a multiple of 64
+    const int* cu_snap;               // [B + 1]
+    const int* snap_slot;             // [n_snap]
+    int n_snap;
 };
 
 // Shortest sequence the stateful inference calls (rwkv6_cuda_forward_bf16, rwkv6_forward_varlen_bf16) hand to the chunked kernel; shorter
@@ -120,6 +130,30 @@ __device__ __forceinline__ int state_slot_of(const ScanArgs& a, int b, int ntok)
 {
     const int slot = a.state_slot ? a.state_slot[b] : b;
     return (ntok > 0 && slot >= 0 && slot < a.n_slots) ? slot : -1;
+}
+// SNAP: the slot that takes the final state of sequence b whose source slot is `src`, or -1: nothing is stored.  The same rule, on its own.
+__device__ __forceinline__ int state_slot_out_of(const ScanArgs& a, int b, int ntok, int src)
+{
+    if (!a.state_slot_out) return src;
+    const int slot = a.state_slot_out[b];
+    return (ntok > 0 && slot >= 0 && slot < a.n_slots) ? slot : -1;
+}
+// SNAP: the snapshots of sequence b -- snap_slot[first + j] takes the state after (j + 1) * snap_every tokens, j < count.  first + count never
+// passes n_snap, so every index formed from it lies inside snap_slot.
+struct SnapPlan {
+    int first, count;
+};
+__device__ __forceinline__ SnapPlan snap_plan(const ScanArgs& a, int b, int ntok)
+{
+    if (a.snap_every <= 0 || !a.cu_snap || !a.snap_slot || a.n_snap <= 0) return SnapPlan{0, 0};
+    const int lo = min(max(a.cu_snap[b], 0), a.n_snap), hi = min(max(a.cu_snap[b + 1], 0), a.n_snap);
+    return SnapPlan{lo, min(ntok / a.snap_every, max(hi - lo, 0))};
+}
+// slot of snapshot j < count, or -1: skipped (tested before any address is formed, like a state slot)
+__device__ __forceinline__ int snap_slot_of(const ScanArgs& a, const SnapPlan& sp, int j)
+{
+    const int slot = a.snap_slot[sp.first + j];
+    return (slot >= 0 && slot < a.n_slots) ? slot : -1;
 }
 // (decided once per workgroup, in front of everything else)
 __device__ __forceinline__ bool outside_len_window(const ScanArgs& a, int ntok)
@@ -211,6 +245,13 @@ inline bool slots_ok(const ScanArgs& a)
 }
 hipError_t launch_scan_fwd_slots(const ScanArgs& a, int io, hipStream_t st);
 hipError_t launch_chunk_fwd_slots(const ScanArgs& a, hipStream_t st);
+// ... with a separate output slot and state snapshots (ScanArgs: state_slot_out, snap_every, cu_snap, snap_slot, n_snap)
+inline bool snap_ok(const ScanArgs& a)
+{
+    return a.snap_every >= 0 && a.snap_every % 64 == 0 && a.n_snap >= 0 && (a.snap_every == 0 || (a.cu_snap && a.snap_slot));
+}
+hipError_t launch_scan_fwd_snap(const ScanArgs& a, int io, hipStream_t st);
+hipError_t launch_chunk_fwd_snap(const ScanArgs& a, hipStream_t st);
 hipError_t launch_chunk_state_pass(const ScanArgs& a, hipStream_t st);   // state recurrence only (s_out, ckpt, dsum)
 // In-run clock probe (wkv6_set_clock_ring, wkv6_api.hip): where launch number n of kind (0: chunked forward, 1: chunked backward) stamps,
 // or null; takes the launch's place in the ring (host side, one atomic increment per launch)

@@ -107,9 +107,14 @@ __device__ __forceinline__ void load_ew(const ScanArgs& a, long idx, bool valid,
 // SLOTS (packed stateful inference, launch_scan_fwd_slots): the fp32 state of sequence b lives in slot a.state_slot[b] of the pool
 // a.s0 == a.s_out and is updated in place; a.len_lo / a.len_hi select the sequences this launch serves (wkv6_scan.h).  Instantiations of
 // their own: the dense and the packed training kernels keep their instruction streams.
-template <typename T, int NW, bool SLOTS = false>
+// SNAP (launch_scan_fwd_snap): SLOTS, and the final state goes to slot a.state_slot_out[b], the state after every a.snap_every tokens to a
+// slot of its own (wkv6_scan.h: SnapPlan) -- the registers S after a token batch, through the epilogue's per-lane store.  SNAP implies
+// SLOTS and is instantiated as <T, NW, false, true>: the ISA guard of the SLOTS instantiations picks them by the prefix
+// scan_fwd_kernel<T, 8, true of their mangled names, which has to stay theirs alone.
+template <typename T, int NW, bool SLOTS_ = false, bool SNAP = false>
 __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
 {
+    constexpr bool SLOTS = SLOTS_ || SNAP;
     using G = Geo<NW>;
     constexpr int CPT = G::CPT, TPT = G::TPT, JPW = HEAD / NW, JR = JPW / 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -130,6 +135,14 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
     if constexpr (SLOTS) {
         if (outside_len_window(a, ntok)) return;        // (workgroup-uniform, in front of the first barrier and the first access)
         slot = state_slot_of(a, b, ntok);
+    }
+    [[maybe_unused]] int slot_out = slot;               // SNAP: where the final state goes, -1: nowhere
+    [[maybe_unused]] SnapPlan snaps{0, 0};
+    [[maybe_unused]] int snap_j = 0, snap_at = 0;       // SNAP: the next snapshot and the token batch that completes it
+    if constexpr (SNAP) {
+        slot_out = state_slot_out_of(a, b, ntok, slot);
+        snaps = snap_plan(a, b, ntok);
+        snap_at = a.snap_every / TB;
     }
     const RevMap tokmap = make_revmap(a, b, ntok);      // token each tensor holds at scan position p (wkv6_scan.h)
     const long base = (a.tok_off ? (long)a.tok_off[b] : (long)b * a.T) * a.C + (long)h * HEAD;
@@ -230,6 +243,22 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
                 }
             }
         }
+        if constexpr (SNAP) {
+            // (snap_j < count: (snap_j + 1) * snap_every <= ntok, so this batch was a full one; workgroup-uniform)
+            if (snap_j < snaps.count && q + 1 == snap_at) {
+                const int ss = snap_slot_of(a, snaps, snap_j);
+                if (ss >= 0) {
+                    const long so_ = ((long)ss * a.H + h) * HEAD * HEAD;
+#pragma unroll
+                    for (int jj = 0; jj < JR; ++jj) {
+                        const float t4[4] = {S[0][jj], S[1][jj], S[2][jj], S[3][jj]};
+                        io4<float>::store(reinterpret_cast<float*>(a.s_out) + so_ + (long)(j0 + jj) * HEAD + i0, t4);
+                    }
+                }
+                ++snap_j;
+                snap_at += a.snap_every / TB;
+            }
+        }
         if (q + 1 < nq) write_lds(buf ^ 1);
         __syncthreads();
         {   // ---- coalesced store of this batch's outputs
@@ -252,8 +281,8 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanArgs a)
             }
         }
     }
-    if (SLOTS ? slot >= 0 : a.s_out != nullptr) {
-        const long so_ = ((long)(SLOTS ? slot : b) * a.H + h) * HEAD * HEAD;
+    if (SLOTS ? (SNAP ? slot_out : slot) >= 0 : a.s_out != nullptr) {
+        const long so_ = ((long)(SLOTS ? (SNAP ? slot_out : slot) : b) * a.H + h) * HEAD * HEAD;
 #pragma unroll
         for (int jj = 0; jj < JR; ++jj) {
             const float t4[4] = {S[0][jj], S[1][jj], S[2][jj], S[3][jj]};
@@ -801,6 +830,17 @@ hipError_t launch_scan_fwd_slots(const ScanArgs& a, int io, hipStream_t st)
     if (io == IO_F32) hipLaunchKernelGGL((scan_fwd_kernel<float, NWAVES, true>), grid, block, lds, st, a);
     else if (io == IO_F16) hipLaunchKernelGGL((scan_fwd_kernel<f16_t, NWAVES, true>), grid, block, lds, st, a);
     else hipLaunchKernelGGL((scan_fwd_kernel<bf16_t, NWAVES, true>), grid, block, lds, st, a);
+    return hipGetLastError();
+}
+// ... with the final state in slot a.state_slot_out and the snapshots of wkv6_scan.h: SnapPlan
+hipError_t launch_scan_fwd_snap(const ScanArgs& a, int io, hipStream_t st)
+{
+    if (!varlen_scan_ok(a) || !slots_ok(a) || !snap_ok(a) || a.reverse || a.rev_n) return hipErrorInvalidValue;
+    constexpr size_t lds = (2 * 4 * TB * ROW + 64 + 2 * TB * ROW) * sizeof(float);
+    const dim3 grid(a.B * a.H), block(NWAVES * 64);
+    if (io == IO_F32) hipLaunchKernelGGL((scan_fwd_kernel<float, NWAVES, false, true>), grid, block, lds, st, a);
+    else if (io == IO_F16) hipLaunchKernelGGL((scan_fwd_kernel<f16_t, NWAVES, false, true>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((scan_fwd_kernel<bf16_t, NWAVES, false, true>), grid, block, lds, st, a);
     return hipGetLastError();
 }
 

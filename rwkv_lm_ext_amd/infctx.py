@@ -120,22 +120,51 @@ def _keep_last_tokens(shift_pool, slots, x, cu_seqlens, max_seqlen=None):
     shift_pool.copy_(torch.cat((shift_pool, shift_pool.new_zeros(1, shift_pool.shape[1]))).index_copy_(0, dest, rows)[:n])
 
 
-def tmix_forward_packed(tm, x, cu_seqlens, max_seqlen, shift_pool, wkv_pool, slots):
+def _keep_snap_tokens(shift_pool, snap, x, cu_seqlens, max_seqlen=None):
+    """shift_pool[snap_slots[cu_snap[s] + j]] = token (j + 1) * snap_every - 1 of sequence s for every snapshot j the operator keeps
+    (include/wkv6_amd.h: rwkv6_forward_varlen_snap_*, the same clamps); everything else goes to the dummy slot behind the pool."""
+    snap_every, cu_snap, snap_slots = snap
+    n, T, n_snap = shift_pool.shape[0], x.shape[0], snap_slots.numel()
+    most = (T if max_seqlen is None else min(T, int(max_seqlen))) // int(snap_every)     # snapshots of the longest sequence there can be
+    if most < 1 or n_snap < 1:
+        return
+    cu, cs = cu_seqlens.long().clamp(0, T), cu_snap.long().clamp(0, n_snap)
+    length = cu[1:] - cu[:-1]
+    if max_seqlen is not None:
+        length = length.clamp(max=int(max_seqlen))
+    count = torch.minimum(length.clamp(min=0) // int(snap_every), (cs[1:] - cs[:-1]).clamp(min=0))
+    j = torch.arange(most, device=x.device).unsqueeze(0)                                 # [1, most] against [n_seq, 1]
+    s = snap_slots.long()[(cs[:-1].unsqueeze(1) + j).clamp(0, n_snap - 1)]
+    alive = (j < count.unsqueeze(1)) & (s >= 0) & (s < n)
+    rows = x[(cu[:-1].unsqueeze(1) + (j + 1) * int(snap_every) - 1).clamp(0, T - 1).reshape(-1)].to(shift_pool.dtype)
+    dest = torch.where(alive, s, torch.full_like(s, n)).reshape(-1)
+    shift_pool.copy_(torch.cat((shift_pool, shift_pool.new_zeros(1, shift_pool.shape[1]))).index_copy_(0, dest, rows)[:n])
+
+
+def tmix_forward_packed(tm, x, cu_seqlens, max_seqlen, shift_pool, wkv_pool, slots, out_slots=None, snap=None):
     """tmix_forward_infctx for every sequence of a packed batch x [1,total_T,C] in one pass (a callers.Tmix_x060 `tm`): the token shift
-    starts from shift_pool[slots[s]], the operator (wkv.RUN_RWKV_6_VARLEN) from wkv_pool[slots[s]]; both pools are updated in place."""
+    starts from shift_pool[slots[s]], the operator (wkv.RUN_RWKV_6_VARLEN) from wkv_pool[slots[s]]; both pools are updated in place.
+    out_slots (int32 [n_seq]): what the sequences leave goes to these slots of both pools instead, slots keeps its contents.
+    snap = (snap_every, cu_snap, snap_slots): the state after every snap_every tokens is kept as well -- the WKV state and the token in
+    front of the next one land in the same slot number snap_slots[cu_snap[s] + j] of their pools."""
     from .wkv import RUN_RWKV_6_VARLEN
     B, T, C = x.size()
     assert B == 1, "a packed batch is [1,total_T,C]"
     r, k, v, g, w = tm.jit_func(x, cu_seqlens=cu_seqlens, shifted0=_carried_tokens(shift_pool, slots).to(x.dtype))
     u = tm.time_faaaa.to(r.dtype).contiguous()
-    y, _ = RUN_RWKV_6_VARLEN(T, C, tm.n_head, wkv_pool, slots, *(t.contiguous() for t in (r, k, v, w.to(r.dtype))), u, cu_seqlens, max_seqlen)
+    snap_every, cu_snap, snap_slots = snap if snap is not None else (0, None, None)
+    y, _ = RUN_RWKV_6_VARLEN(T, C, tm.n_head, wkv_pool, slots, *(t.contiguous() for t in (r, k, v, w.to(r.dtype))), u, cu_seqlens, max_seqlen,
+                             state_slot_out=out_slots, snap_every=snap_every, cu_snap=cu_snap, snap_slot=snap_slots)
     out = tm.jit_func_2(y, g)
-    _keep_last_tokens(shift_pool, slots, x[0], cu_seqlens, max_seqlen)
+    _keep_last_tokens(shift_pool, slots if out_slots is None else out_slots, x[0], cu_seqlens, max_seqlen)
+    if snap is not None and snap_every > 0:
+        _keep_snap_tokens(shift_pool, snap, x[0], cu_seqlens, max_seqlen)
     return out
 
 
-def cmix_forward_packed(cm, x, cu_seqlens, shift_pool, slots):
-    """cmix_forward_infctx for every sequence of a packed batch x [1,total_T,C] (a callers.CMix_x060 `cm`); shift_pool is this sub-layer's."""
+def cmix_forward_packed(cm, x, cu_seqlens, shift_pool, slots, out_slots=None, snap=None):
+    """cmix_forward_infctx for every sequence of a packed batch x [1,total_T,C] (a callers.CMix_x060 `cm`); shift_pool is this sub-layer's.
+    out_slots and snap as in tmix_forward_packed."""
     from .callers import _packed_prev
     B, T, C = x.size()
     assert B == 1, "a packed batch is [1,total_T,C]"
@@ -148,5 +177,7 @@ def cmix_forward_packed(cm, x, cu_seqlens, shift_pool, slots):
         xx = _packed_prev(x, cu_seqlens, carried) - x
         k = torch.relu(cm.key(x + xx * cm.time_maa_k)) ** 2
         out = torch.sigmoid(cm.receptance(x + xx * cm.time_maa_r)) * cm.value(k)
-    _keep_last_tokens(shift_pool, slots, x[0], cu_seqlens)
+    _keep_last_tokens(shift_pool, slots if out_slots is None else out_slots, x[0], cu_seqlens)
+    if snap is not None and snap[0] > 0:
+        _keep_snap_tokens(shift_pool, snap, x[0], cu_seqlens)
     return out

@@ -481,10 +481,13 @@ class RWKV_6_VARLEN(torch.autograd.Function):
     """RWKV_6 on a packed batch for a serving loop: the sequences lie back to back in [total_T,C] tensors (sequence s = rows
     cu_seqlens[s] .. cu_seqlens[s+1]-1: prompts of any lengths, prefill next to one-token decode steps) and sequence s keeps its fp32
     state in slot state_slot[s] (int32 [n_seq] on the device; None: slot s) of the caller's pool state_pool [n_slots,H,N,N], which is
-    updated in place and returned.  A slot outside the pool means no state: zero in, nothing out.  w is the raw decay parameter."""
+    updated in place and returned.  A slot outside the pool means no state: zero in, nothing out.  w is the raw decay parameter.
+    state_slot_out / snap_every, cu_snap, snap_slot: a separate slot for the final state and state snapshots every snap_every tokens
+    (wkv6_op.rwkv6.forward_varlen_*)."""
 
     @staticmethod
-    def forward(ctx, total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen):
+    def forward(ctx, total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen, state_slot_out=None, snap_every=0,
+                cu_snap=None, snap_slot=None):
         with torch.no_grad():
             assert HEAD_SIZE == C // H
             assert state_pool.dtype == torch.float32
@@ -498,9 +501,12 @@ class RWKV_6_VARLEN(torch.autograd.Function):
                   torch.float16: wkv6_op.rwkv6.forward_varlen_fp16}.get(r.dtype)
             if fn is None:
                 raise RuntimeError(f"unsupported dtype {r.dtype}")
-            fn(total_T, C, H, state_pool, state_slot, r, k, v, eew, u, y, cu_seqlens, max_seqlen)
+            fn(total_T, C, H, state_pool, state_slot, r, k, v, eew, u, y, cu_seqlens, max_seqlen, state_slot_out=state_slot_out,
+               snap_every=snap_every, cu_snap=cu_snap, snap_slot=snap_slot)
             return y.view(shape), state_pool
 
 
-def RUN_RWKV_6_VARLEN(total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen):
-    return RWKV_6_VARLEN.apply(total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen)
+def RUN_RWKV_6_VARLEN(total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen, state_slot_out=None, snap_every=0,
+                      cu_snap=None, snap_slot=None):
+    return RWKV_6_VARLEN.apply(total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen, state_slot_out, snap_every,
+                               cu_snap, snap_slot)

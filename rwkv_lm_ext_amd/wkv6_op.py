@@ -195,10 +195,15 @@ class _Rwkv6:
 
     # ---- packed batches with a state-slot pool (include/wkv6_amd.h: rwkv6_forward_varlen_*) ----
     @staticmethod
-    def _call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, io):
+    def _call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, io,
+                     state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None, force_snap=False):
         """Every sequence of the packed [total_T,C] tensors (rows cu_seqlens[s] .. cu_seqlens[s+1]-1) from the state in slot state_slot[s]
         (None: slot s) of state_pool fp32 [n_slots,H,N,N], which is updated in place; y is written, rows outside every sequence as +0.
-        w is the fp32 decay.  algo="scan" forces the exact scan kernel; ws: a new_rwkv6_varlen_workspace() buffer (graph capture)."""
+        w is the fp32 decay.  algo="scan" forces the exact scan kernel; ws: a new_rwkv6_varlen_workspace() buffer (graph capture).
+        state_slot_out (int32 [n_seq]): the slot that takes the final state of sequence s instead of its source slot.  snap_every (a
+        multiple of 64) with cu_snap (int32 [n_seq + 1]) and snap_slot (int32 [n_snap]): the state after the first (j + 1) * snap_every
+        tokens of sequence s goes to slot snap_slot[cu_snap[s] + j] as well (include/wkv6_amd.h: rwkv6_forward_varlen_snap_*).  With all
+        four at their defaults the plain entry point is called (force_snap: the snap entry point all the same)."""
         tc = (total_T, C)
         named = dict(state_pool=(state_pool, None, torch.float32), r=(r, tc, io), k=(k, tc, io), v=(v, tc, io),
                      w=(w, tc, torch.float32), u=(u, (H, HEAD_SIZE), io), y=(y, tc, io))
@@ -225,27 +230,79 @@ class _Rwkv6:
         if ws is not None and not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous()
                                    and ws.device == r.device):
             raise RuntimeError("ws must be a new_rwkv6_varlen_workspace() buffer on the device of r")
+
+        def int_array(name, t, shape, what):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1
+                    and (shape is None or tuple(t.shape) == shape) and t.device == r.device):
+                raise RuntimeError(f"{name} must be a contiguous int32 {what} tensor on the device of r")
+
+        snap = force_snap or not (state_slot_out is None and isinstance(snap_every, int) and snap_every == 0 and cu_snap is None and snap_slot is None)
+        if snap:
+            if not isinstance(snap_every, int) or snap_every < 0 or snap_every % 64 != 0:
+                raise RuntimeError(f"snap_every must be 0 or a multiple of 64, got {snap_every!r}")
+            if state_slot_out is not None:
+                int_array("state_slot_out", state_slot_out, (n_seq,), "[n_seq]")
+            if snap_every == 0:
+                if cu_snap is not None or snap_slot is not None:
+                    raise RuntimeError("cu_snap and snap_slot belong to snap_every > 0")
+            else:
+                int_array("cu_snap", cu_snap, (n_seq + 1,), "[n_seq + 1]")
+                int_array("snap_slot", snap_slot, None, "[n_snap]")
         dev = _check_tensors(n_seq, total_T, C, H, named, dtype=io)
         lib = _lib.load()
-        fn = {torch.bfloat16: lib.rwkv6_forward_varlen_bf16, torch.float16: lib.rwkv6_forward_varlen_fp16,
-              torch.float32: lib.rwkv6_forward_varlen_fp32}[io]
+        base = (int(total_T), n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(state_slot), n_slots, _ptr(state_pool), _ptr(r),
+                _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _ptr(ws), 0 if ws is None else ws.numel(),
+                _lib.ALGO_SCAN if algo == "scan" else 0)
         with torch.cuda.device(dev):
-            rc = fn(int(total_T), n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(state_slot), n_slots, _ptr(state_pool), _ptr(r),
-                    _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _ptr(ws), 0 if ws is None else ws.numel(),
-                    _lib.ALGO_SCAN if algo == "scan" else 0, _stream_ptr())
+            if snap:
+                fn = {torch.bfloat16: lib.rwkv6_forward_varlen_snap_bf16, torch.float16: lib.rwkv6_forward_varlen_snap_fp16,
+                      torch.float32: lib.rwkv6_forward_varlen_snap_fp32}[io]
+                rc = fn(*base, _stream_ptr(), _ptr(state_slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slot),
+                        0 if snap_slot is None else snap_slot.numel())
+            else:
+                fn = {torch.bfloat16: lib.rwkv6_forward_varlen_bf16, torch.float16: lib.rwkv6_forward_varlen_fp16,
+                      torch.float32: lib.rwkv6_forward_varlen_fp32}[io]
+                rc = fn(*base, _stream_ptr())
         _lib.check(rc, "rwkv6 forward_varlen")
 
     @staticmethod
-    def forward_varlen_bf16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None):
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.bfloat16)
+    def forward_varlen_bf16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None,
+                            state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None):
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.bfloat16,
+                            state_slot_out, snap_every, cu_snap, snap_slot)
 
     @staticmethod
-    def forward_varlen_fp16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None):
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.float16)
+    def forward_varlen_snap_bf16(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
+                                 cu_snap, snap_slot):
+        """torch.ops.rwkv6.forward_varlen_snap_bf16: always the snap entry point of the library, defaults included."""
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, None, torch.bfloat16,
+                            state_slot_out, snap_every, cu_snap, snap_slot, force_snap=True)
 
     @staticmethod
-    def forward_varlen_fp32(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None):
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.float32)
+    def forward_varlen_fp16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None,
+                            state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None):
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.float16,
+                            state_slot_out, snap_every, cu_snap, snap_slot)
+
+    @staticmethod
+    def forward_varlen_snap_fp16(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
+                                 cu_snap, snap_slot):
+        """torch.ops.rwkv6.forward_varlen_snap_fp16: always the snap entry point of the library, defaults included."""
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, None, torch.float16,
+                            state_slot_out, snap_every, cu_snap, snap_slot, force_snap=True)
+
+    @staticmethod
+    def forward_varlen_fp32(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None,
+                            state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None):
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.float32,
+                            state_slot_out, snap_every, cu_snap, snap_slot)
+
+    @staticmethod
+    def forward_varlen_snap_fp32(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
+                                 cu_snap, snap_slot):
+        """torch.ops.rwkv6.forward_varlen_snap_fp32: always the snap entry point of the library, defaults included."""
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, None, torch.float32,
+                            state_slot_out, snap_every, cu_snap, snap_slot, force_snap=True)
 
 
 class _Wkv5:
@@ -984,6 +1041,12 @@ def _register():
     for name in ("forward_varlen_bf16", "forward_varlen_fp16", "forward_varlen_fp32"):
         rv.define(name + "(int total_T, int C, int H, Tensor(s!) state_pool, Tensor? state_slot, Tensor r, Tensor k, Tensor v, Tensor w, "
                          "Tensor u, Tensor(a!) y, Tensor cu_seqlens, int max_seqlen) -> ()")
+        rv.impl(name, getattr(_Rwkv6, name), "CUDA")
+    # ... with a separate output slot and state snapshots; the snapshot slots of state_pool are written too
+    for name in ("forward_varlen_snap_bf16", "forward_varlen_snap_fp16", "forward_varlen_snap_fp32"):
+        rv.define(name + "(int total_T, int C, int H, Tensor(s!) state_pool, Tensor? state_slot, Tensor? state_slot_out, Tensor r, Tensor k, "
+                         "Tensor v, Tensor w, Tensor u, Tensor(a!) y, Tensor cu_seqlens, int max_seqlen, int snap_every, Tensor? cu_snap, "
+                         "Tensor? snap_slot) -> ()")
         rv.impl(name, getattr(_Rwkv6, name), "CUDA")
     libs.append(rv)
     w5 = torch.library.Library("wkv5", "DEF")           # TORCH_LIBRARY(wkv5, m), cuda/wkv5_op.cpp:19-22
