@@ -255,6 +255,46 @@ int rwkv6_forward_varlen_snap_fp32(long total_T, int n_seq, int max_seqlen, int 
                                    const float* u, float* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream,
                                    const int* state_slot_out, int snap_every, const int* cu_snap, const int* snap_slot, int n_snap);
 
+/* ---- ... with long sequences cut over T (a long prompt of a serving batch: one workgroup per (sequence, head) leaves most of the chip idle
+ * for the whole prefill).  The argument list of rwkv6_forward_varlen_snap_bf16 and then
+ *   seg_len : 0, or a multiple of 64
+ * seg_len == 0 is rwkv6_forward_varlen_snap_bf16: the same launches, the same results.  With seg_len > 0 every sequence whose clamped length
+ * passes seg_len is cut at multiples of seg_len into ITEMS (item g = its tokens [g * seg_len, min((g + 1) * seg_len, len_s))) that run as one
+ * workgroup per (item, head); every other sequence is one item and runs as in the snap call.  The cut is made on the device, behind the clamps
+ * of cu_seqlens: the host never reads it and bounds the item table by n_seq + total_T / seg_len entries (the grid is that times H; workgroups
+ * without an item return at once).  A sequence whose full segments do not fit under total_T / seg_len together with those in front of it --
+ * only a cu_seqlens that is no partition of the rows can cause that -- runs uncut; the call stays memory-safe.  Dispatch order: the full
+ * segments first, then the tails and the uncut sequences, longest first.
+ * Three stages behind the one preparation launch, the two-level scan of the dense call on packed rows:
+ *   1. every item that has a successor runs the state recurrence from a zero state (its own contribution A and its log-decay sums);
+ *   2. one small kernel per (sequence, head) chains them from the source slot, S_in(g + 1) = 2^{dsum_g} (.) S_in(g) + A_g, into scratch;
+ *   3. the forward per item from its entry state.
+ * Every state the call stores is a running state of stage 3: the final state comes from a sequence's last item, snapshot j from the item
+ * that contains position (j + 1) * snap_every.  Stages 1 and 2 only read the pool, and the first item of a cut sequence starts from a copy
+ * of its source slot that stage 2 took, so the hazard rules of the snap call hold unchanged: fan-out from one source slot and the in-place
+ * use are legal.
+ * Contract:
+ *  - Sequences that are not cut: y, the destination slot and the snapshots are bit-identical to rwkv6_forward_varlen_snap_bf16.
+ *  - Cut sequences: rows [0, seg_len) of y and every snapshot at a position <= seg_len are bit-identical to that call; behind them the
+ *    results differ from it by the re-association of the state across the cut (the entry state is rounded once per segment in another order),
+ *    within the bounds of the dense two-level path, whose y it reproduces bit for bit (rwkv6_cuda_forward_bf16(B = 1) at the same cut).
+ *  - Snapshot j is bit-identical to the final state of the same call, with the same seg_len, on the sequence cut to (j + 1) * snap_every
+ *    tokens; a snapshot at position len_s equals the final state.
+ * Routing: bf16 on the chunked route only; sequences below 32 tokens take the exact scan as before.  Refused before anything is launched, in
+ * addition to what the snap call refuses (with the same codes): seg_len < 0 or no multiple of 64 (WKV6_EINVAL); seg_len > 0 together with
+ * WKV6_ALGO_SCAN (WKV6_EUNSUPPORTED).  No relation between seg_len and snap_every is required.  Limits stay per sequence:
+ * (max_seqlen + 64) * C < 2^30.
+ * workspace: rwkv6_varlen_split_workspace_bytes(total_T, n_seq, seg_len, C, H) bytes from host data alone (0 for a bad shape or seg_len;
+ * rwkv6_varlen_workspace_bytes(n_seq) at seg_len == 0): the int arrays of the plain call, the item table, and per item and head A, the
+ * entry state (16 KB each) and the decay sums.  NULL: a stream-ordered allocation of the call; shorter than that: WKV6_EWORKSPACE.
+ * Out of scope, not half-supported: what the snap call lists except the two-level scan over T, which this entry point is; fp16 / fp32 I/O
+ * (they stay on the exact scan); the C++ torch shim; an automatic choice of seg_len (the caller knows its batch: INTEGRATION.md). */
+size_t rwkv6_varlen_split_workspace_bytes(long total_T, int n_seq, int seg_len, int C, int H);
+int rwkv6_forward_varlen_split_bf16(long total_T, int n_seq, int max_seqlen, int C, int H, const int* cu_seqlens, const int* state_slot,
+                                    int n_slots, float* state_pool, const void* r, const void* k, const void* v, const float* w, const void* u,
+                                    void* y, void* workspace, size_t workspace_bytes, unsigned flags, void* stream, const int* state_slot_out,
+                                    int snap_every, const int* cu_snap, const int* snap_slot, int n_snap, int seg_len);
+
 /* ---- wkv5 (RWKV-5: the decay is a parameter, constant over batch and time): replaces cuda_forward / cuda_backward of
  * cuda/wkv5_op.cpp:5-6 (cuda/wkv5_cuda.cu:190-202).  w, u : [H,N];  gw, gu : [B,C] per-batch partials (the caller sums them over
  * the batch, src/model.py:283-284).  `eew` is the fp32 decay exp(-exp(w_raw)) and `ew` the fp32 -exp(w_raw) that src/model.py:260-261

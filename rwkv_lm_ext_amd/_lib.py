@@ -40,6 +40,8 @@ SIGNATURES = {
     "rwkv6_forward_varlen_fp16": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP]),
     "rwkv6_forward_varlen_fp32": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP]),
     "rwkv6_forward_varlen_snap_bf16": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP] + [_VP, _I, _VP, _VP, _I]),
+    "rwkv6_forward_varlen_split_bf16": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP] + [_VP, _I, _VP, _VP, _I] + [_I]),
+    "rwkv6_varlen_split_workspace_bytes": (_SZ, [_L, _I, _I, _I, _I]),
     "rwkv6_forward_varlen_snap_fp16": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP] + [_VP, _I, _VP, _VP, _I]),
     "rwkv6_forward_varlen_snap_fp32": (_I, [_L] + [_I] * 4 + [_VP, _VP, _I] + [_VP] * 8 + [_SZ, _U, _VP] + [_VP, _I, _VP, _VP, _I]),
     "wkv6_backward_workspace_bytes": (_SZ, [_I] * 4),

@@ -121,9 +121,14 @@ __device__ __forceinline__ bool fwd_hw_wave_produces(int hw) { return hw >= 4; }
 // SNAP (chunk_fwd_varlen_snap_kernel; SLOTS only): the final state goes to slot a.state_slot_out[b] instead, and the state after every
 // a.snap_every tokens (a whole number of groups) to a slot of its own (wkv6_scan.h: SnapPlan) -- the consumers' registers St behind a group's
 // last block, through the epilogue's per-lane store: a wave-uniform test per group, no barrier and no LDS of its own
+// SEG (rwkv6_forward_varlen_split_bf16; VARLEN only): row b is an ITEM -- a sequence, or one segment of a long one (wkv6_scan.h: SegArgs).  Two
+// instantiations: the state pass of every item that has a successor (STATE_ONLY: from zero, a.s_out / a.dsum indexed by the item), and the
+// forward per item (SNAP): entry state from the pool or from sg.sin, final state from a sequence's last item only, snapshot positions
+// counted from the sequence's first token.  All of it in front of and behind the group loops, which it leaves alone.
 template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false, bool VARLEN = false, bool SLOTS = false,
-          bool SNAP = false>
-__device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned slot, const unsigned sslot, FwdRaw& raw, const FwdChain& ch = FwdChain{})
+          bool SNAP = false, bool SEG = false>
+__device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned slot, const unsigned sslot, FwdRaw& raw, const FwdChain& ch = FwdChain{},
+                                               const SegArgs& sg = SegArgs{})
 {
     [[maybe_unused]] const bool nxvalid = ch.nx_valid, chained_in = ch.chained_in, nx_use_u = ch.nx_use_u;
     [[maybe_unused]] const unsigned nxbh = ch.nx_bh;
@@ -148,6 +153,10 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
     cidx = hwid;
     const bool producer = wid >= 4;
     const int wv = wid & 3;                                          // block (producer) / column tile (consumer)
+    if constexpr (SEG) {
+        static_assert(VARLEN && !CHAIN && !CLK && !ACC && !GN && (STATE_ONLY ? !SLOTS : SNAP), "items: the state pass and the stateful forward");
+        if (bh / a.H >= sg.n[0]) return;                        // (workgroup-uniform; in front of every barrier and every access: no such item)
+    }
     // (CHAIN: the persistent launch has looked the row's batch index and length up -- two dependent memory round trips -- a call ahead)
     const int b = CHAIN ? b_known : (a.order ? a.order[bh / a.H] : bh / a.H), h = bh % a.H;
     // (batch, head) origin: uniform, folded into the pointers; per-lane offsets below stay 32-bit (T*C < 2^31, checked by the API)
@@ -159,16 +168,25 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
     int ntok = a.T;
     if constexpr (CHAIN) ntok = ntok_known;
     else if (a.lens) ntok = min(max(a.lens[b], 0), a.T);
+    [[maybe_unused]] int sq_ = b, pos_ = 0, slen_ = ntok;        // SEG: the item's sequence, its first position in it, the sequence's length
+    if constexpr (SEG) {
+        sq_ = sg.seq[b]; pos_ = sg.pos[b]; slen_ = sg.seq_lens[sq_];
+        // (the state pass: an item without a successor has nothing to hand on.  Workgroup-uniform, in front of every barrier)
+        if (ntok <= 0 || (STATE_ONLY && pos_ + ntok >= slen_)) return;
+    }
+    [[maybe_unused]] const bool seg_last = !SEG || pos_ + ntok >= slen_;
+    [[maybe_unused]] const bool seg_entry = SEG && !(pos_ == 0 && seg_last);   // the entry state comes from sg.sin, not from the pool
     [[maybe_unused]] int sslot_ = -1;                            // SLOTS: this sequence's state slot, -1: none (zero in, nothing out)
     if constexpr (SLOTS) {
         static_assert(VARLEN && !CHAIN && !CLK, "state slots: plain packed rows only");
         if (outside_len_window(a, ntok)) return;                  // (workgroup-uniform; in front of every barrier and every access)
-        sslot_ = state_slot_of(a, b, ntok);
+        sslot_ = state_slot_of(a, SEG ? sq_ : b, ntok);
     }
     [[maybe_unused]] int dslot_ = sslot_;                         // SNAP: where the final state goes, -1: nowhere
     if constexpr (SNAP) {
         static_assert(SLOTS && !STATE_ONLY && !ACC && !GN, "snapshots: packed stateful inference only");
-        dslot_ = state_slot_out_of(a, b, ntok, sslot_);
+        dslot_ = state_slot_out_of(a, SEG ? sq_ : b, ntok, sslot_);
+        if constexpr (SEG) { if (!seg_last) dslot_ = -1; }        // (only a sequence's last item stores the final state)
     }
     const int ngrp = (ntok + GRP - 1) / GRP;
     const TokAddr<AFF> tok(a, b, ntok);                           // token addressing (wkv6_scan.h): AFF = no per-tensor reversal map
@@ -383,7 +401,9 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             float t4[4] = {0.f, 0.f, 0.f, 0.f};
-            if (SLOTS ? sslot_ >= 0 : a.s0 != nullptr) {
+            if (SEG && !STATE_ONLY && seg_entry) {                 // (SEG: fp32 entry state of item b, written by the chaining kernel; the state pass starts from zero)
+                if constexpr (SEG) io4<float>::load(sg.sin + ((long)b * a.H + h) * HEAD * HEAD + (long)(16 * wv + x) * HEAD + tile_ch(it) + 8 * g, t4);
+            } else if (SLOTS ? sslot_ >= 0 : a.s0 != nullptr) {
                 const long so_ = (long)(SLOTS ? sslot_ : b) * a.s0_bstride + ((long)h * HEAD + 16 * wv + x) * HEAD + tile_ch(it) + 8 * g;
                 if (a.state_f32) io4<float>::load(reinterpret_cast<const float*>(a.s0) + so_, t4);
                 else io4<bf16_t>::load(reinterpret_cast<const bf16_t*>(a.s0) + so_, t4);
@@ -505,9 +525,19 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
         };
         [[maybe_unused]] SnapPlan snaps{0, 0};
         [[maybe_unused]] int snap_j = 0, snap_at = 0;             // SNAP: the next snapshot and the number of groups that completes it
-        if constexpr (SNAP) {
+        if constexpr (SNAP && !SEG) {
             snaps = snap_plan(a, b, ntok);
             snap_at = a.snap_every / GRP;
+        }
+        if constexpr (SNAP && SEG) {
+            // the sequence's plan; this item's first candidate is the first snapshot behind position pos_, snap_at its distance in groups.
+            // (Both are multiples of 64.  A snapshot behind this item's last FULL group is never reached; one inside a partial last
+            // group does not exist: only a sequence's last item has one, and count stops at the sequence's length.)
+            snaps = snap_plan(a, sq_, slen_);
+            if (snaps.count > 0) {
+                snap_j = pos_ / a.snap_every;
+                snap_at = ((snap_j + 1) * a.snap_every - pos_) / GRP;
+            }
         }
         if (!(CHAIN && chained_in)) __syncthreads();            // (a call that was prepared for: the barriers that closed the call before it)
         constexpr bool STAGE_Y = !STATE_ONLY && !GN;              // (bf16 y of this launch goes through the staged rows; a y_f32 first half stores directly)
@@ -766,6 +796,19 @@ __global__ __launch_bounds__(512) void chunk_fwd_varlen_snap_kernel(const ScanAr
     chunk_fwd_body<false, false, false, false, true, false, false, true, true, true>(a, blockIdx.x, 0u, raw);
 }
 
+// ... with the long sequences cut into segments (rwkv6_forward_varlen_split_bf16; SEG above): the state pass of the items that have a
+// successor, and the forward per item.  Kernels of their own: the two above keep their instruction streams.
+__global__ __launch_bounds__(512) void chunk_fwd_varlen_seg_state_kernel(const ScanArgs a, const SegArgs sg)
+{
+    FwdRaw raw;
+    chunk_fwd_body<false, true, false, false, true, false, false, true, false, false, true>(a, blockIdx.x, 0u, raw, FwdChain{}, sg);
+}
+__global__ __launch_bounds__(512) void chunk_fwd_varlen_seg_kernel(const ScanArgs a, const SegArgs sg)
+{
+    FwdRaw raw;
+    chunk_fwd_body<false, false, false, false, true, false, false, true, true, true, true>(a, blockIdx.x, 0u, raw, FwdChain{}, sg);
+}
+
 // Packed rows under a per-tensor reversal map (a.rev_n, indexed by the sequence): general token addressing from the sequence's first token --
 // scan position p < rev_n[b] of a tensor named in a.rev_mask is token tok_off[b] + rev_n[b] - 1 - p.  Kernels of their own again: the
 // plain packed instantiations above keep their instruction streams.
@@ -1016,6 +1059,34 @@ hipError_t launch_chunk_fwd_snap(const ScanArgs& a_, hipStream_t st)
     static LdsAttrOnce attr;
     if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_snap_kernel), lds)) return e;
     hipLaunchKernelGGL(chunk_fwd_varlen_snap_kernel, dim3(a.B * a.H), dim3(512), lds, st, a);
+    return hipGetLastError();
+}
+
+// ... over the item table of a split call (wkv6_scan.h: SegArgs; a.B = the number of table entries this launch covers, a.lens / a.tok_off per
+// item).  state_only: the items' own contributions from a zero state into a.s_out (fp32 [a.B,H,N,N]) and a.dsum, nothing else; otherwise the
+// forward per item with the slot and snapshot rules of launch_chunk_fwd_snap.
+hipError_t launch_chunk_fwd_seg(const ScanArgs& a_, const SegArgs& sg, bool state_only, hipStream_t st)
+{
+    if (!offsets_fit(a_)) return hipErrorInvalidValue;
+    if (!a_.tok_off || !a_.ck_off || !a_.lens || a_.order || a_.wkind != 2 || !a_.state_f32) return hipErrorInvalidValue;
+    if (!sg.n || !sg.seq || !sg.pos || !sg.seq_lens || a_.len_hi != 0) return hipErrorInvalidValue;
+    if (state_only ? (a_.s0 || !a_.s_out || !a_.dsum || a_.y) : (!sg.sin || !slots_ok(a_) || !snap_ok(a_) || a_.dsum)) return hipErrorInvalidValue;
+    ScanArgs t = a_;
+    t.dsum = nullptr;
+    if (!varlen_fwd_plain(t) || a_.rev_n || a_.ckpt) return hipErrorNotSupported;
+    ScanArgs a = a_;
+    a.split = 0;
+    a.clk = nullptr; a.clk_slots = 0;
+    attach_debug_buffer(a);
+    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
+    static LdsAttrOnce attr_state, attr_fwd;
+    if (state_only) {
+        if (hipError_t e = attr_state.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_seg_state_kernel), lds)) return e;
+        hipLaunchKernelGGL(chunk_fwd_varlen_seg_state_kernel, dim3(a.B * a.H), dim3(512), lds, st, a, sg);
+    } else {
+        if (hipError_t e = attr_fwd.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_seg_kernel), lds)) return e;
+        hipLaunchKernelGGL(chunk_fwd_varlen_seg_kernel, dim3(a.B * a.H), dim3(512), lds, st, a, sg);
+    }
     return hipGetLastError();
 }
 

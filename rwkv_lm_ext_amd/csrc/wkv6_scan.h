@@ -121,6 +121,21 @@ struct ScanArgs {
     int n_snap;
 };
 
+// Long sequences cut over T (rwkv6_forward_varlen_split_bf16: the SEG instantiations of the packed forward take this beside their ScanArgs --
+// an argument block of its own, so that ScanArgs and with it every other kernel's kernarg layout stay as they are).  Row b of the ScanArgs is
+// ITEM b of a table the API's preparation kernel writes in dispatch order: a.lens / a.tok_off are per item (a.order is null, a.ck_off any
+// array of as many ints), a.B is the number of table entries the launch covers; item b covers tokens [pos[b], pos[b] + a.lens[b]) of sequence
+// seq[b], whose clamped length is seq_lens[seq[b]].  a.state_slot, a.state_slot_out and a.cu_snap stay indexed by the SEQUENCE.  An item that
+// is not its sequence's only one starts from sin[b] (fp32 [a.B,H,N,N], the chaining kernel's entry states) instead of the pool; only a
+// sequence's last item stores the final state.  n[0] items exist: workgroups past them return before anything else.
+struct SegArgs {
+    const int* n;
+    const int* seq;
+    const int* pos;
+    const int* seq_lens;
+    const float* sin;
+};
+
 // Shortest sequence the stateful inference calls (rwkv6_cuda_forward_bf16, rwkv6_forward_varlen_bf16) hand to the chunked kernel; shorter
 // ones (decode steps) take the exact scan
 constexpr int INFER_CHUNK_MIN_T = 32;
@@ -252,6 +267,8 @@ inline bool snap_ok(const ScanArgs& a)
 }
 hipError_t launch_scan_fwd_snap(const ScanArgs& a, int io, hipStream_t st);
 hipError_t launch_chunk_fwd_snap(const ScanArgs& a, hipStream_t st);
+// ... over the item table of a split call (SegArgs): the state pass of the items that have a successor, or the forward per item
+hipError_t launch_chunk_fwd_seg(const ScanArgs& a, const SegArgs& sg, bool state_only, hipStream_t st);
 hipError_t launch_chunk_state_pass(const ScanArgs& a, hipStream_t st);   // state recurrence only (s_out, ckpt, dsum)
 // In-run clock probe (wkv6_set_clock_ring, wkv6_api.hip): where launch number n of kind (0: chunked forward, 1: chunked backward) stamps,
 // or null; takes the launch's place in the ring (host side, one atomic increment per launch)

@@ -141,12 +141,13 @@ def _keep_snap_tokens(shift_pool, snap, x, cu_seqlens, max_seqlen=None):
     shift_pool.copy_(torch.cat((shift_pool, shift_pool.new_zeros(1, shift_pool.shape[1]))).index_copy_(0, dest, rows)[:n])
 
 
-def tmix_forward_packed(tm, x, cu_seqlens, max_seqlen, shift_pool, wkv_pool, slots, out_slots=None, snap=None):
+def tmix_forward_packed(tm, x, cu_seqlens, max_seqlen, shift_pool, wkv_pool, slots, out_slots=None, snap=None, seg_len=0):
     """tmix_forward_infctx for every sequence of a packed batch x [1,total_T,C] in one pass (a callers.Tmix_x060 `tm`): the token shift
     starts from shift_pool[slots[s]], the operator (wkv.RUN_RWKV_6_VARLEN) from wkv_pool[slots[s]]; both pools are updated in place.
     out_slots (int32 [n_seq]): what the sequences leave goes to these slots of both pools instead, slots keeps its contents.
     snap = (snap_every, cu_snap, snap_slots): the state after every snap_every tokens is kept as well -- the WKV state and the token in
-    front of the next one land in the same slot number snap_slots[cu_snap[s] + j] of their pools."""
+    front of the next one land in the same slot number snap_slots[cu_snap[s] + j] of their pools.
+    seg_len (0: off): handed to the operator, which cuts sequences longer than that over T; the token shift has no recurrence to cut."""
     from .wkv import RUN_RWKV_6_VARLEN
     B, T, C = x.size()
     assert B == 1, "a packed batch is [1,total_T,C]"
@@ -154,7 +155,7 @@ def tmix_forward_packed(tm, x, cu_seqlens, max_seqlen, shift_pool, wkv_pool, slo
     u = tm.time_faaaa.to(r.dtype).contiguous()
     snap_every, cu_snap, snap_slots = snap if snap is not None else (0, None, None)
     y, _ = RUN_RWKV_6_VARLEN(T, C, tm.n_head, wkv_pool, slots, *(t.contiguous() for t in (r, k, v, w.to(r.dtype))), u, cu_seqlens, max_seqlen,
-                             state_slot_out=out_slots, snap_every=snap_every, cu_snap=cu_snap, snap_slot=snap_slots)
+                             state_slot_out=out_slots, snap_every=snap_every, cu_snap=cu_snap, snap_slot=snap_slots, seg_len=seg_len)
     out = tm.jit_func_2(y, g)
     _keep_last_tokens(shift_pool, slots if out_slots is None else out_slots, x[0], cu_seqlens, max_seqlen)
     if snap is not None and snap_every > 0:

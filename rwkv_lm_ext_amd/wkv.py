@@ -483,11 +483,12 @@ class RWKV_6_VARLEN(torch.autograd.Function):
     state in slot state_slot[s] (int32 [n_seq] on the device; None: slot s) of the caller's pool state_pool [n_slots,H,N,N], which is
     updated in place and returned.  A slot outside the pool means no state: zero in, nothing out.  w is the raw decay parameter.
     state_slot_out / snap_every, cu_snap, snap_slot: a separate slot for the final state and state snapshots every snap_every tokens
-    (wkv6_op.rwkv6.forward_varlen_*)."""
+    (wkv6_op.rwkv6.forward_varlen_*).  seg_len (bf16 only; 0: off): sequences longer than seg_len tokens are cut into segments that run as
+    workgroups of their own (wkv6_op.rwkv6.forward_varlen_bf16)."""
 
     @staticmethod
     def forward(ctx, total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen, state_slot_out=None, snap_every=0,
-                cu_snap=None, snap_slot=None):
+                cu_snap=None, snap_slot=None, seg_len=0):
         with torch.no_grad():
             assert HEAD_SIZE == C // H
             assert state_pool.dtype == torch.float32
@@ -501,12 +502,14 @@ class RWKV_6_VARLEN(torch.autograd.Function):
                   torch.float16: wkv6_op.rwkv6.forward_varlen_fp16}.get(r.dtype)
             if fn is None:
                 raise RuntimeError(f"unsupported dtype {r.dtype}")
+            if seg_len != 0 and r.dtype != torch.bfloat16:
+                raise RuntimeError(f"seg_len is a bf16 option, got {r.dtype}")
             fn(total_T, C, H, state_pool, state_slot, r, k, v, eew, u, y, cu_seqlens, max_seqlen, state_slot_out=state_slot_out,
-               snap_every=snap_every, cu_snap=cu_snap, snap_slot=snap_slot)
+               snap_every=snap_every, cu_snap=cu_snap, snap_slot=snap_slot, **(dict(seg_len=seg_len) if seg_len != 0 else {}))
             return y.view(shape), state_pool
 
 
 def RUN_RWKV_6_VARLEN(total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen, state_slot_out=None, snap_every=0,
-                      cu_snap=None, snap_slot=None):
+                      cu_snap=None, snap_slot=None, seg_len=0):
     return RWKV_6_VARLEN.apply(total_T, C, H, state_pool, state_slot, r, k, v, w, u, cu_seqlens, max_seqlen, state_slot_out, snap_every,
-                               cu_snap, snap_slot)
+                               cu_snap, snap_slot, seg_len)

@@ -196,14 +196,17 @@ class _Rwkv6:
     # ---- packed batches with a state-slot pool (include/wkv6_amd.h: rwkv6_forward_varlen_*) ----
     @staticmethod
     def _call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, io,
-                     state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None, force_snap=False):
+                     state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None, force_snap=False, seg_len=0, force_split=False):
         """Every sequence of the packed [total_T,C] tensors (rows cu_seqlens[s] .. cu_seqlens[s+1]-1) from the state in slot state_slot[s]
         (None: slot s) of state_pool fp32 [n_slots,H,N,N], which is updated in place; y is written, rows outside every sequence as +0.
         w is the fp32 decay.  algo="scan" forces the exact scan kernel; ws: a new_rwkv6_varlen_workspace() buffer (graph capture).
         state_slot_out (int32 [n_seq]): the slot that takes the final state of sequence s instead of its source slot.  snap_every (a
         multiple of 64) with cu_snap (int32 [n_seq + 1]) and snap_slot (int32 [n_snap]): the state after the first (j + 1) * snap_every
         tokens of sequence s goes to slot snap_slot[cu_snap[s] + j] as well (include/wkv6_amd.h: rwkv6_forward_varlen_snap_*).  With all
-        four at their defaults the plain entry point is called (force_snap: the snap entry point all the same)."""
+        four at their defaults the plain entry point is called (force_snap: the snap entry point all the same).
+        seg_len (0, or a multiple of 64; bf16 on the chunked route only): every sequence longer than seg_len tokens is cut at multiples of
+        seg_len and served by one workgroup per (segment, head) (include/wkv6_amd.h: rwkv6_forward_varlen_split_bf16); ws is then a
+        new_rwkv6_varlen_split_workspace() buffer.  seg_len > 0 or force_split: the split entry point."""
         tc = (total_T, C)
         named = dict(state_pool=(state_pool, None, torch.float32), r=(r, tc, io), k=(k, tc, io), v=(v, tc, io),
                      w=(w, tc, torch.float32), u=(u, (H, HEAD_SIZE), io), y=(y, tc, io))
@@ -236,6 +239,14 @@ class _Rwkv6:
                     and (shape is None or tuple(t.shape) == shape) and t.device == r.device):
                 raise RuntimeError(f"{name} must be a contiguous int32 {what} tensor on the device of r")
 
+        if not isinstance(seg_len, int) or isinstance(seg_len, bool) or seg_len < 0 or seg_len % 64 != 0:
+            raise RuntimeError(f"seg_len must be 0 or a multiple of 64, got {seg_len!r}")
+        if seg_len > 0 and algo == "scan":
+            raise RuntimeError("seg_len > 0 cuts sequences on the chunked route only: not with algo='scan'")
+        if seg_len > 0 and io != torch.bfloat16:
+            raise RuntimeError(f"seg_len > 0 is a bf16 call, got {io}")
+        split = force_split or seg_len > 0
+        force_snap = force_snap or split
         snap = force_snap or not (state_slot_out is None and isinstance(snap_every, int) and snap_every == 0 and cu_snap is None and snap_slot is None)
         if snap:
             if not isinstance(snap_every, int) or snap_every < 0 or snap_every % 64 != 0:
@@ -254,7 +265,10 @@ class _Rwkv6:
                 _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _ptr(ws), 0 if ws is None else ws.numel(),
                 _lib.ALGO_SCAN if algo == "scan" else 0)
         with torch.cuda.device(dev):
-            if snap:
+            if split:
+                rc = lib.rwkv6_forward_varlen_split_bf16(*base, _stream_ptr(), _ptr(state_slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slot),
+                                                         0 if snap_slot is None else snap_slot.numel(), seg_len)
+            elif snap:
                 fn = {torch.bfloat16: lib.rwkv6_forward_varlen_snap_bf16, torch.float16: lib.rwkv6_forward_varlen_snap_fp16,
                       torch.float32: lib.rwkv6_forward_varlen_snap_fp32}[io]
                 rc = fn(*base, _stream_ptr(), _ptr(state_slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slot),
@@ -267,9 +281,16 @@ class _Rwkv6:
 
     @staticmethod
     def forward_varlen_bf16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None,
-                            state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None):
+                            state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None, seg_len=0):
         _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.bfloat16,
-                            state_slot_out, snap_every, cu_snap, snap_slot)
+                            state_slot_out, snap_every, cu_snap, snap_slot, seg_len=seg_len)
+
+    @staticmethod
+    def forward_varlen_split_bf16(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
+                                  cu_snap, snap_slot, seg_len, ws=None):
+        """torch.ops.rwkv6.forward_varlen_split_bf16: always the split entry point of the library, seg_len = 0 included."""
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, ws, torch.bfloat16,
+                            state_slot_out, snap_every, cu_snap, snap_slot, seg_len=seg_len, force_split=True)
 
     @staticmethod
     def forward_varlen_snap_bf16(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
@@ -459,6 +480,15 @@ def new_rwkv6_varlen_workspace(n_seq, device):
     n = _lib.load().rwkv6_varlen_workspace_bytes(n_seq)
     if n == 0:
         raise RuntimeError(f"bad n_seq {n_seq}")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def new_rwkv6_varlen_split_workspace(total_T, n_seq, seg_len, C, H, device):
+    """Workspace of rwkv6.forward_varlen_bf16(..., seg_len=) / forward_varlen_split_bf16: the prepared int arrays, the item table and the
+    per-item states of the cut (a caller that replays graphs owns it).  Sized from the host-side bound, no device data needed."""
+    n = _lib.load().rwkv6_varlen_split_workspace_bytes(total_T, n_seq, seg_len, C, H)
+    if n == 0:
+        raise RuntimeError(f"bad packed shape: total_T {total_T}, n_seq {n_seq}, seg_len {seg_len}, C {C}, H {H}")
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
@@ -1048,6 +1078,11 @@ def _register():
                          "Tensor v, Tensor w, Tensor u, Tensor(a!) y, Tensor cu_seqlens, int max_seqlen, int snap_every, Tensor? cu_snap, "
                          "Tensor? snap_slot) -> ()")
         rv.impl(name, getattr(_Rwkv6, name), "CUDA")
+    # ... and with the sequences longer than seg_len tokens cut into segments (bf16 only)
+    rv.define("forward_varlen_split_bf16(int total_T, int C, int H, Tensor(s!) state_pool, Tensor? state_slot, Tensor? state_slot_out, Tensor r, "
+              "Tensor k, Tensor v, Tensor w, Tensor u, Tensor(a!) y, Tensor cu_seqlens, int max_seqlen, int snap_every, Tensor? cu_snap, "
+              "Tensor? snap_slot, int seg_len) -> ()")
+    rv.impl("forward_varlen_split_bf16", _Rwkv6.forward_varlen_split_bf16, "CUDA")
     libs.append(rv)
     w5 = torch.library.Library("wkv5", "DEF")           # TORCH_LIBRARY(wkv5, m), cuda/wkv5_op.cpp:19-22
     w5.define("forward(int B, int T, int C, int H, Tensor r, Tensor k, Tensor v, Tensor w, Tensor u, Tensor(a!) y) -> ()")
