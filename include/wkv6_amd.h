@@ -417,6 +417,42 @@ int wkv6_ddlerp_varlen_rev_forward(long total_T, int n_seq, int C, int NS, const
 int wkv6_ddlerp_varlen_rev_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
                                     const void* m, const void* maa, const int* rev_n, const void* dout, void* dx, void* dm,
                                     float* dmaa_part, int nparts, void* stream);
+/* ---- the token-shift state of a serving loop as a device-side slot pool (bf16, forward only), beside the WKV state pool of
+ * rwkv6_forward_varlen_*: shift_pool is bf16 [n_slots,C], one pool per sub-layer; row p is the last token slot p's sequence was served.
+ *
+ * wkv6_ddlerp_slots_forward: wkv6_ddlerp_varlen_forward, except that the token in front of sequence s is row slot[s] of shift_pool instead
+ * of row s of a gathered shifted0.  The slot is judged on the device before an address is formed: a slot outside [0, n_slots) means a zero
+ * token.  slot (int32 [n_seq] on the device, never read by the host) == NULL: slot = sequence index, which needs n_slots >= n_seq
+ * (WKV6_EINVAL otherwise).  Any number of sequences may name one slot; the pool is only read.  Which row opens which sequence is the
+ * rule of the varlen call (the last sequence whose boundary is the row), so an empty sequence never reads its slot.  Same (NS, m) pairs,
+ * same arithmetic: results are bit-identical to wkv6_ddlerp_varlen_forward(shifted0 = the gathered rows).
+ *
+ * wkv6_shift_keep: one launch that stores what the batch leaves, writing only the rows that change.  With
+ *   a_s = clamp(cu_seqlens[s], 0, total_T), b_s = clamp(cu_seqlens[s+1], 0, total_T), len_s = min(max(b_s - a_s, 0), max_seqlen):
+ *   - if len_s > 0 and slot_out[s] lies in the pool, row a_s + len_s - 1 of x goes to shift_pool[slot_out[s]] (slot_out == NULL: the
+ *     sequence index, n_slots >= n_seq as above);
+ *   - snap_every > 0: with cu_snap clamped into [0, n_snap] and m_s = min(len_s / snap_every, max(cu_snap[s+1] - cu_snap[s], 0)), row
+ *     a_s + (j + 1) * snap_every - 1 goes to shift_pool[snap_slot[cu_snap[s] + j]] for every j < m_s whose slot lies in the pool -- the
+ *     clamps and the m_s of rwkv6_forward_varlen_snap_*, so that a snapshot's shift token and its WKV state land under one slot number.
+ *     (No multiple-of-64 rule here: any snap_every >= 0.  snap_every == 0 or n_snap == 0: no snapshots, cu_snap / snap_slot may be NULL.)
+ * One workgroup per candidate row (n_seq + n_snap of them; a snapshot entry finds its sequence by bisection in cu_snap); dead candidates
+ * return before any access.  Every index is clamped or judged before use: garbage in any int array touches no memory outside x and the
+ * pool.  The pool is not read; rows that no live candidate names keep their bits, and rows are copied as bits.  Two live writers of one
+ * row are out of contract (one of them wins; the call stays memory-safe).
+ *
+ * The two are separate launches on purpose: with slot_out == slot (a decode loop's in-place use) the workgroup of a sequence's first
+ * token reads the row that the workgroup of its last token writes; stream order between the launches makes that defined.
+ *
+ * Refused before any launch: WKV6_EINVAL -- C (as every kernel here: a multiple of 64, at most 4096), total_T, n_seq, n_slots or
+ * max_seqlen < 1, snap_every < 0, n_snap < 0, x / out / shift_pool not 8-byte aligned, x (shift_keep) or out (ddlerp_slots) overlapping
+ * the pool; WKV6_ENULL -- a NULL tensor, cu_seqlens or pool, cu_snap or snap_slot NULL while snap_every > 0 and n_snap > 0;
+ * WKV6_EUNSUPPORTED -- total_T > INT_MAX, an (NS, m) pair the ddlerp does not have. */
+int wkv6_ddlerp_slots_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x,
+                              const void* shift_pool, int n_slots, const int* slot,
+                              const void* m, const void* maa, void* out, void* stream);
+int wkv6_shift_keep(long total_T, int n_seq, int max_seqlen, int C, const int* cu_seqlens, const void* x,
+                    void* shift_pool, int n_slots, const int* slot_out,
+                    int snap_every, const int* cu_snap, const int* snap_slot, int n_snap, void* stream);
 /* gn_gate (src/model.py:462-468): out = GroupNorm_H(y; gamma, beta, eps) * g on rows of C = 64 H channels (nn.GroupNorm(H, C)
  * applied to [rows, C]); stats fp32 [rows,H,2] (mean, rstd) is written for the backward (may be NULL in inference).
  * backward: dy, dg [rows,C]; dgamma_part, dbeta_part fp32 [nparts,C] partial sums. */

@@ -135,7 +135,7 @@ class Tmix_x060(nn.Module):
                     and C % 64 == 0 and C <= 4096)
         return self.fused
 
-    def jit_func(self, x, shifted=None, rev_n=None, cu_seqlens=None, shifted0=None):
+    def jit_func(self, x, shifted=None, rev_n=None, cu_seqlens=None, shifted0=None, shift_pool=None, slots=None):
         """Inputs of the WKV operator from the block input (src/model.py:435-459): every projection reads its own
         data-dependent blend of x_t and x_{t-1},  x + (x_{t-1} - x) * (maa_s + m_s),  where the five corrections m_s come
         from one shared low-rank pair (tanh(blend_x @ W1) -> per-stream W2).  Then r, k, v = Linear(blend), g = silu(Linear),
@@ -148,13 +148,27 @@ class Tmix_x060(nn.Module):
         `cu_seqlens` (int32 [n_seq + 1]): x is a packed variable-length batch [1,total_T,C]; the shift does not cross a sequence
         boundary (zero in front of every sequence); rev_n is then int32 [n_seq].
         `shifted0` (packed batches only, [n_seq,C]): the token in front of every sequence -- what a serving loop carried over from the
-        sequence's previous call -- instead of zero."""
+        sequence's previous call -- instead of zero.
+        `shift_pool` (bf16 [n_slots,C]) with `slots` (int32 [n_seq], None: the sequence index), instead of shifted0, on the packed fused
+        path without autograd: the token in front of sequence s is shift_pool[slots[s]] (zero for a slot outside the pool), fetched by the
+        kernel itself (mix_op.ddlerp_slots)."""
         B, T, C = x.size()
         if cu_seqlens is not None:
             assert B == 1 and shifted is None, "a packed batch is [1,total_T,C]; the carried tokens go in as shifted0 [n_seq,C]"
         else:
             assert shifted0 is None, "shifted0 belongs to a packed batch (cu_seqlens); a dense batch passes `shifted`"
-        if self._use_fused(x):
+        if shift_pool is not None:
+            assert cu_seqlens is not None and shifted0 is None and rev_n is None, \
+                "shift_pool / slots belong to a packed batch (cu_seqlens) and exclude shifted0 and rev_n"
+            if not self._use_fused(x):
+                raise RuntimeError("shift_pool / slots exist in the fused (HIP) path only; gather the rows and pass shifted0")
+            from . import mix_op
+            lead = mix_op.ddlerp_slots(x, self.time_maa_x.view(1, C), None, shift_pool, slots, cu_seqlens)[0]
+            low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
+            corr = torch.bmm(low, self.time_maa_w2).view(5, B, T, C)
+            xw, xk, xv, xr, xg = mix_op.ddlerp_slots(x, self._maa5(), corr, shift_pool, slots, cu_seqlens).unbind(0)
+        elif self._use_fused(x):
+            assert slots is None, "slots name rows of shift_pool"
             from . import mix_op
             first = None if shifted is None else shifted[:, 0].contiguous()
             if shifted0 is not None:
@@ -165,6 +179,7 @@ class Tmix_x060(nn.Module):
             xw, xk, xv, xr, xg = mix_op.ddlerp(x, self._maa5(), corr, first, rev_n, cu_seqlens=cu_seqlens).unbind(0)
         else:
             assert rev_n is None, "the reversed-stream shift exists in the fused (HIP) path only"
+            assert slots is None, "slots name rows of shift_pool"
             if cu_seqlens is not None:
                 prev = _packed_prev(x, cu_seqlens, shifted0)
             else:

@@ -10,6 +10,9 @@
 //           backward dr = dout kv s (1 - s), dkv = dout s.
 //   gn_gate (src/model.py:462-468):  out = GroupNorm_H(y) (.) g  -- per-head normalisation of the WKV output over its 64
 //           channels (nn.GroupNorm(H, C, eps) on [B*T, C]) fused with the gate multiply that feeds the output GEMM.
+//   ddlerp_slots / shift_keep (forward only, packed batches): the token-shift state of a serving loop as a slot pool [n_slots,C] -- the
+//           lerp with the token in front of a sequence fetched from the pool by slot number, and the one launch that stores what the batch
+//           leaves (last tokens, snapshot tokens), writing only the rows that change (include/wkv6_amd.h).
 // Forward and backward of both; parameter gradients (time_maa_*, ln_x.weight/bias) leave as per-workgroup fp32 partial rows
 // that the caller sums (deterministic, no atomics).
 //
@@ -40,6 +43,11 @@ struct LerpArgs {
     // then [n_seq,C], the token in front of each sequence's first one
     const int* cu;            // [n_seq + 1]
     int n_seq;
+};
+// ddlerp_fwd_slots_kernel (forward, packed): shifted0 is a pool [n_slots,C] and the token in front of sequence s its row slot[s]
+struct SlotLerpArgs : LerpArgs {
+    const int* slot;          // [n_seq] or null (slot = sequence index)
+    int n_slots;
 };
 
 // Packed batches: the sequence that holds row r = the last s with cu[s] <= r (-1: none), by bisection in cu_seqlens -- workgroup-uniform
@@ -95,6 +103,35 @@ __global__ void ddlerp_fwd_kernel(const LerpArgs a)
         else if (a.shifted0) ld4(a.shifted0 + (long)b * a.C + c, xp);
     }
     const long plane = (long)a.B * a.T * a.C;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float maa[4], m[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
+        ld4(a.maa + (long)s * a.C + c, maa);
+        if constexpr (HAS_M) ld4(a.m + s * plane + row * a.C + c, m);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = fmaf(xp[q] - x[q], maa[q] + m[q], x[q]);
+        io4<bf16_t>::store(a.out + s * plane + row * a.C + c, o);
+    }
+}
+
+// The VARLEN forward with the token in front of a sequence taken from a slot pool (wkv6_ddlerp_slots_forward): the same loads of x, the same
+// lerp.  A kernel of its own rather than one more flag of ddlerp_fwd_kernel: the kernels of the training path keep their names, their
+// argument block and their instruction streams.
+template <int NS, bool HAS_M>
+__global__ void ddlerp_fwd_slots_kernel(const SlotLerpArgs a)
+{
+    const long row = blockIdx.x;
+    const int c = 4 * threadIdx.x;
+    float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f};
+    ld4(a.x + row * a.C + c, x);
+    const int sq = seq_of_row(a.cu, a.n_seq, row);
+    const bool first = sq >= 0 && (long)a.cu[sq] == row;
+    if (!first) { if (row > 0) ld4(a.x + (row - 1) * a.C + c, xp); }
+    else {                                               // the slot is judged before an address is formed: outside the pool = zero token
+        const int sl = a.slot ? a.slot[sq] : sq;
+        if (sl >= 0 && sl < a.n_slots) ld4(a.shifted0 + (long)sl * a.C + c, xp);
+    }
+    const long plane = (long)a.T * a.C;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         float maa[4], m[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
@@ -466,6 +503,58 @@ template <bool BWD> __global__ __launch_bounds__(256) void sigmul_kernel(const F
         }
     }
 }
+// wkv6_shift_keep: what a packed batch leaves in a token-shift slot pool.  One workgroup per candidate row: workgroup i < n_seq carries the
+// last served token of sequence i to slot_out[i], workgroup n_seq + e carries snapshot entry e (its sequence by bisection in the clamped
+// cu_snap) to snap_slot[e].  Every index is clamped or judged before it forms an address; a dead candidate leaves before any access to x or
+// the pool, which is never read.  Rows are copied as bits (8 bytes per thread), not through fp32: a NaN keeps its payload.
+struct KeepArgs {
+    int total_T, n_seq, max_seqlen, C, n_slots, snap_every, n_snap;
+    const int* cu;            // [n_seq + 1]
+    const bf16_t* x;          // [total_T,C]
+    bf16_t* pool;             // [n_slots,C]
+    const int* slot_out;      // [n_seq] or null (slot = sequence index)
+    const int* cu_snap;       // [n_seq + 1]
+    const int* snap_slot;     // [n_snap]
+};
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+__global__ void shift_keep_kernel(const KeepArgs a)
+{
+    const int i = blockIdx.x;
+    const bool last = i < a.n_seq;
+    const int e = i - a.n_seq;                           // snapshot entry (!last): 0 <= e < n_snap by the grid
+    int s = i;
+    if (!last) {                                         // the last s < n_seq with cu_snap[s] <= e
+        int lo = 0, hi = a.n_seq;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (clampi(a.cu_snap[mid], 0, a.n_snap) <= e) lo = mid + 1;
+            else hi = mid;
+        }
+        s = lo - 1;
+        if (s < 0) return;
+    }
+    const int a0 = clampi(a.cu[s], 0, a.total_T), b0 = clampi(a.cu[s + 1], 0, a.total_T);
+    const int len = min(max(b0 - a0, 0), a.max_seqlen);
+    if (len <= 0) return;
+    int row, dst;
+    if (last) {
+        row = a0 + len - 1;
+        dst = a.slot_out ? a.slot_out[s] : s;
+    } else {
+        const int c0 = clampi(a.cu_snap[s], 0, a.n_snap), c1 = clampi(a.cu_snap[s + 1], 0, a.n_snap);
+        const int j = e - c0;                            // >= 0 by the bisection
+        if (j >= min(len / a.snap_every, max(c1 - c0, 0))) return;
+        row = a0 + (j + 1) * a.snap_every - 1;           // (j + 1) snap_every <= len: inside the sequence, no overflow
+        dst = a.snap_slot[e];
+    }
+    if (dst < 0 || dst >= a.n_slots) return;
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    const int c = 4 * threadIdx.x;
+    *(v2u*)(a.pool + (long)dst * a.C + c) = *(const v2u*)(a.x + (long)row * a.C + c);
+}
+
 template <typename K> int launch_flat(K kernel, const FlatArgs& a, hipStream_t st)
 {
     const long blocks = (a.n8 + 255) / 256;
@@ -506,6 +595,24 @@ int dispatch_lerp(const LerpArgs& a, bool bwd, hipStream_t st)
     else return WKV6_EUNSUPPORTED;
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? WKV6_OK : (int)e;
+}
+
+int dispatch_slot_lerp(const SlotLerpArgs& a, hipStream_t st)
+{
+    const dim3 grid((unsigned)a.T), block(a.C / 4);
+    if (a.NS == 1 && !a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<1, false>), grid, block, 0, st, a);
+    else if (a.NS == 5 && a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<5, true>), grid, block, 0, st, a);
+    else if (a.NS == 1 && a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<1, true>), grid, block, 0, st, a);
+    else if (a.NS == 2 && !a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<2, false>), grid, block, 0, st, a);
+    else return WKV6_EUNSUPPORTED;
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WKV6_OK : (int)e;
+}
+
+bool overlap(const void* p, size_t pn, const void* q, size_t qn)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qn && b < a + pn;
 }
 
 }  // namespace
@@ -581,6 +688,48 @@ int wkv6_ddlerp_varlen_backward(long total_T, int n_seq, int C, int NS, const in
     a.cu = cu_seqlens; a.n_seq = n_seq;
     a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
     return dispatch_lerp(a, true, (hipStream_t)stream);
+}
+
+int wkv6_ddlerp_slots_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shift_pool,
+                              int n_slots, const int* slot, const void* m, const void* maa, void* out, void* stream)
+{
+    if (total_T < 1 || n_seq < 1 || n_slots < 1) return WKV6_EINVAL;
+    if (int rc = check_rows(total_T, C)) return rc;
+    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;          // cu_seqlens is int32
+    if (!slot && n_slots < n_seq) return WKV6_EINVAL;             // slot = sequence index: the pool must hold n_seq slots
+    if (!cu_seqlens || !x || !maa || !out || !shift_pool) return WKV6_ENULL;
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)shift_pool) & 7) return WKV6_EINVAL;
+    if (overlap(out, (size_t)NS * total_T * C * 2, shift_pool, (size_t)n_slots * C * 2)) return WKV6_EINVAL;
+    SlotLerpArgs a = {};
+    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
+    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shift_pool; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    a.cu = cu_seqlens; a.n_seq = n_seq; a.slot = slot; a.n_slots = n_slots;
+    a.out = (bf16_t*)out;
+    return dispatch_slot_lerp(a, (hipStream_t)stream);
+}
+
+int wkv6_shift_keep(long total_T, int n_seq, int max_seqlen, int C, const int* cu_seqlens, const void* x, void* shift_pool, int n_slots,
+                    const int* slot_out, int snap_every, const int* cu_snap, const int* snap_slot, int n_snap, void* stream)
+{
+    if (total_T < 1 || n_seq < 1 || n_slots < 1 || max_seqlen < 1 || snap_every < 0 || n_snap < 0) return WKV6_EINVAL;
+    if (int rc = check_rows(total_T, C)) return rc;
+    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;          // cu_seqlens is int32
+    if (!slot_out && n_slots < n_seq) return WKV6_EINVAL;
+    if (!cu_seqlens || !x || !shift_pool) return WKV6_ENULL;
+    const bool snaps = snap_every > 0 && n_snap > 0;
+    if (snaps && (!cu_snap || !snap_slot)) return WKV6_ENULL;
+    if (((uintptr_t)x | (uintptr_t)shift_pool) & 7) return WKV6_EINVAL;
+    if (overlap(x, (size_t)total_T * C * 2, shift_pool, (size_t)n_slots * C * 2)) return WKV6_EINVAL;
+    const long grid = (long)n_seq + (snaps ? n_snap : 0);
+    if (grid > 0x7fffffffL) return WKV6_EUNSUPPORTED;
+    KeepArgs a = {};
+    a.total_T = (int)total_T; a.n_seq = n_seq; a.max_seqlen = max_seqlen; a.C = C; a.n_slots = n_slots;
+    a.snap_every = snaps ? snap_every : 0; a.n_snap = snaps ? n_snap : 0;
+    a.cu = cu_seqlens; a.x = (const bf16_t*)x; a.pool = (bf16_t*)shift_pool; a.slot_out = slot_out;
+    a.cu_snap = cu_snap; a.snap_slot = snap_slot;
+    hipLaunchKernelGGL(shift_keep_kernel, dim3((unsigned)grid), dim3(C / 4), 0, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? WKV6_OK : (int)e;
 }
 
 // rev_n == null: the plain packed shift

@@ -141,34 +141,72 @@ def _keep_snap_tokens(shift_pool, snap, x, cu_seqlens, max_seqlen=None):
     shift_pool.copy_(torch.cat((shift_pool, shift_pool.new_zeros(1, shift_pool.shape[1]))).index_copy_(0, dest, rows)[:n])
 
 
-def tmix_forward_packed(tm, x, cu_seqlens, max_seqlen, shift_pool, wkv_pool, slots, out_slots=None, snap=None, seg_len=0):
+def _pool_kernels(mod, x, shift_pool, pool_kernels, ints):
+    """Whether the HIP slot-pool kernels (mix_op.ddlerp_slots, mix_op.shift_keep) serve this call.  pool_kernels None: when the module's
+    fused path applies, the pool is contiguous bf16 on x's device and no gradient is required; False: never (the eager code, which also
+    serves fp16 / fp32 and autograd); True: they must, or this raises.  `ints`: the call's int arrays; the kernels take them as contiguous
+    int32 on x's device, the eager code casts whatever it gets, so anything else stays with it (under True, mix_op refuses it)."""
+    if pool_kernels is False:
+        return False
+    if pool_kernels is None and not all(t is None or (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous()
+                                                      and t.device == x.device) for t in ints):
+        return False
+    why = None
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and mod._use_fused(x)):
+        why = "the module's fused (HIP) path does not apply to x"
+    elif not (shift_pool.dtype == torch.bfloat16 and shift_pool.dim() == 2 and shift_pool.is_contiguous() and shift_pool.device == x.device):
+        why = "the shift pool must be a contiguous bf16 [n_slots,C] tensor on the device of x"
+    elif torch.is_grad_enabled() and (x.requires_grad or shift_pool.requires_grad or any(p.requires_grad for p in mod.parameters())):
+        why = "a gradient is required (the slot-pool kernels are forward only: call under torch.no_grad())"
+    if why is not None and pool_kernels:
+        raise RuntimeError("pool_kernels=True: " + why)
+    return why is None
+
+
+def tmix_forward_packed(tm, x, cu_seqlens, max_seqlen, shift_pool, wkv_pool, slots, out_slots=None, snap=None, seg_len=0, pool_kernels=None):
     """tmix_forward_infctx for every sequence of a packed batch x [1,total_T,C] in one pass (a callers.Tmix_x060 `tm`): the token shift
     starts from shift_pool[slots[s]], the operator (wkv.RUN_RWKV_6_VARLEN) from wkv_pool[slots[s]]; both pools are updated in place.
     out_slots (int32 [n_seq]): what the sequences leave goes to these slots of both pools instead, slots keeps its contents.
     snap = (snap_every, cu_snap, snap_slots): the state after every snap_every tokens is kept as well -- the WKV state and the token in
     front of the next one land in the same slot number snap_slots[cu_snap[s] + j] of their pools.
-    seg_len (0: off): handed to the operator, which cuts sequences longer than that over T; the token shift has no recurrence to cut."""
+    seg_len (0: off): handed to the operator, which cuts sequences longer than that over T; the token shift has no recurrence to cut.
+    pool_kernels (None: where they apply, see _pool_kernels): the shift pool is read inside the lerp kernels and written by one launch
+    that touches only the rows that change, instead of the eager gather / scatter over the whole pool; the results are bit-identical."""
     from .wkv import RUN_RWKV_6_VARLEN
     B, T, C = x.size()
     assert B == 1, "a packed batch is [1,total_T,C]"
-    r, k, v, g, w = tm.jit_func(x, cu_seqlens=cu_seqlens, shifted0=_carried_tokens(shift_pool, slots).to(x.dtype))
+    kernels = _pool_kernels(tm, x, shift_pool, pool_kernels, (cu_seqlens, slots, out_slots) + (tuple(snap[1:]) if snap is not None else ()))
+    if kernels:
+        r, k, v, g, w = tm.jit_func(x, cu_seqlens=cu_seqlens, shift_pool=shift_pool, slots=slots)
+    else:
+        r, k, v, g, w = tm.jit_func(x, cu_seqlens=cu_seqlens, shifted0=_carried_tokens(shift_pool, slots).to(x.dtype))
     u = tm.time_faaaa.to(r.dtype).contiguous()
     snap_every, cu_snap, snap_slots = snap if snap is not None else (0, None, None)
     y, _ = RUN_RWKV_6_VARLEN(T, C, tm.n_head, wkv_pool, slots, *(t.contiguous() for t in (r, k, v, w.to(r.dtype))), u, cu_seqlens, max_seqlen,
                              state_slot_out=out_slots, snap_every=snap_every, cu_snap=cu_snap, snap_slot=snap_slots, seg_len=seg_len)
     out = tm.jit_func_2(y, g)
+    if kernels:         # behind the lerps in stream order: with out_slots None they read the rows this writes
+        from . import mix_op
+        mix_op.shift_keep(x, cu_seqlens, int(max_seqlen), shift_pool, slots if out_slots is None else out_slots, snap)
+        return out
     _keep_last_tokens(shift_pool, slots if out_slots is None else out_slots, x[0], cu_seqlens, max_seqlen)
     if snap is not None and snap_every > 0:
         _keep_snap_tokens(shift_pool, snap, x[0], cu_seqlens, max_seqlen)
     return out
 
 
-def cmix_forward_packed(cm, x, cu_seqlens, shift_pool, slots, out_slots=None, snap=None):
+def cmix_forward_packed(cm, x, cu_seqlens, shift_pool, slots, out_slots=None, snap=None, pool_kernels=None):
     """cmix_forward_infctx for every sequence of a packed batch x [1,total_T,C] (a callers.CMix_x060 `cm`); shift_pool is this sub-layer's.
-    out_slots and snap as in tmix_forward_packed."""
+    out_slots, snap and pool_kernels as in tmix_forward_packed."""
     from .callers import _packed_prev
     B, T, C = x.size()
     assert B == 1, "a packed batch is [1,total_T,C]"
+    if _pool_kernels(cm, x, shift_pool, pool_kernels, (cu_seqlens, slots, out_slots) + (tuple(snap[1:]) if snap is not None else ())):
+        from . import mix_op
+        xk, xr = mix_op.ddlerp_slots(x, torch.cat([cm.time_maa_k, cm.time_maa_r], 0).view(2, -1), None, shift_pool, slots, cu_seqlens)
+        out = mix_op.sigmoid_mul(cm.receptance(xr), cm.value(mix_op.sqrelu(cm.key(xk))))
+        mix_op.shift_keep(x, cu_seqlens, T, shift_pool, slots if out_slots is None else out_slots, snap)      # no max_seqlen here: total_T
+        return out
     carried = _carried_tokens(shift_pool, slots).to(x.dtype)
     if cm._use_fused(x):
         from . import mix_op
@@ -182,3 +220,49 @@ def cmix_forward_packed(cm, x, cu_seqlens, shift_pool, slots, out_slots=None, sn
     if snap is not None and snap[0] > 0:
         _keep_snap_tokens(shift_pool, snap, x[0], cu_seqlens)
     return out
+
+
+# ---- the block-level serving step on a packed stateful batch
+@dataclass
+class PackedPools:
+    """Every layer's carried state of a serving loop, slot p of every pool belonging to one sequence: shift_att / shift_ffn [L,n_slots,C]
+    (the token in front of the sequence's next one, per sub-layer, activation dtype) and wkv fp32 [L,n_slots,H,64,64]."""
+    shift_att: torch.Tensor
+    shift_ffn: torch.Tensor
+    wkv: torch.Tensor
+
+    @staticmethod
+    def create(n_layer, n_slots, C, H, device, dtype):
+        head = C // H
+        return PackedPools(torch.zeros((n_layer, n_slots, C), device=device, dtype=dtype),
+                           torch.zeros((n_layer, n_slots, C), device=device, dtype=dtype),
+                           torch.zeros((n_layer, n_slots, H, head, head), device=device, dtype=torch.float32))
+
+
+def block_forward_packed(block, x, cu_seqlens, max_seqlen, pools, layer, slots, out_slots=None, snap=None, seg_len=0, pool_kernels=None):
+    """One RWKV-6 block (anything shaped like train_dp.Block: ln0 where there is one, ln1, att, ln2, ffn) on a packed stateful batch
+    x [1,total_T,C]: x + att(ln1 x), then + ffn(ln2 .), the sub-layers through tmix_forward_packed / cmix_forward_packed on slice
+    `layer` of the pools.  Nothing here reads a device array on the host."""
+    if getattr(block, "ln0", None) is not None:
+        x = block.ln0(x)
+    x = x + tmix_forward_packed(block.att, block.ln1(x), cu_seqlens, max_seqlen, pools.shift_att[layer], pools.wkv[layer], slots,
+                                out_slots=out_slots, snap=snap, seg_len=seg_len, pool_kernels=pool_kernels)
+    return x + cmix_forward_packed(block.ffn, block.ln2(x), cu_seqlens, pools.shift_ffn[layer], slots, out_slots=out_slots, snap=snap,
+                                   pool_kernels=pool_kernels)
+
+
+def step_packed(blocks, x, cu_seqlens, max_seqlen, pools, slots, out_slots=None, snap=None, seg_len=0, pool_kernels=None):
+    """block_forward_packed over a stack of blocks, block i on layer i of the pools."""
+    for layer, block in enumerate(blocks):
+        x = block_forward_packed(block, x, cu_seqlens, max_seqlen, pools, layer, slots, out_slots=out_slots, snap=snap, seg_len=seg_len,
+                                 pool_kernels=pool_kernels)
+    return x
+
+
+def last_token_rows(x, cu_seqlens, max_seqlen):
+    """[n_seq,C]: the last served token of every sequence of the packed bf16 batch x [1,total_T,C] (token min(len_s, max_seqlen) - 1), zeros
+    for an empty one -- the rows the head needs.  One mix_op.shift_keep launch into a zeroed buffer with identity slots."""
+    from . import mix_op
+    rows = torch.zeros((cu_seqlens.numel() - 1, x.shape[-1]), device=x.device, dtype=x.dtype)
+    mix_op.shift_keep(x, cu_seqlens, int(max_seqlen), rows, None)
+    return rows

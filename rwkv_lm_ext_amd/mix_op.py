@@ -202,6 +202,102 @@ def ddlerp(x, maa, m=None, shifted0=None, rev_n=None, cu_seqlens=None):
     return _DDLerp.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, rev_n)
 
 
+# ---- the token-shift state of a serving loop as a device-side slot pool (include/wkv6_amd.h: wkv6_ddlerp_slots_forward, wkv6_shift_keep);
+# inference only: no autograd.  Shapes and types are judged first, the device last (there is no CPU path).
+def _check_ints(t, shape, name):
+    """shape None: any 1-d length.  The device is judged by the caller, behind every shape."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous()
+            and (t.dim() == 1 if shape is None else tuple(t.shape) == shape)):
+        raise RuntimeError(f"{name} must be a contiguous int32 {'1-d' if shape is None else list(shape)} tensor on the device of x")
+
+
+def _check_packed(x, shift_pool, cu_seqlens):
+    """(total_T, C, n_seq, n_slots) of a packed bf16 batch x [1,total_T,C] (or [total_T,C]) and a bf16 slot pool [n_slots,C]."""
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16 and x.dim() in (2, 3)):
+        raise RuntimeError("x must be a bf16 tensor [1, total_T, C] (or [total_T, C])")
+    if x.dim() == 3 and x.shape[0] != 1:
+        raise RuntimeError("a packed batch is [1, total_T, C] (or [total_T, C])")
+    C = x.shape[-1]
+    if not (isinstance(shift_pool, torch.Tensor) and shift_pool.dtype == torch.bfloat16 and shift_pool.dim() == 2
+            and shift_pool.shape[1] == C and shift_pool.is_contiguous()):
+        raise RuntimeError(f"shift_pool must be a contiguous bf16 tensor [n_slots, C = {C}] (it is used in place, never copied)")
+    if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2):
+        raise RuntimeError("cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of x")
+    return x.numel() // C, C, cu_seqlens.numel() - 1, shift_pool.shape[0]
+
+
+def _check_gpu(x, shift_pool, cu_seqlens):
+    if not x.is_cuda:
+        raise RuntimeError("x must be on the GPU (the slot-pool kernels have no CPU path)")
+    if shift_pool.device != x.device or cu_seqlens.device != x.device:
+        raise RuntimeError("shift_pool and cu_seqlens must be on the device of x")
+
+
+def ddlerp_slots(x, maa, m, shift_pool, slots, cu_seqlens):
+    """ddlerp(x, maa, m, shifted0, cu_seqlens=cu_seqlens) with shifted0[s] = shift_pool[slots[s]] taken inside the kernel (zero where the
+    slot lies outside the pool): no gather, the pool [n_slots,C] is only read.  slots: int32 [n_seq] or None (slot = sequence index,
+    n_slots >= n_seq).  Inference only: raises when a gradient is required."""
+    total, C, n_seq, n_slots = _check_packed(x, shift_pool, cu_seqlens)
+    if not isinstance(maa, torch.Tensor) or maa.dtype != torch.bfloat16 or maa.numel() % C:
+        raise RuntimeError("maa must be a bf16 tensor [NS, C]")
+    maa = maa.reshape(-1, C).contiguous()
+    NS = maa.shape[0]
+    if m is not None and not (isinstance(m, torch.Tensor) and m.dtype == torch.bfloat16 and tuple(m.shape) == (NS,) + tuple(x.shape)):
+        raise RuntimeError(f"m must be a bf16 tensor {[NS] + list(x.shape)} or None")
+    if (NS, m is not None) not in ((1, False), (1, True), (5, True), (2, False)):
+        raise RuntimeError("ddlerp_slots: supported are (NS = 1, m or not), (NS = 5, m), (NS = 2, no m)")
+    if slots is None and n_slots < n_seq:
+        raise RuntimeError("slots = None means slot = sequence index: the pool must hold n_seq slots")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, maa, m, shift_pool)):
+        raise RuntimeError("ddlerp_slots has no backward: call it under torch.no_grad() (training uses ddlerp with shifted0)")
+    if slots is not None:
+        _check_ints(slots, (n_seq,), "slots")
+    _check_gpu(x, shift_pool, cu_seqlens)
+    if any(t is not None and t.device != x.device for t in (maa, m, slots)):
+        raise RuntimeError("maa, m and slots must be on the device of x")
+    x, m = x.contiguous(), None if m is None else m.contiguous()
+    out = torch.empty((NS,) + tuple(x.shape), device=x.device, dtype=x.dtype)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().wkv6_ddlerp_slots_forward(total, n_seq, C, NS, _ptr(cu_seqlens), _ptr(x), _ptr(shift_pool), n_slots, _ptr(slots),
+                                                   _ptr(m), _ptr(maa), _ptr(out), _stream_ptr())
+    _lib.check(rc, "ddlerp slots forward")
+    return out
+
+
+def shift_keep(x, cu_seqlens, max_seqlen, shift_pool, slot_out, snap=None):
+    """shift_pool[slot_out[s]] = the last served token of sequence s (token min(len_s, max_seqlen) - 1; empty sequences and slots outside
+    the pool write nothing), and with snap = (snap_every, cu_snap, snap_slots) also shift_pool[snap_slots[cu_snap[s] + j]] = token
+    (j + 1) * snap_every - 1 for every snapshot j the operator keeps.  One launch that writes only those rows of the pool, in place.
+    slot_out: int32 [n_seq] or None (slot = sequence index)."""
+    total, C, n_seq, n_slots = _check_packed(x, shift_pool, cu_seqlens)
+    if isinstance(max_seqlen, bool) or not isinstance(max_seqlen, int) or max_seqlen < 1:
+        raise RuntimeError("max_seqlen must be an int >= 1")
+    if slot_out is None and n_slots < n_seq:
+        raise RuntimeError("slot_out = None means slot = sequence index: the pool must hold n_seq slots")
+    snap_every, cu_snap, snap_slots = (0, None, None) if snap is None else snap
+    if isinstance(snap_every, bool) or not isinstance(snap_every, int) or snap_every < 0:
+        raise RuntimeError("snap_every must be an int >= 0")
+    if snap_every > 0:
+        _check_ints(cu_snap, (n_seq + 1,), "cu_snap")
+        _check_ints(snap_slots, None, "snap_slots")
+    else:
+        cu_snap = snap_slots = None
+    if slot_out is not None:
+        _check_ints(slot_out, (n_seq,), "slot_out")
+    if shift_pool.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("shift_keep writes the pool in place and has no backward")
+    _check_gpu(x, shift_pool, cu_seqlens)
+    for t, name in ((slot_out, "slot_out"), (cu_snap, "cu_snap"), (snap_slots, "snap_slots")):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{name} must be a contiguous int32 tensor on the device of x")
+    x, n_snap = x.contiguous(), 0 if snap_slots is None else snap_slots.numel()
+    with torch.cuda.device(x.device):
+        rc = _lib.load().wkv6_shift_keep(total, n_seq, min(max_seqlen, 0x7fffffff), C, _ptr(cu_seqlens), _ptr(x), _ptr(shift_pool), n_slots,
+                                         _ptr(slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slots), n_snap, _stream_ptr())
+    _lib.check(rc, "shift keep")
+
+
 def gn_gate_forward(y, g, gamma, beta, H, eps):
     """(out, stats): out = GroupNorm_H(y) * g on [rows, C]; stats fp32 [rows, H, 2] = mean, rstd (for gn_gate_backward)."""
     y, g, gamma, beta = _require(y, "y"), _require(g, "g"), _require(gamma, "gamma"), _require(beta, "beta")
