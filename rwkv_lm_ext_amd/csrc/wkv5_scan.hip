@@ -1,6 +1,6 @@
 // Exact-fp32 token-serial WKV5 (static decay) kernels for gfx950.  Design notes: wkv5_scan.h.
 #include "wkv5_scan.h"
-#include "wkv6_scan.h"                 // LdsAttrOnce
+#include "wkv6_scan.h"                 // launch<>
 
 namespace wkv6 {
 namespace {
@@ -498,12 +498,10 @@ constexpr size_t LDS_BWD_G = (2 * 4 * TB * ROW + 2 * TB * ROW + 2 * NW * TB * RO
 template <typename T> hipError_t launch_bwd(const Wkv5Args& a, hipStream_t st)
 {
     static_assert(LDS_BWD_G > 64 * 1024 && LDS_BWD_G <= 160 * 1024, "the descending pass needs the large LDS window");
-    static LdsAttrOnce attr;                   // once per (instantiation, device): nothing but launches on later calls
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(wkv5_bwd_g_kernel<T>), LDS_BWD_G)) return e;
+    constexpr auto G = wkv5_bwd_g_kernel<T>, A = wkv5_bwd_a_kernel<T>;   // (named in the order the device code lists them)
     const dim3 grid(a.B * a.H), block(NT);
-    hipLaunchKernelGGL((wkv5_bwd_a_kernel<T>), grid, block, LDS_BWD_A, st, a);
-    hipLaunchKernelGGL((wkv5_bwd_g_kernel<T>), grid, block, LDS_BWD_G, st, a);
-    return hipGetLastError();
+    if (hipError_t e = launch<A>(grid, block, LDS_BWD_A, st, a)) return e;
+    return launch<G>(grid, block, LDS_BWD_G, st, a);
 }
 
 }  // namespace

@@ -717,6 +717,30 @@ static bool bi_workspace(void* workspace, size_t workspace_bytes, int nside, int
     return true;
 }
 
+// The caller's workspace where it gave one of `need` bytes, else stream-ordered scratch of `scratch_need` bytes, released when `scratch`
+// goes out of scope.  Null (the workspace is too small, or the allocation failed) is WKV6_EWORKSPACE.
+static void* acquire(void* workspace, size_t workspace_bytes, size_t need, StreamScratch& scratch, hipStream_t st, size_t scratch_need)
+{
+    if (workspace) return workspace_bytes >= need ? workspace : nullptr;
+    return scratch.get(scratch_need, st);
+}
+static void* acquire(void* workspace, size_t workspace_bytes, size_t need, StreamScratch& scratch, hipStream_t st)
+{
+    return acquire(workspace, workspace_bytes, need, scratch, st, need);
+}
+// the initial state: one for the whole batch, or one per batch entry (WKV6_S0_PER_BATCH)
+static void set_state(ScanArgs& a, const void* s0, unsigned flags)
+{
+    a.s0 = s0;
+    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)a.H * HEAD * HEAD : 0;
+}
+// the per-tensor reversal map: no lengths, no map
+static void set_rev(ScanArgs& a, const int* rev_n, unsigned rev_mask)
+{
+    a.rev_n = rev_n;
+    a.rev_mask = rev_n ? rev_mask : 0u;
+}
+
 int wkv6_forward_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v,
                     const void* w, const void* u, const void* s0, void* s_out, void* y,
                     unsigned flags, void* stream)
@@ -724,8 +748,7 @@ int wkv6_forward_ex(int B, int T, int C, int H, const void* r, const void* k, co
     if (int rc = check_shape(B, T, C, H)) return rc;
     if (!r || !k || !v || !w || !u || !y) return WKV6_ENULL;
     ScanArgs a = base_args(B, T, C, H, r, k, v, w, u, flags);
-    a.s0 = s0;
-    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
+    set_state(a, s0, flags);
     a.s_out = s_out;
     a.y = y;
     return to_rc(run_fwd(a, flags, (hipStream_t)stream));
@@ -740,8 +763,7 @@ int wkv6_forward_ckpt_ex(int B, int T, int C, int H, const void* r, const void* 
     if (flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN)) return WKV6_EUNSUPPORTED;
     if (ckpt_bytes < wkv6_backward_workspace_bytes(B, T, C, H)) return WKV6_EWORKSPACE;
     ScanArgs a = base_args(B, T, C, H, r, k, v, w, u, flags);
-    a.s0 = s0;
-    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
+    set_state(a, s0, flags);
     a.s_out = s_out;
     a.y = y;
     a.ckpt = reinterpret_cast<float*>(ckpt);
@@ -758,8 +780,7 @@ int wkv6_forward_gn_ex(int B, int T, int C, int H, const void* r, const void* k,
     if (ckpt && ckpt_bytes < wkv6_backward_workspace_bytes(B, T, C, H)) return WKV6_EWORKSPACE;
     if (want_split(B * H)) return WKV6_EUNSUPPORTED;      // two workgroups per (batch, head): a head's statistics span both
     ScanArgs a = base_args(B, T, C, H, r, k, v, w, u, flags);
-    a.s0 = s0;
-    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
+    set_state(a, s0, flags);
     a.s_out = s_out;
     a.y = y;
     a.ckpt = reinterpret_cast<float*>(ckpt);
@@ -774,17 +795,11 @@ int wkv6_backward_ex(int B, int T, int C, int H, const void* r, const void* k, c
 {
     if (int rc = check_shape(B, T, C, H)) return rc;
     if (!r || !k || !v || !w || !u || !gy || !gr || !gk || !gv || !gw) return WKV6_ENULL;
-    const size_t need = wkv6_backward_workspace_bytes(B, T, C, H);
     StreamScratch scratch;                     // released (stream-ordered) when this call returns
-    if (!workspace) {
-        workspace = scratch.get(need, (hipStream_t)stream);
-        if (!workspace) return WKV6_EWORKSPACE;
-    } else if (workspace_bytes < need) {
-        return WKV6_EWORKSPACE;
-    }
+    workspace = acquire(workspace, workspace_bytes, wkv6_backward_workspace_bytes(B, T, C, H), scratch, (hipStream_t)stream);
+    if (!workspace) return WKV6_EWORKSPACE;
     ScanArgs a = base_args(B, T, C, H, r, k, v, w, u, flags);
-    a.s0 = s0;
-    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
+    set_state(a, s0, flags);
     a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu; a.gs = gs;
     return to_rc(run_bwd(a, flags, reinterpret_cast<float*>(workspace), (hipStream_t)stream));
 }
@@ -834,16 +849,22 @@ static void varlen_carve(ScanArgs& a, void* workspace, long total_T, int n_seq, 
 // One launch: workgroup 0 derives the int arrays (prepare), the others zero the rows of `out` that lie in no sequence -- as many workgroups
 // as would zero the whole tensors with eight 16-byte stores per lane and tensor (nobody reads cu_seqlens here, so the launch cannot know
 // how much there is to zero), 1024 at the most.
+struct FillLaunch { VarlenFill fill; unsigned nwg; };      // the gap-zeroing part of a preparation launch: its arguments and workgroups
+static FillLaunch make_fill(long row_bytes, long total_T, std::initializer_list<void*> out)
+{
+    FillLaunch f = {};
+    for (void* p : out) f.fill.out[f.fill.n_out++] = p;
+    f.fill.row_bytes = row_bytes;
+    const long per_wg = 256L * 16 * 8;
+    f.nwg = (unsigned)std::min<long>(1024, (total_T * row_bytes + per_wg - 1) / per_wg);
+    return f;
+}
 static hipError_t varlen_prepare(const ScanArgs& a, const int* cu, long total_T, int max_seqlen, bool prepare, unsigned flags,
                                  std::initializer_list<void*> out, hipStream_t st)
 {
-    VarlenFill fill = {};
-    for (void* p : out) fill.out[fill.n_out++] = p;
-    fill.row_bytes = (long)a.C * ((flags & WKV6_IO_F32) ? 4 : 2);
-    const long per_wg = 256L * 16 * 8;
-    const unsigned nfill = (unsigned)std::min<long>(1024, (total_T * fill.row_bytes + per_wg - 1) / per_wg);
-    hipLaunchKernelGGL(varlen_prepare_kernel, dim3(1 + nfill), dim3(256), 0, st, cu, a.B, total_T, max_seqlen, a.ck_stride, const_cast<int*>(a.lens),
-                       const_cast<int*>(a.tok_off), const_cast<int*>(a.ck_off), const_cast<int*>(a.order), prepare ? 1 : 0, fill);
+    const FillLaunch f = make_fill((long)a.C * ((flags & WKV6_IO_F32) ? 4 : 2), total_T, out);
+    hipLaunchKernelGGL(varlen_prepare_kernel, dim3(1 + f.nwg), dim3(256), 0, st, cu, a.B, total_T, max_seqlen, a.ck_stride, const_cast<int*>(a.lens),
+                       const_cast<int*>(a.tok_off), const_cast<int*>(a.ck_off), const_cast<int*>(a.order), prepare ? 1 : 0, f.fill);
     return hipGetLastError();
 }
 
@@ -858,22 +879,17 @@ static int varlen_forward(long total_T, int n_seq, int max_seqlen, int C, int H,
     hipStream_t st = (hipStream_t)stream;
     StreamScratch scratch;
     const bool keep = workspace != nullptr;
-    if (workspace) {
-        if (workspace_bytes < wkv6_varlen_workspace_bytes(total_T, n_seq, C, H)) return WKV6_EWORKSPACE;
-    } else {
-        workspace = scratch.get(varlen_int_bytes(n_seq), st);       // the int arrays only: no checkpoints are kept
-        if (!workspace) return WKV6_EWORKSPACE;
-    }
+    // (scratch: the int arrays only: no checkpoints are kept)
+    workspace = acquire(workspace, workspace_bytes, wkv6_varlen_workspace_bytes(total_T, n_seq, C, H), scratch, st, varlen_int_bytes(n_seq));
+    if (!workspace) return WKV6_EWORKSPACE;
     if (!varlen_aligned({y})) return WKV6_EINVAL;
     ScanArgs a = base_args(n_seq, max_seqlen, C, H, r, k, v, w, u, flags);
     float* area = nullptr;
     varlen_carve(a, workspace, total_T, n_seq, &area);
-    a.s0 = s0;
-    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
+    set_state(a, s0, flags);
     a.s_out = s_out;
     a.y = y;
-    a.rev_n = rev_n;
-    a.rev_mask = rev_n ? rev_mask : 0u;
+    set_rev(a, rev_n, rev_mask);
     if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, true, flags, {y}, st)) return to_rc(e);
     if (flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN)) return to_rc(launch_scan_fwd_varlen(a, flags & WKV6_IO_F32, st));
     a.ckpt = keep ? area : nullptr;
@@ -889,24 +905,17 @@ static int varlen_backward(long total_T, int n_seq, int max_seqlen, int C, int H
     if (rev_mask & ~(unsigned)REV_ALL) return WKV6_EINVAL;
     if (!cu_seqlens || !r || !k || !v || !w || !u || !gy || !gr || !gk || !gv || !gw) return WKV6_ENULL;
     hipStream_t st = (hipStream_t)stream;
-    const size_t need = wkv6_varlen_workspace_bytes(total_T, n_seq, C, H);
     StreamScratch scratch;
-    if (!workspace) {
-        if (flags & WKV6_CKPT_VALID) return WKV6_ENULL;             // the checkpoints live in the workspace
-        workspace = scratch.get(need, st);
-        if (!workspace) return WKV6_EWORKSPACE;
-    } else if (workspace_bytes < need) {
-        return WKV6_EWORKSPACE;
-    }
+    if (!workspace && (flags & WKV6_CKPT_VALID)) return WKV6_ENULL;  // the checkpoints live in the workspace
+    workspace = acquire(workspace, workspace_bytes, wkv6_varlen_workspace_bytes(total_T, n_seq, C, H), scratch, st);
+    if (!workspace) return WKV6_EWORKSPACE;
     if (!varlen_aligned({gr, gk, gv, gw})) return WKV6_EINVAL;
     ScanArgs a = base_args(n_seq, max_seqlen, C, H, r, k, v, w, u, flags);
     float* area = nullptr;
     varlen_carve(a, workspace, total_T, n_seq, &area);
-    a.s0 = s0;
-    a.s0_bstride = (flags & WKV6_S0_PER_BATCH) ? (long)H * HEAD * HEAD : 0;
+    set_state(a, s0, flags);
     a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu; a.gs = gs;
-    a.rev_n = rev_n;
-    a.rev_mask = rev_n ? rev_mask : 0u;
+    set_rev(a, rev_n, rev_mask);
     const bool scan = flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN);
     // (WKV6_CKPT_VALID on the chunked path: the forward left the int arrays beside its checkpoints; the launch only zeroes the gaps)
     if (hipError_t e = varlen_prepare(a, cu_seqlens, total_T, max_seqlen, scan || !(flags & WKV6_CKPT_VALID), flags, {gr, gk, gv, gw}, st))
@@ -974,8 +983,7 @@ static int varlen_pair_args(long total_T, int n_seq, int max_seqlen, int C, int 
     for (int i = 0; i < 2; ++i) {
         const wkv6_seq_set& q = s[i];
         a[i] = base_args(n_seq, max_seqlen, C, H, q.r, q.k, q.v, q.w, u, flags);
-        a[i].rev_n = q.rev_n;
-        a[i].rev_mask = q.rev_n ? q.rev_mask : 0u;
+        set_rev(a[i], q.rev_n, q.rev_mask);
         area[i] = q.ckpt ? reinterpret_cast<float*>(reinterpret_cast<char*>(q.ckpt) + varlen_int_bytes(n_seq)) : nullptr;
         if (bwd) { a[i].gy = q.gy; a[i].gr = q.gr; a[i].gk = q.gk; a[i].gv = q.gv; a[i].gw = q.gw; a[i].gu = q.gu; }
         else a[i].y = q.y;
@@ -991,11 +999,9 @@ int wkv6_forward_varlen_pair_ex(long total_T, int n_seq, int max_seqlen, int C, 
     if (int rc = varlen_pair_args(total_T, n_seq, max_seqlen, C, H, cu_seqlens, u, s, flags, false, a, area)) return rc;
     hipStream_t st = (hipStream_t)stream;
     StreamScratch scratch;
-    void* ints = s[0].ckpt;
-    if (!ints) {
-        ints = scratch.get(varlen_int_bytes(n_seq), st);
-        if (!ints) return WKV6_EWORKSPACE;
-    }
+    // (the int arrays only: they lead s[0].ckpt, whose size varlen_pair_args has checked, where the caller keeps checkpoints)
+    void* const ints = acquire(s[0].ckpt, s[0].ckpt_bytes, varlen_int_bytes(n_seq), scratch, st);
+    if (!ints) return WKV6_EWORKSPACE;
     float* unused = nullptr;
     for (int i = 0; i < 2; ++i) {
         varlen_carve(a[i], ints, total_T, n_seq, &unused);
@@ -1035,8 +1041,7 @@ int wkv6_forward_rev_ex(int B, int T, int C, int H, const void* r, const void* k
     if (ckpt && ckpt_bytes < wkv6_backward_workspace_bytes(B, T, C, H)) return WKV6_EWORKSPACE;
     ScanArgs a = base_args(B, T, C, H, r, k, v, w, u, flags);
     a.y = y;
-    a.rev_n = rev_n;
-    a.rev_mask = rev_mask;
+    set_rev(a, rev_n, rev_mask);
     if (flags & (WKV6_IO_F32 | WKV6_ALGO_SCAN))        // exact scan kernels (fp32 I/O, or forced): same index maps, no checkpoints
         return to_rc(launch_scan_fwd(a, (flags & WKV6_IO_F32) ? IO_F32 : IO_BF16, (hipStream_t)stream));
     a.ckpt = reinterpret_cast<float*>(ckpt);
@@ -1051,18 +1056,12 @@ int wkv6_backward_rev_ex(int B, int T, int C, int H, const void* r, const void* 
     if (int rc = check_shape(B, T, C, H)) return rc;
     if (!r || !k || !v || !w || !u || !gy || !gr || !gk || !gv || !gw || !rev_n) return WKV6_ENULL;
     if (rev_mask & ~(unsigned)REV_ALL) return WKV6_EUNSUPPORTED;
-    const size_t need = wkv6_backward_workspace_bytes(B, T, C, H);
     StreamScratch scratch;                     // released (stream-ordered) when this call returns
-    if (!workspace) {
-        workspace = scratch.get(need, (hipStream_t)stream);
-        if (!workspace) return WKV6_EWORKSPACE;
-    } else if (workspace_bytes < need) {
-        return WKV6_EWORKSPACE;
-    }
+    workspace = acquire(workspace, workspace_bytes, wkv6_backward_workspace_bytes(B, T, C, H), scratch, (hipStream_t)stream);
+    if (!workspace) return WKV6_EWORKSPACE;
     ScanArgs a = base_args(B, T, C, H, r, k, v, w, u, flags);
     a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu;
-    a.rev_n = rev_n;
-    a.rev_mask = rev_mask;
+    set_rev(a, rev_n, rev_mask);
     return to_rc(run_bwd(a, flags, reinterpret_cast<float*>(workspace), (hipStream_t)stream));
 }
 
@@ -1080,8 +1079,7 @@ static int pair_args(int B, int T, int C, int H, const void* u, const wkv6_seq_s
         if (q.ckpt && q.ckpt_bytes < need) return WKV6_EWORKSPACE;
         a[i] = base_args(B, T, C, H, q.r, q.k, q.v, q.w, u, flags);
         a[i].ckpt = reinterpret_cast<float*>(q.ckpt);
-        a[i].rev_n = q.rev_n;
-        a[i].rev_mask = q.rev_n ? q.rev_mask : 0u;
+        set_rev(a[i], q.rev_n, q.rev_mask);
         if (bwd) {
             a[i].gy = q.gy; a[i].gr = q.gr; a[i].gk = q.gk; a[i].gv = q.gv; a[i].gw = q.gw; a[i].gu = q.gu;
             a[i].ckpt_valid = 1;
@@ -1376,13 +1374,9 @@ static SplitWorkspace split_carve(float* area, long total_T, int n_seq, int seg_
 // varlen_prepare with the item table (bf16 rows)
 static hipError_t varlen_split_prepare(const ScanArgs& a, const int* cu, long total_T, int max_seqlen, const SegTable& tb, void* y, hipStream_t st)
 {
-    VarlenFill fill = {};
-    fill.out[fill.n_out++] = y;
-    fill.row_bytes = (long)a.C * 2;
-    const long per_wg = 256L * 16 * 8;
-    const unsigned nfill = (unsigned)std::min<long>(1024, (total_T * fill.row_bytes + per_wg - 1) / per_wg);
-    hipLaunchKernelGGL(varlen_split_prepare_kernel, dim3(1 + nfill), dim3(256), 0, st, cu, a.B, total_T, max_seqlen, a.ck_stride,
-                       const_cast<int*>(a.lens), const_cast<int*>(a.tok_off), const_cast<int*>(a.ck_off), const_cast<int*>(a.order), tb, fill);
+    const FillLaunch f = make_fill((long)a.C * 2, total_T, {y});
+    hipLaunchKernelGGL(varlen_split_prepare_kernel, dim3(1 + f.nwg), dim3(256), 0, st, cu, a.B, total_T, max_seqlen, a.ck_stride,
+                       const_cast<int*>(a.lens), const_cast<int*>(a.tok_off), const_cast<int*>(a.ck_off), const_cast<int*>(a.order), tb, f.fill);
     return hipGetLastError();
 }
 
@@ -1407,12 +1401,8 @@ static int rwkv6_infer_varlen(long total_T, int n_seq, int max_seqlen, int C, in
     const size_t need = cut ? split_workspace_bytes(total_T, n_seq, seg_len, H) : rwkv6_varlen_workspace_bytes(n_seq);
     hipStream_t st = (hipStream_t)stream;
     StreamScratch scratch;
-    if (workspace) {
-        if (workspace_bytes < need) return WKV6_EWORKSPACE;
-    } else {
-        workspace = scratch.get(need, st);
-        if (!workspace) return WKV6_EWORKSPACE;
-    }
+    workspace = acquire(workspace, workspace_bytes, need, scratch, st);
+    if (!workspace) return WKV6_EWORKSPACE;
     if (!varlen_aligned({y})) return WKV6_EINVAL;
     ScanArgs a = base_args(n_seq, max_seqlen, C, H, r, k, v, w, u, 0);
     float* area = nullptr;

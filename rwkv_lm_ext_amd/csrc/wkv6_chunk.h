@@ -20,6 +20,15 @@ inline void attach_debug_buffer([[maybe_unused]] ScanArgs& a)
     a.aux = reinterpret_cast<float*>(g_stamp_buffer);
 #endif
 }
+// the argument block every packed launcher hands its kernel: one workgroup per (sequence, head), no clock probe
+inline ScanArgs packed_launch_args(const ScanArgs& a_)
+{
+    ScanArgs a = a_;
+    a.split = 0;
+    a.clk = nullptr; a.clk_slots = 0;
+    attach_debug_buffer(a);
+    return a;
+}
 }  // namespace wkv6
 #ifdef WKV6_STAMP
 #define WKV6_T(var) do { __builtin_amdgcn_sched_barrier(0); \

@@ -905,14 +905,14 @@ __global__ __launch_bounds__(512) void chunk_fwd_bi_kernel(const ScanArgs a1_, f
     }
 }
 
+// LDS of a forward workgroup: two operand groups, the consumers' checkpoint transposition buffers, two staged y groups
+constexpr size_t FWD_LDS = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
+
 template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF> hipError_t launch_fwd_variant2(const ScanArgs& a, hipStream_t st)
 {
-    constexpr size_t lds = 2 * (size_t)GRP_BYTES + (GN ? 4096 : 0) + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr;                   // per instantiation and device
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_kernel<W_RAW, STATE_ONLY, ACC, GN, AFF>), lds)) return e;
-    if (a.split) hipLaunchKernelGGL((chunk_fwd_kernel<W_RAW, STATE_ONLY, ACC, GN, AFF>), dim3(2 * a.B * a.H), dim3(384), lds, st, a);
-    else hipLaunchKernelGGL((chunk_fwd_kernel<W_RAW, STATE_ONLY, ACC, GN, AFF>), dim3(a.B * a.H), dim3(512), lds, st, a);
-    return hipGetLastError();
+    constexpr auto K = chunk_fwd_kernel<W_RAW, STATE_ONLY, ACC, GN, AFF>;
+    constexpr size_t lds = FWD_LDS + (GN ? 4096 : 0);
+    return a.split ? launch<K>(dim3(2 * a.B * a.H), dim3(384), lds, st, a) : launch<K>(dim3(a.B * a.H), dim3(512), lds, st, a);
 }
 // per-tensor reversal maps (a.rev_n: the compositions' *_rev_ex calls and their state passes) take the general token addressing; the
 // accumulating half of wkv6_bi and the GroupNorm epilogue never carry one
@@ -924,9 +924,6 @@ template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN = false> hipError_t lau
 }
 
 }  // namespace
-
-// per-lane byte offsets are 32-bit: bf16 tensors need (T + 64) C < 2^31 (checked by the API), the fp32 decay input half of that
-static bool offsets_fit(const ScanArgs& a) { return a.wkind == 1 || ((long)a.T + 64) * a.C < (1L << 30); }
 
 hipError_t launch_chunk_fwd(const ScanArgs& a_, hipStream_t st)
 {
@@ -949,7 +946,7 @@ hipError_t launch_chunk_fwd(const ScanArgs& a_, hipStream_t st)
 hipError_t launch_chunk_fwd_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipStream_t st)
 {
     if (!offsets_fit(a0_) || !offsets_fit(a1_)) return hipErrorInvalidValue;
-    if (a0_.B != a1_.B || a0_.T != a1_.T || a0_.C != a1_.C || a0_.H != a1_.H || a0_.wkind != a1_.wkind) return hipErrorInvalidValue;
+    if (!same_problem(a0_, a1_)) return hipErrorInvalidValue;
     const auto plain = [](const ScanArgs& a) { return !a.accumulate && !a.y_f32 && !a.zero_tail && !a.gn_out && !a.dsum && !a.ckpt_segs; };
     if (!plain(a0_) || !plain(a1_)) return hipErrorNotSupported;
     if (want_split(a0_.B * a0_.H)) {
@@ -958,16 +955,9 @@ hipError_t launch_chunk_fwd_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipSt
     }
     ScanArgs a0 = a0_, a1 = a1_;
     a0.split = a1.split = 0;
-    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr_raw, attr_ew;
-    if (a0.wkind == 1) {
-        if (hipError_t e = attr_raw.ensure(reinterpret_cast<const void*>(chunk_fwd_pair_kernel<true>), lds)) return e;
-        hipLaunchKernelGGL((chunk_fwd_pair_kernel<true>), dim3(2 * a0.B * a0.H), dim3(512), lds, st, a0, a1);
-    } else {
-        if (hipError_t e = attr_ew.ensure(reinterpret_cast<const void*>(chunk_fwd_pair_kernel<false>), lds)) return e;
-        hipLaunchKernelGGL((chunk_fwd_pair_kernel<false>), dim3(2 * a0.B * a0.H), dim3(512), lds, st, a0, a1);
-    }
-    return hipGetLastError();
+    const dim3 grid(2 * a0.B * a0.H);
+    return a0.wkind == 1 ? launch<chunk_fwd_pair_kernel<true>>(grid, dim3(512), FWD_LDS, st, a0, a1)
+                         : launch<chunk_fwd_pair_kernel<false>>(grid, dim3(512), FWD_LDS, st, a0, a1);
 }
 
 hipError_t launch_chunk_fwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* slots, hipStream_t st)
@@ -981,16 +971,8 @@ hipError_t launch_chunk_fwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* sl
     a1.side_compact = a2.side_compact = 1;
     attach_debug_buffer(a1);
     attach_debug_buffer(a2);
-    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr_raw, attr_ew;
-    if (a1.wkind == 1) {
-        if (hipError_t e = attr_raw.ensure(reinterpret_cast<const void*>(chunk_fwd_bi_kernel<true>), lds)) return e;
-        hipLaunchKernelGGL((chunk_fwd_bi_kernel<true>), dim3(n), dim3(512), lds, st, a1, a2.ckpt);
-    } else {
-        if (hipError_t e = attr_ew.ensure(reinterpret_cast<const void*>(chunk_fwd_bi_kernel<false>), lds)) return e;
-        hipLaunchKernelGGL((chunk_fwd_bi_kernel<false>), dim3(n), dim3(512), lds, st, a1, a2.ckpt);
-    }
-    return hipGetLastError();
+    return a1.wkind == 1 ? launch<chunk_fwd_bi_kernel<true>>(dim3(n), dim3(512), FWD_LDS, st, a1, a2.ckpt)
+                         : launch<chunk_fwd_bi_kernel<false>>(dim3(n), dim3(512), FWD_LDS, st, a1, a2.ckpt);
 }
 
 // Packed rows (a.tok_off / a.ck_off / a.lens / a.order set by the API's preparation kernel; a.B = sequences, a.T = longest length allowed).
@@ -998,16 +980,9 @@ hipError_t launch_chunk_fwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* sl
 // a.rev_n (per-tensor reversal maps, indexed by the sequence) selects the general-addressing instantiations.
 template <bool W_RAW, bool STATE_ONLY> static hipError_t launch_fwd_varlen_inst(const ScanArgs& a, hipStream_t st)
 {
-    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr, attr_rev;
-    if (a.rev_n) {
-        if (hipError_t e = attr_rev.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_rev_kernel<W_RAW, STATE_ONLY>), lds)) return e;
-        hipLaunchKernelGGL((chunk_fwd_varlen_rev_kernel<W_RAW, STATE_ONLY>), dim3(a.B * a.H), dim3(512), lds, st, a);
-        return hipGetLastError();
-    }
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_kernel<W_RAW, STATE_ONLY>), lds)) return e;
-    hipLaunchKernelGGL((chunk_fwd_varlen_kernel<W_RAW, STATE_ONLY>), dim3(a.B * a.H), dim3(512), lds, st, a);
-    return hipGetLastError();
+    const dim3 grid(a.B * a.H);
+    return a.rev_n ? launch<chunk_fwd_varlen_rev_kernel<W_RAW, STATE_ONLY>>(grid, dim3(512), FWD_LDS, st, a)
+                   : launch<chunk_fwd_varlen_kernel<W_RAW, STATE_ONLY>>(grid, dim3(512), FWD_LDS, st, a);
 }
 static bool varlen_fwd_plain(const ScanArgs& a)
 {
@@ -1015,13 +990,9 @@ static bool varlen_fwd_plain(const ScanArgs& a)
 }
 hipError_t launch_chunk_fwd_varlen(const ScanArgs& a_, bool state_only, hipStream_t st)
 {
-    if (!offsets_fit(a_)) return hipErrorInvalidValue;
-    if (!a_.tok_off || !a_.ck_off || !a_.lens || !a_.order) return hipErrorInvalidValue;
+    if (!offsets_fit(a_) || !packed_arrays_ok(a_)) return hipErrorInvalidValue;
     if (!varlen_fwd_plain(a_)) return hipErrorNotSupported;
-    ScanArgs a = a_;
-    a.split = 0;
-    a.clk = nullptr; a.clk_slots = 0;
-    attach_debug_buffer(a);
+    const ScanArgs a = packed_launch_args(a_);
     const bool raw = a.wkind == 1;
     if (state_only) return raw ? launch_fwd_varlen_inst<true, true>(a, st) : launch_fwd_varlen_inst<false, true>(a, st);
     return raw ? launch_fwd_varlen_inst<true, false>(a, st) : launch_fwd_varlen_inst<false, false>(a, st);
@@ -1031,35 +1002,17 @@ hipError_t launch_chunk_fwd_varlen(const ScanArgs& a_, bool state_only, hipStrea
 // a.state_slot; sequences outside [a.len_lo, a.len_hi) are left to another launch
 hipError_t launch_chunk_fwd_slots(const ScanArgs& a_, hipStream_t st)
 {
-    if (!offsets_fit(a_)) return hipErrorInvalidValue;
-    if (!a_.tok_off || !a_.ck_off || !a_.lens || !a_.order || !slots_ok(a_) || a_.wkind != 2) return hipErrorInvalidValue;
+    if (!offsets_fit(a_) || !packed_arrays_ok(a_) || !slots_ok(a_) || a_.wkind != 2) return hipErrorInvalidValue;
     if (!varlen_fwd_plain(a_) || a_.rev_n || a_.ckpt) return hipErrorNotSupported;
-    ScanArgs a = a_;
-    a.split = 0;
-    a.clk = nullptr; a.clk_slots = 0;
-    attach_debug_buffer(a);
-    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr;
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_slots_kernel), lds)) return e;
-    hipLaunchKernelGGL(chunk_fwd_varlen_slots_kernel, dim3(a.B * a.H), dim3(512), lds, st, a);
-    return hipGetLastError();
+    return launch<chunk_fwd_varlen_slots_kernel>(dim3(a_.B * a_.H), dim3(512), FWD_LDS, st, packed_launch_args(a_));
 }
 
 // ... with the final state in slot a.state_slot_out and the snapshots of wkv6_scan.h: SnapPlan
 hipError_t launch_chunk_fwd_snap(const ScanArgs& a_, hipStream_t st)
 {
-    if (!offsets_fit(a_)) return hipErrorInvalidValue;
-    if (!a_.tok_off || !a_.ck_off || !a_.lens || !a_.order || !slots_ok(a_) || !snap_ok(a_) || a_.wkind != 2) return hipErrorInvalidValue;
+    if (!offsets_fit(a_) || !packed_arrays_ok(a_) || !slots_ok(a_) || !snap_ok(a_) || a_.wkind != 2) return hipErrorInvalidValue;
     if (!varlen_fwd_plain(a_) || a_.rev_n || a_.ckpt) return hipErrorNotSupported;
-    ScanArgs a = a_;
-    a.split = 0;
-    a.clk = nullptr; a.clk_slots = 0;
-    attach_debug_buffer(a);
-    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr;
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_snap_kernel), lds)) return e;
-    hipLaunchKernelGGL(chunk_fwd_varlen_snap_kernel, dim3(a.B * a.H), dim3(512), lds, st, a);
-    return hipGetLastError();
+    return launch<chunk_fwd_varlen_snap_kernel>(dim3(a_.B * a_.H), dim3(512), FWD_LDS, st, packed_launch_args(a_));
 }
 
 // ... over the item table of a split call (wkv6_scan.h: SegArgs; a.B = the number of table entries this launch covers, a.lens / a.tok_off per
@@ -1068,26 +1021,17 @@ hipError_t launch_chunk_fwd_snap(const ScanArgs& a_, hipStream_t st)
 hipError_t launch_chunk_fwd_seg(const ScanArgs& a_, const SegArgs& sg, bool state_only, hipStream_t st)
 {
     if (!offsets_fit(a_)) return hipErrorInvalidValue;
+    // (not packed_arrays_ok: the table is in dispatch order already, so a.order must be null here)
     if (!a_.tok_off || !a_.ck_off || !a_.lens || a_.order || a_.wkind != 2 || !a_.state_f32) return hipErrorInvalidValue;
     if (!sg.n || !sg.seq || !sg.pos || !sg.seq_lens || a_.len_hi != 0) return hipErrorInvalidValue;
     if (state_only ? (a_.s0 || !a_.s_out || !a_.dsum || a_.y) : (!sg.sin || !slots_ok(a_) || !snap_ok(a_) || a_.dsum)) return hipErrorInvalidValue;
     ScanArgs t = a_;
     t.dsum = nullptr;
     if (!varlen_fwd_plain(t) || a_.rev_n || a_.ckpt) return hipErrorNotSupported;
-    ScanArgs a = a_;
-    a.split = 0;
-    a.clk = nullptr; a.clk_slots = 0;
-    attach_debug_buffer(a);
-    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr_state, attr_fwd;
-    if (state_only) {
-        if (hipError_t e = attr_state.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_seg_state_kernel), lds)) return e;
-        hipLaunchKernelGGL(chunk_fwd_varlen_seg_state_kernel, dim3(a.B * a.H), dim3(512), lds, st, a, sg);
-    } else {
-        if (hipError_t e = attr_fwd.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_seg_kernel), lds)) return e;
-        hipLaunchKernelGGL(chunk_fwd_varlen_seg_kernel, dim3(a.B * a.H), dim3(512), lds, st, a, sg);
-    }
-    return hipGetLastError();
+    const ScanArgs a = packed_launch_args(a_);
+    const dim3 grid(a.B * a.H);
+    return state_only ? launch<chunk_fwd_varlen_seg_state_kernel>(grid, dim3(512), FWD_LDS, st, a, sg)
+                      : launch<chunk_fwd_varlen_seg_kernel>(grid, dim3(512), FWD_LDS, st, a, sg);
 }
 
 // Both problems of a bidirectional composition on packed rows in one launch: the same sequences (one set of prepared int arrays), each
@@ -1095,27 +1039,12 @@ hipError_t launch_chunk_fwd_seg(const ScanArgs& a_, const SegArgs& sg, bool stat
 hipError_t launch_chunk_fwd_varlen_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipStream_t st)
 {
     if (!offsets_fit(a0_) || !offsets_fit(a1_)) return hipErrorInvalidValue;
-    if (a0_.B != a1_.B || a0_.T != a1_.T || a0_.C != a1_.C || a0_.H != a1_.H || a0_.wkind != a1_.wkind) return hipErrorInvalidValue;
-    if (!a0_.tok_off || !a0_.ck_off || !a0_.lens || !a0_.order) return hipErrorInvalidValue;
-    if (a0_.tok_off != a1_.tok_off || a0_.ck_off != a1_.ck_off || a0_.lens != a1_.lens || a0_.order != a1_.order || a0_.ck_stride != a1_.ck_stride)
-        return hipErrorInvalidValue;
+    if (!same_problem(a0_, a1_) || !packed_arrays_ok(a0_) || !same_packed_arrays(a0_, a1_)) return hipErrorInvalidValue;
     if (!varlen_fwd_plain(a0_) || !varlen_fwd_plain(a1_)) return hipErrorNotSupported;
-    ScanArgs a0 = a0_, a1 = a1_;
-    for (ScanArgs* a : {&a0, &a1}) {
-        a->split = 0;
-        a->clk = nullptr; a->clk_slots = 0;
-        attach_debug_buffer(*a);
-    }
-    constexpr size_t lds = 2 * (size_t)GRP_BYTES + CKX_BYTES + 2 * YS_BYTES;
-    static LdsAttrOnce attr_raw, attr_ew;
-    if (a0.wkind == 1) {
-        if (hipError_t e = attr_raw.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_pair_kernel<true>), lds)) return e;
-        hipLaunchKernelGGL((chunk_fwd_varlen_pair_kernel<true>), dim3(2 * a0.B * a0.H), dim3(512), lds, st, a0, a1);
-    } else {
-        if (hipError_t e = attr_ew.ensure(reinterpret_cast<const void*>(chunk_fwd_varlen_pair_kernel<false>), lds)) return e;
-        hipLaunchKernelGGL((chunk_fwd_varlen_pair_kernel<false>), dim3(2 * a0.B * a0.H), dim3(512), lds, st, a0, a1);
-    }
-    return hipGetLastError();
+    const ScanArgs a0 = packed_launch_args(a0_), a1 = packed_launch_args(a1_);
+    const dim3 grid(2 * a0.B * a0.H);
+    return a0.wkind == 1 ? launch<chunk_fwd_varlen_pair_kernel<true>>(grid, dim3(512), FWD_LDS, st, a0, a1)
+                         : launch<chunk_fwd_varlen_pair_kernel<false>>(grid, dim3(512), FWD_LDS, st, a0, a1);
 }
 
 // state recurrence only, dumping the stage-entry states into a.ckpt (first half of the self-contained backward)

@@ -1457,16 +1457,8 @@ __global__ __launch_bounds__(768) void chunk_bwd12k_bi_kernel(const ScanArgs a1_
 
 template <bool W_RAW, int GEN, bool AFF> hipError_t launch_bwd12k_inst2(const ScanArgs& a, hipStream_t st)
 {
-    constexpr size_t lds = BWD12K_LDS;
-    static LdsAttrOnce attr, attr_split;       // per instantiation and device
-    if (a.split) {
-        if (hipError_t e = attr_split.ensure(reinterpret_cast<const void*>(chunk_bwd12k_kernel<W_RAW, GEN, true, AFF>), lds)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_kernel<W_RAW, GEN, true, AFF>), dim3(2 * a.B * a.H), dim3(512), lds, st, a);
-    } else {
-        if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_bwd12k_kernel<W_RAW, GEN, false, AFF>), lds)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_kernel<W_RAW, GEN, false, AFF>), dim3(a.B * a.H), dim3(768), lds, st, a);
-    }
-    return hipGetLastError();
+    return a.split ? launch<chunk_bwd12k_kernel<W_RAW, GEN, true, AFF>>(dim3(2 * a.B * a.H), dim3(512), BWD12K_LDS, st, a)
+                   : launch<chunk_bwd12k_kernel<W_RAW, GEN, false, AFF>>(dim3(a.B * a.H), dim3(768), BWD12K_LDS, st, a);
 }
 // per-tensor reversal maps (a.rev_n: the compositions' *_rev_ex calls) take the general token addressing; the halves of wkv6_bi never
 // carry one
@@ -1504,7 +1496,7 @@ hipError_t launch_chunk_bwd(const ScanArgs& a_, hipStream_t st)
 {
     ScanArgs a = a_;
     a.split = want_split(a.B * a.H);
-    if (a.wkind != 1 && ((long)a.T + 64) * a.C >= (1L << 30)) return hipErrorInvalidValue;   // 32-bit byte offsets of the fp32 decay input
+    if (!offsets_fit(a)) return hipErrorInvalidValue;   // 32-bit byte offsets of the fp32 decay input
     if (!a.ckpt_valid) {                   // self-contained backward: state pass first (same inputs, no outputs)
         ScanArgs sp = a;
         sp.y = nullptr; sp.y_f32 = nullptr; sp.s_out = nullptr; sp.accumulate = 0; sp.zero_tail = 0;
@@ -1517,15 +1509,9 @@ hipError_t launch_chunk_bwd(const ScanArgs& a_, hipStream_t st)
 // whole-row `reverse`, no wkv6_bi halves, no two-level scan over T; a.rev_n selects the general-addressing instantiations.
 template <bool W_RAW> static hipError_t launch_bwd12k_varlen_inst(const ScanArgs& a, hipStream_t st)
 {
-    static LdsAttrOnce attr, attr_rev;
-    if (a.rev_n) {
-        if (hipError_t e = attr_rev.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_rev_kernel<W_RAW>), BWD12K_LDS)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_varlen_rev_kernel<W_RAW>), dim3(a.B * a.H), dim3(768), BWD12K_LDS, st, a);
-        return hipGetLastError();
-    }
-    if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_kernel<W_RAW>), BWD12K_LDS)) return e;
-    hipLaunchKernelGGL((chunk_bwd12k_varlen_kernel<W_RAW>), dim3(a.B * a.H), dim3(768), BWD12K_LDS, st, a);
-    return hipGetLastError();
+    const dim3 grid(a.B * a.H);
+    return a.rev_n ? launch<chunk_bwd12k_varlen_rev_kernel<W_RAW>>(grid, dim3(768), BWD12K_LDS, st, a)
+                   : launch<chunk_bwd12k_varlen_kernel<W_RAW>>(grid, dim3(768), BWD12K_LDS, st, a);
 }
 static bool varlen_bwd_plain(const ScanArgs& a)
 {
@@ -1534,18 +1520,14 @@ static bool varlen_bwd_plain(const ScanArgs& a)
 }
 hipError_t launch_chunk_bwd_varlen(const ScanArgs& a_, hipStream_t st)
 {
-    if (!a_.ckpt || !a_.tok_off || !a_.ck_off || !a_.lens || !a_.order) return hipErrorInvalidValue;
-    if (a_.wkind != 1 && ((long)a_.T + 64) * a_.C >= (1L << 30)) return hipErrorInvalidValue;
+    if (!a_.ckpt || !packed_arrays_ok(a_) || !offsets_fit(a_)) return hipErrorInvalidValue;
     if (!varlen_bwd_plain(a_)) return hipErrorNotSupported;
-    ScanArgs a = a_;
-    a.split = 0;
-    a.clk = nullptr; a.clk_slots = 0;
+    const ScanArgs a = packed_launch_args(a_);
     if (!a.ckpt_valid) {
         ScanArgs sp = a;
         sp.y = nullptr; sp.s_out = nullptr;
         if (hipError_t e = launch_chunk_fwd_varlen(sp, true, st)) return e;
     }
-    attach_debug_buffer(a);
     return a.wkind ? launch_bwd12k_varlen_inst<true>(a, st) : launch_bwd12k_varlen_inst<false>(a, st);
 }
 
@@ -1553,28 +1535,13 @@ hipError_t launch_chunk_bwd_varlen(const ScanArgs& a_, hipStream_t st)
 // the prepared int arrays the two problems share
 hipError_t launch_chunk_bwd_varlen_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipStream_t st)
 {
-    if (a0_.B != a1_.B || a0_.T != a1_.T || a0_.C != a1_.C || a0_.H != a1_.H || a0_.wkind != a1_.wkind) return hipErrorInvalidValue;
-    if (!a0_.tok_off || !a0_.ck_off || !a0_.lens || !a0_.order) return hipErrorInvalidValue;
-    if (a0_.tok_off != a1_.tok_off || a0_.ck_off != a1_.ck_off || a0_.lens != a1_.lens || a0_.order != a1_.order || a0_.ck_stride != a1_.ck_stride)
-        return hipErrorInvalidValue;
-    if (a0_.wkind != 1 && ((long)a0_.T + 64) * a0_.C >= (1L << 30)) return hipErrorInvalidValue;
+    if (!same_problem(a0_, a1_) || !packed_arrays_ok(a0_) || !same_packed_arrays(a0_, a1_) || !offsets_fit(a0_)) return hipErrorInvalidValue;
     const auto plain = [](const ScanArgs& a) { return varlen_bwd_plain(a) && a.ckpt && a.ckpt_valid; };
     if (!plain(a0_) || !plain(a1_)) return hipErrorNotSupported;
-    ScanArgs a0 = a0_, a1 = a1_;
-    for (ScanArgs* a : {&a0, &a1}) {
-        a->split = 0;
-        a->clk = nullptr; a->clk_slots = 0;
-        attach_debug_buffer(*a);
-    }
-    static LdsAttrOnce attr_raw, attr_ew;
-    if (a0.wkind == 1) {
-        if (hipError_t e = attr_raw.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_pair_kernel<true>), BWD12K_LDS)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_varlen_pair_kernel<true>), dim3(2 * a0.B * a0.H), dim3(768), BWD12K_LDS, st, a0, a1);
-    } else {
-        if (hipError_t e = attr_ew.ensure(reinterpret_cast<const void*>(chunk_bwd12k_varlen_pair_kernel<false>), BWD12K_LDS)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_varlen_pair_kernel<false>), dim3(2 * a0.B * a0.H), dim3(768), BWD12K_LDS, st, a0, a1);
-    }
-    return hipGetLastError();
+    const ScanArgs a0 = packed_launch_args(a0_), a1 = packed_launch_args(a1_);
+    const dim3 grid(2 * a0.B * a0.H);
+    return a0.wkind == 1 ? launch<chunk_bwd12k_varlen_pair_kernel<true>>(grid, dim3(768), BWD12K_LDS, st, a0, a1)
+                         : launch<chunk_bwd12k_varlen_pair_kernel<false>>(grid, dim3(768), BWD12K_LDS, st, a0, a1);
 }
 
 hipError_t launch_chunk_bwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* slots, hipStream_t st)
@@ -1582,7 +1549,7 @@ hipError_t launch_chunk_bwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* sl
     const int n = bi_slots(a1_.B * a1_.H);
     if (slots) *slots = n;
     if (!n || !a1_.ckpt || !a2_.ckpt || a1_.g_in || a1_.rc_in) return hipErrorNotSupported;
-    if (a1_.wkind != 1 && ((long)a1_.T + 64) * a1_.C >= (1L << 30)) return hipErrorInvalidValue;
+    if (!offsets_fit(a1_)) return hipErrorInvalidValue;
     ScanArgs a1 = a1_, a2 = a2_;
     for (ScanArgs* a : {&a1, &a2}) {
         a->split = 0;
@@ -1595,23 +1562,15 @@ hipError_t launch_chunk_bwd_bi(const ScanArgs& a1_, const ScanArgs& a2_, int* sl
         attach_debug_buffer(*a);
     }
     // (both decay kinds since round 6: the reference-signature symbols pass fp32 ew = -exp(w), cuda/wkv6_bi_op.cpp:5-13)
-    constexpr size_t lds = BWD12K_LDS;
-    static LdsAttrOnce attr_raw, attr_ew;
-    if (a1.wkind == 1) {
-        if (hipError_t e = attr_raw.ensure(reinterpret_cast<const void*>(chunk_bwd12k_bi_kernel<true>), lds)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_bi_kernel<true>), dim3(n), dim3(768), lds, st, a1, a2.ckpt);
-    } else {
-        if (hipError_t e = attr_ew.ensure(reinterpret_cast<const void*>(chunk_bwd12k_bi_kernel<false>), lds)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_bi_kernel<false>), dim3(n), dim3(768), lds, st, a1, a2.ckpt);
-    }
-    return hipGetLastError();
+    return a1.wkind == 1 ? launch<chunk_bwd12k_bi_kernel<true>>(dim3(n), dim3(768), BWD12K_LDS, st, a1, a2.ckpt)
+                         : launch<chunk_bwd12k_bi_kernel<false>>(dim3(n), dim3(768), BWD12K_LDS, st, a1, a2.ckpt);
 }
 
 // Backward of both problems of a bidirectional composition in one launch; both checkpoint sets must come from the forward
 // (ckpt_valid).  Two launches where a (batch, head) pair is split over two workgroups or the two-level kernel is selected.
 hipError_t launch_chunk_bwd_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipStream_t st)
 {
-    if (a0_.B != a1_.B || a0_.T != a1_.T || a0_.C != a1_.C || a0_.H != a1_.H || a0_.wkind != a1_.wkind) return hipErrorInvalidValue;
+    if (!same_problem(a0_, a1_)) return hipErrorInvalidValue;
     const auto plain = [](const ScanArgs& a) {
         return !a.accumulate && !a.zero_tail && !a.g_f32[0] && !a.g_f32[1] && !a.g_f32[2] && !a.g_f32[3] && a.ckpt && a.ckpt_valid;
     };
@@ -1620,21 +1579,14 @@ hipError_t launch_chunk_bwd_pair(const ScanArgs& a0_, const ScanArgs& a1_, hipSt
         if (hipError_t e = launch_chunk_bwd(a0_, st)) return e;
         return launch_chunk_bwd(a1_, st);
     }
-    if (a0_.wkind != 1 && ((long)a0_.T + 64) * a0_.C >= (1L << 30)) return hipErrorInvalidValue;
+    if (!offsets_fit(a0_)) return hipErrorInvalidValue;
     ScanArgs a0 = a0_, a1 = a1_;
     a0.split = a1.split = 0;
     attach_debug_buffer(a0);
     attach_debug_buffer(a1);
-    constexpr size_t lds = BWD12K_LDS;
-    static LdsAttrOnce attr_raw, attr_ew;
-    if (a0.wkind == 1) {
-        if (hipError_t e = attr_raw.ensure(reinterpret_cast<const void*>(chunk_bwd12k_pair_kernel<true>), lds)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_pair_kernel<true>), dim3(2 * a0.B * a0.H), dim3(768), lds, st, a0, a1);
-    } else {
-        if (hipError_t e = attr_ew.ensure(reinterpret_cast<const void*>(chunk_bwd12k_pair_kernel<false>), lds)) return e;
-        hipLaunchKernelGGL((chunk_bwd12k_pair_kernel<false>), dim3(2 * a0.B * a0.H), dim3(768), lds, st, a0, a1);
-    }
-    return hipGetLastError();
+    const dim3 grid(2 * a0.B * a0.H);
+    return a0.wkind == 1 ? launch<chunk_bwd12k_pair_kernel<true>>(grid, dim3(768), BWD12K_LDS, st, a0, a1)
+                         : launch<chunk_bwd12k_pair_kernel<false>>(grid, dim3(768), BWD12K_LDS, st, a0, a1);
 }
 
 }  // namespace wkv6

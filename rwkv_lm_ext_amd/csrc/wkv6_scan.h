@@ -44,6 +44,18 @@ struct LdsAttrOnce {
     }
 };
 
+// The one way a kernel is launched: raise the kernel's LDS limit where the launch needs more than the default 64 KB (once per instantiation
+// and device: Kernel is a template argument, so the static is the instantiation's own), launch, report the launch's error.
+template <auto Kernel, typename... Args>
+hipError_t launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args)
+{
+    static LdsAttrOnce attr;
+    if (lds > 64 * 1024)
+        if (hipError_t e = attr.ensure(reinterpret_cast<const void*>(Kernel), lds)) return e;
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+
 struct ScanArgs {
     int B, T, C, H;
     const void *r, *k, *v, *w, *u;   // w: float ew = -exp(w) when wkind == 0, raw w in the I/O type when 1,
@@ -223,6 +235,22 @@ struct TokAddr {
         else return (unsigned)(m(pu + plane, bit) * stride + ch);
     }
 };
+
+// Preconditions the chunked launchers share (wkv6_chunk.hip, wkv6_chunk_bwd12k.hip).
+// per-lane byte offsets are 32-bit: bf16 tensors need (T + 64) C < 2^31 (checked by the API), the fp32 decay input half of that
+inline bool offsets_fit(const ScanArgs& a) { return a.wkind == 1 || ((long)a.T + 64) * a.C < (1L << 30); }
+// the int arrays of a packed batch, as the API's preparation kernel leaves them
+inline bool packed_arrays_ok(const ScanArgs& a) { return a.tok_off && a.ck_off && a.lens && a.order; }
+// two problems that one launch of 2 B H workgroups can serve ...
+inline bool same_problem(const ScanArgs& a0, const ScanArgs& a1)
+{
+    return a0.B == a1.B && a0.T == a1.T && a0.C == a1.C && a0.H == a1.H && a0.wkind == a1.wkind;
+}
+// ... over the same packed sequences: one set of prepared int arrays
+inline bool same_packed_arrays(const ScanArgs& a0, const ScanArgs& a1)
+{
+    return a0.tok_off == a1.tok_off && a0.ck_off == a1.ck_off && a0.lens == a1.lens && a0.order == a1.order && a0.ck_stride == a1.ck_stride;
+}
 
 enum { IO_BF16 = 0, IO_F32 = 1, IO_F16 = 2 };   // I/O element type of the scan forward (fp16: inference entry point only)
 hipError_t launch_scan_fwd(const ScanArgs& a, int io, hipStream_t st);

@@ -766,43 +766,36 @@ __global__ void selftest_kernel(int* result)
     if (bad) atomicOr(result, bad);
 }
 
-template <typename K> hipError_t set_lds(K kernel, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 constexpr int NWAVES = 8;
+constexpr size_t SCAN_FWD_LDS = (2 * 4 * TB * ROW + 64 + 2 * TB * ROW) * sizeof(float);
 
-}  // namespace
-
-hipError_t launch_scan_fwd(const ScanArgs& a, int io, hipStream_t st)
+// the scan forward in its I/O type: plain, or the packed stateful instantiations (SLOTS / SNAP)
+template <bool SLOTS, bool SNAP> hipError_t launch_scan_fwd_io(const ScanArgs& a, int io, hipStream_t st)
 {
-    constexpr size_t lds = (2 * 4 * TB * ROW + 64 + 2 * TB * ROW) * sizeof(float);
     const dim3 grid(a.B * a.H), block(NWAVES * 64);
-    if (io == IO_F32) hipLaunchKernelGGL((scan_fwd_kernel<float, NWAVES>), grid, block, lds, st, a);
-    else if (io == IO_F16) hipLaunchKernelGGL((scan_fwd_kernel<f16_t, NWAVES>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((scan_fwd_kernel<bf16_t, NWAVES>), grid, block, lds, st, a);
-    return hipGetLastError();
+    if (io == IO_F32) return launch<scan_fwd_kernel<float, NWAVES, SLOTS, SNAP>>(grid, block, SCAN_FWD_LDS, st, a);
+    if (io == IO_F16) return launch<scan_fwd_kernel<f16_t, NWAVES, SLOTS, SNAP>>(grid, block, SCAN_FWD_LDS, st, a);
+    return launch<scan_fwd_kernel<bf16_t, NWAVES, SLOTS, SNAP>>(grid, block, SCAN_FWD_LDS, st, a);
 }
 
-hipError_t launch_scan_bwd(const ScanArgs& a, bool io_f32, hipStream_t st)
+// sweep S, then sweep G
+template <typename T> hipError_t launch_scan_bwd_io(const ScanArgs& a, hipStream_t st)
 {
+    constexpr auto G = scan_bwd_g_kernel<T, NWAVES>, S = scan_bwd_s_kernel<T, NWAVES>;   // (named in the order the device code lists them)
     constexpr size_t lds_s = (2 * 4 * TB * ROW + 2 * TB * ROW) * sizeof(float);
     constexpr size_t lds_g = (2 * 5 * TB * ROW + 2 * TB * ROW + 2 * NWAVES * TB * ROW + 2 * TB * ROW) * sizeof(float);
     const dim3 grid(a.B * a.H), block(NWAVES * 64);
-    hipError_t e;
-    if (io_f32) {
-        if ((e = set_lds(scan_bwd_g_kernel<float, NWAVES>, lds_g)) != hipSuccess) return e;
-        hipLaunchKernelGGL((scan_bwd_s_kernel<float, NWAVES>), grid, block, lds_s, st, a);
-        hipLaunchKernelGGL((scan_bwd_g_kernel<float, NWAVES>), grid, block, lds_g, st, a);
-    } else {
-        if ((e = set_lds(scan_bwd_g_kernel<bf16_t, NWAVES>, lds_g)) != hipSuccess) return e;
-        hipLaunchKernelGGL((scan_bwd_s_kernel<bf16_t, NWAVES>), grid, block, lds_s, st, a);
-        hipLaunchKernelGGL((scan_bwd_g_kernel<bf16_t, NWAVES>), grid, block, lds_g, st, a);
-    }
-    return hipGetLastError();
+    if (hipError_t e = launch<S>(grid, block, lds_s, st, a)) return e;
+    return launch<G>(grid, block, lds_g, st, a);
+}
+
+}  // namespace
+
+hipError_t launch_scan_fwd(const ScanArgs& a, int io, hipStream_t st) { return launch_scan_fwd_io<false, false>(a, io, st); }
+
+hipError_t launch_scan_bwd(const ScanArgs& a, bool io_f32, hipStream_t st)
+{
+    return io_f32 ? launch_scan_bwd_io<float>(a, st) : launch_scan_bwd_io<bf16_t>(a, st);
 }
 
 // Packed variable-length rows: the same kernels, addressed through a.tok_off / a.order (one workgroup per (sequence, head)); a reversal
@@ -825,29 +818,15 @@ hipError_t launch_scan_bwd_varlen(const ScanArgs& a, bool io_f32, hipStream_t st
 hipError_t launch_scan_fwd_slots(const ScanArgs& a, int io, hipStream_t st)
 {
     if (!varlen_scan_ok(a) || !slots_ok(a) || a.reverse || a.rev_n) return hipErrorInvalidValue;
-    constexpr size_t lds = (2 * 4 * TB * ROW + 64 + 2 * TB * ROW) * sizeof(float);
-    const dim3 grid(a.B * a.H), block(NWAVES * 64);
-    if (io == IO_F32) hipLaunchKernelGGL((scan_fwd_kernel<float, NWAVES, true>), grid, block, lds, st, a);
-    else if (io == IO_F16) hipLaunchKernelGGL((scan_fwd_kernel<f16_t, NWAVES, true>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((scan_fwd_kernel<bf16_t, NWAVES, true>), grid, block, lds, st, a);
-    return hipGetLastError();
+    return launch_scan_fwd_io<true, false>(a, io, st);
 }
 // ... with the final state in slot a.state_slot_out and the snapshots of wkv6_scan.h: SnapPlan
 hipError_t launch_scan_fwd_snap(const ScanArgs& a, int io, hipStream_t st)
 {
     if (!varlen_scan_ok(a) || !slots_ok(a) || !snap_ok(a) || a.reverse || a.rev_n) return hipErrorInvalidValue;
-    constexpr size_t lds = (2 * 4 * TB * ROW + 64 + 2 * TB * ROW) * sizeof(float);
-    const dim3 grid(a.B * a.H), block(NWAVES * 64);
-    if (io == IO_F32) hipLaunchKernelGGL((scan_fwd_kernel<float, NWAVES, false, true>), grid, block, lds, st, a);
-    else if (io == IO_F16) hipLaunchKernelGGL((scan_fwd_kernel<f16_t, NWAVES, false, true>), grid, block, lds, st, a);
-    else hipLaunchKernelGGL((scan_fwd_kernel<bf16_t, NWAVES, false, true>), grid, block, lds, st, a);
-    return hipGetLastError();
+    return launch_scan_fwd_io<false, true>(a, io, st);
 }
 
-hipError_t launch_selftest(int* result, hipStream_t st)
-{
-    hipLaunchKernelGGL(selftest_kernel, dim3(1), dim3(64), 0, st, result);
-    return hipGetLastError();
-}
+hipError_t launch_selftest(int* result, hipStream_t st) { return launch<selftest_kernel>(dim3(1), dim3(64), 0, st, result); }
 
 }  // namespace wkv6
