@@ -453,6 +453,36 @@ int wkv6_ddlerp_slots_forward(long total_T, int n_seq, int C, int NS, const int*
 int wkv6_shift_keep(long total_T, int n_seq, int max_seqlen, int C, const int* cu_seqlens, const void* x,
                     void* shift_pool, int n_slots, const int* slot_out,
                     int snap_every, const int* cu_snap, const int* snap_slot, int n_snap, void* stream);
+/* ---- per-sequence LoRA adapters on a packed batch (bf16, forward only; csrc/wkv6_lora.hip): the reference switches one adapter per call
+ * (src/layers.py: LoraLinear.set_adapter); here every sequence of the batch names its own, on the device, and the batch runs once.
+ *   x bf16 [total_T,K];  y bf16 [total_T,N], updated in place: it already holds x W^T of the base GEMM;
+ *   A_pool bf16 [n_adapters,R,K], B_pool bf16 [n_adapters,N,R] (the layout of nn.Linear weights = the reference's lora_A / lora_B);
+ *   scale fp32 [n_adapters] = alpha / r;  adapter int32 [n_seq] and cu_seqlens int32 [n_seq + 1] on the device, never read by the host.
+ * With a_s = clamp(cu_seqlens[s], 0, total_T), b_s = clamp(cu_seqlens[s+1], 0, total_T): a row t finds its sequence s by the varlen rule
+ * (the last s with cu_seqlens[s] <= t) and is served when a_s <= t < b_s -- every row of the sequence, no max_seqlen cut -- and
+ * a = adapter[s] lies in [0, n_adapters).  A served row gets
+ *     xa[t,j] = bf16( sum_k x[t,k] A[a,j,k] )                                  (fp32 accumulation, rounded to bf16 once)
+ *     y[t,n]  = bf16( fmaf(scale[a], sum_j xa[t,j] B[a,n,j], float(y[t,n])) )
+ * Every other row -- in no sequence, or of a sequence whose adapter lies outside the pool; -1 is the value for "base model only" -- keeps
+ * its bits: it is not read-modify-written.  The adapter number is judged before an address is formed from it, every cu_seqlens entry is
+ * clamped or compared before use: garbage in either int array touches no memory outside the arguments.  An adapter of lower rank is
+ * zero-padded to R by whoever fills the pools.
+ * Two launches in stream order, "shrink" (xa into the workspace, bf16 [total_T,R]) and "expand"; tiles of 16 packed rows on the 16x16x32
+ * bf16 MFMAs, operands straight from global memory.  Every output element is its own dot product: the split of K over the waves of a
+ * shrink workgroup depends on K alone and is summed in a fixed order, there are no atomics, so a row's result does not depend on the
+ * rows that share its tile or its batch -- a mixed batch equals one call per sequence bit for bit.  A tile that holds several adapters
+ * is served group by group, rows selected by lane, never masked by a multiply: a NaN or Inf in one adapter's matrices reaches only the
+ * rows that name it.
+ * wkv6_lora_packed_workspace_bytes: total_T * R * 2 rounded up to a multiple of 256; 0 for a total_T or an R the call refuses.
+ * Refused before any launch, in this order: (1) WKV6_EINVAL -- total_T, n_seq, n_adapters or R < 1, K or N not a multiple of 64 in
+ * [64, 16384]; (2) WKV6_EUNSUPPORTED -- R outside {8, 16, 32, 64}, total_T > INT_MAX; (3) WKV6_ENULL -- any NULL pointer (workspace
+ * included); (4) WKV6_EINVAL -- x, A_pool, B_pool, y or workspace not 16-byte aligned, cu_seqlens, adapter or scale not 4-byte aligned,
+ * y overlapping x, A_pool or B_pool; (5) WKV6_EWORKSPACE -- workspace_bytes below wkv6_lora_packed_workspace_bytes(total_T, R). */
+size_t wkv6_lora_packed_workspace_bytes(long total_T, int R);
+int wkv6_lora_packed_bf16(long total_T, int n_seq, int K, int N, int R, int n_adapters,
+                          const int* cu_seqlens, const int* adapter,
+                          const void* x, const void* A_pool, const void* B_pool, const float* scale,
+                          void* y, void* workspace, size_t workspace_bytes, void* stream);
 /* gn_gate (src/model.py:462-468): out = GroupNorm_H(y; gamma, beta, eps) * g on rows of C = 64 H channels (nn.GroupNorm(H, C)
  * applied to [rows, C]); stats fp32 [rows,H,2] (mean, rstd) is written for the backward (may be NULL in inference).
  * backward: dy, dg [rows,C]; dgamma_part, dbeta_part fp32 [nparts,C] partial sums. */

@@ -70,6 +70,8 @@ SIGNATURES = {
     "wkv6_ddlerp_varlen_backward": (_I, [_L] + [_I] * 3 + [_VP] * 9 + [_I, _VP]),
     "wkv6_ddlerp_slots_forward": (_I, [_L] + [_I] * 3 + [_VP] * 3 + [_I] + [_VP] * 5),
     "wkv6_shift_keep": (_I, [_L] + [_I] * 3 + [_VP] * 3 + [_I, _VP, _I, _VP, _VP, _I, _VP]),
+    "wkv6_lora_packed_workspace_bytes": (_SZ, [_L, _I]),
+    "wkv6_lora_packed_bf16": (_I, [_L] + [_I] * 5 + [_VP] * 8 + [_SZ, _VP]),
     "wkv6_ddlerp_forward": (_I, [_I] * 4 + [_VP] * 6),
     "wkv6_ddlerp_backward": (_I, [_I] * 4 + [_VP] * 8 + [_I, _VP]),
     "wkv6_ddlerp_rev_forward": (_I, [_I] * 4 + [_VP] * 7),

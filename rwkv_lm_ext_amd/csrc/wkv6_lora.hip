@@ -1,0 +1,274 @@
+// Per-sequence LoRA adapters on a packed batch (include/wkv6_amd.h: wkv6_lora_packed_bf16), hand-written for gfx950: the segmented
+// low-rank matmul behind a base GEMM.  Every sequence of the batch names its adapter on the device; a row t of sequence s with
+// a = adapter[s] inside the pool gets
+//     xa[t,j] = bf16( sum_k x[t,k] A[a,j,k] )                                  ("shrink",  A_pool bf16 [n_adapters,R,K])
+//     y[t,n]  = bf16( fmaf(scale[a], sum_j xa[t,j] B[a,n,j], float(y[t,n])) )   ("expand",  B_pool bf16 [n_adapters,N,R])
+// and every other row keeps its bits.  Two launches in stream order with the bf16 xa [total_T,R] between them in the workspace.
+//
+// Both kernels work on tiles of 16 packed rows with v_mfma_f32_16x16x32_bf16, the TOKEN as the MFMA column: lane (c = lane & 15,
+// g = lane >> 4) feeds 8 consecutive k of token c (one 16-byte global load of x[row] / xa[row]) and 8 consecutive k of pool row c
+// (one 16-byte load of A[a,j] / B[a,n]), and receives rows 4g..4g+3 of column c -- four consecutive j (or n) of its own token, which
+// leave as one wide store.  No LDS for the operands.  Every output element is its own dot product in the MFMA's own k order, so a
+// row's result does not depend on the rows beside it.
+//
+// A tile may hold up to 16 adapters (decode tokens).  Each wave finds the adapter of the tile's 16 rows (bisection in cu_seqlens, the
+// rule of the packed kernels of wkv6_mix.hip; the adapter number is judged before anything is addressed with it) and walks the GROUPS of
+// rows that share an adapter: one pass of MFMAs per group with that adapter's matrices, the token operand of rows outside the group a
+// literal zero, and only the lanes of the group's rows keep (select by lane) what the pass computed.  Nothing is masked by a multiply:
+// a NaN in adapter a's matrices stays in the discarded columns of a's pass.
+#include <climits>
+#include "wkv6_scan.h"                 // launch<>
+#include "../../include/wkv6_amd.h"
+
+namespace wkv6 {
+namespace {
+
+typedef __bf16 b8v __attribute__((ext_vector_type(8)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+constexpr int TILE = 16;               // packed rows per tile (the MFMA's 16 columns)
+constexpr int SHRINK_WAVES = 8;        // waves of a shrink workgroup: they share the (group, K chunk) work items of one tile
+constexpr int SHRINK_CHUNKS = 4;       // K is cut into min(4, K / 32) interleaved chunks of 32-wide steps: fixed by K alone
+constexpr int EXPAND_WAVES = 4;        // waves of an expand workgroup: wave w serves the tile's groups w, w + 4, ...
+constexpr int EXPAND_NB = 64;          // output columns per pass of a wave (4 MFMA tiles: 16 consecutive n per lane)
+constexpr int EXPAND_GRID_Y = 16;      // at most this many workgroups share a tile's N / 64 column blocks
+
+struct LoraArgs {
+    int total_T, n_seq, K, N, R, n_adapters;
+    const int* cu;            // [n_seq + 1]
+    const int* adapter;       // [n_seq]
+    const bf16_t* x;          // [total_T,K]
+    const bf16_t* A;          // [n_adapters,R,K]
+    const bf16_t* B;          // [n_adapters,N,R]
+    const float* scale;       // [n_adapters]
+    bf16_t* y;                // [total_T,N]
+    bf16_t* xa;               // [total_T,R]  (workspace)
+};
+
+// The packed-argument gate of the two launchers, kin of packed_arrays_ok (wkv6_scan.h): the int arrays and every tensor are there, the
+// sizes are ones the kernels have (the API refuses everything else with its own code before it gets here).
+inline bool lora_arrays_ok(const LoraArgs& a) { return a.cu && a.adapter && a.x && a.A && a.B && a.scale && a.y && a.xa; }
+inline bool lora_sizes_ok(const LoraArgs& a)
+{
+    return a.total_T >= 1 && a.n_seq >= 1 && a.n_adapters >= 1 && a.K >= 64 && a.K % 64 == 0 && a.N >= 64 && a.N % 64 == 0 &&
+           (a.R == 8 || a.R == 16 || a.R == 32 || a.R == 64);
+}
+
+// the last s < n_seq with cu[s] <= r, -1: none (seq_of_row of wkv6_mix.hip)
+__device__ __forceinline__ int seq_of_row(const int* __restrict__ cu, int n_seq, long r)
+{
+    int lo = 0, hi = n_seq;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long)cu[mid] <= r) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo - 1;
+}
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// Adapter of packed row `row`, -1: the row is not served (outside [0,total_T), in no sequence, or its sequence's adapter lies outside the
+// pool).  Row t belongs to sequence s = seq_of_row(t) when a_s <= t < b_s with the bounds clamped into [0,total_T]; the adapter number is
+// judged here, before any address is formed from it.
+__device__ __forceinline__ int row_adapter(const LoraArgs& a, long row)
+{
+    if (row >= a.total_T) return -1;
+    const int s = seq_of_row(a.cu, a.n_seq, row);
+    if (s < 0) return -1;
+    if (row < clampi(a.cu[s], 0, a.total_T) || row >= clampi(a.cu[s + 1], 0, a.total_T)) return -1;
+    const int ad = a.adapter[s];
+    return ad >= 0 && ad < a.n_adapters ? ad : -1;
+}
+
+__device__ __forceinline__ b8v zero8() { return __builtin_bit_cast(b8v, v4u{0u, 0u, 0u, 0u}); }
+__device__ __forceinline__ b8v load8(const bf16_t* p) { return __builtin_bit_cast(b8v, *reinterpret_cast<const v4u*>(p)); }
+__device__ __forceinline__ f4v mfma32(b8v a, b8v b, f4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+// Walks the groups of equal adapter among the tile's 16 rows (`mine`: the adapter of row lane & 15, -1: none; the four 16-lane rows of
+// the wave hold copies).  f(index, adapter, in_group): adapter is wave-uniform, in_group per lane.
+template <typename F> __device__ __forceinline__ void for_each_group(int mine, F f)
+{
+    unsigned todo = (unsigned)__ballot(mine >= 0) & 0xffffu;
+    for (int gi = 0; todo; ++gi) {
+        const int first = __ffs(todo) - 1;
+        const int ad = __builtin_amdgcn_readlane(mine, first);
+        const bool in = mine == ad;
+        todo &= ~((unsigned)__ballot(in) & 0xffffu);
+        f(gi, ad, in);
+    }
+}
+
+// ---- shrink: xa = bf16(x A[a]^T).  One workgroup per (tile of 16 rows, 16 columns j of xa); MFMA rows = j, columns = tokens, so lane
+// (c, g) ends with xa[row c][j0 + 4g .. + 3].  The work items of a tile are (group, K chunk): chunk q takes the 32-wide k steps q, q + NCH,
+// q + 2 NCH, ... with NCH = min(4, K / 32) -- fixed by K alone -- and the items go round the waves.  An item leaves its fp32 partial sums
+// in LDS at [chunk][token][j] (a token is in one group only, so the items never meet), and after the barrier wave 0 adds a token's chunks
+// in the order 0, 1, 2, 3, rounds once and stores.  Rows of R that do not exist (R = 8: j = 8..15) are literal zeros, never loaded; a
+// token outside the group, or past total_T, is a literal zero too.
+template <int R>
+__global__ void __launch_bounds__(SHRINK_WAVES * 64) lora_shrink_kernel(const LoraArgs a)
+{
+    __shared__ float part[SHRINK_CHUNKS][TILE][16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const long row = (long)blockIdx.x * TILE + c;
+    const int j = blockIdx.y * 16 + c;                   // the pool row this lane feeds
+    const bool j_ok = j < R;
+    const int mine = row_adapter(a, row);
+    const int nsteps = a.K / 32, nch = min(SHRINK_CHUNKS, nsteps);
+    const bf16_t* xr = a.x + row * a.K + 8 * g;          // (formed, not dereferenced, for rows that are not served)
+    int item = 0;
+    for_each_group(mine, [&](int, int ad, bool in) {
+        const bf16_t* ar = a.A + ((long)ad * R + (j_ok ? j : 0)) * a.K + 8 * g;
+        for (int q = 0; q < nch; ++q, ++item) {
+            if (item % SHRINK_WAVES != wave) continue;
+            f4v acc = {0.f, 0.f, 0.f, 0.f};
+            int s = q;
+            for (; s + 3 * nch < nsteps; s += 4 * nch) {               // four steps' loads in flight
+                b8v af[4], xf[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int k = 32 * (s + u * nch);
+                    af[u] = j_ok ? load8(ar + k) : zero8();
+                    xf[u] = in ? load8(xr + k) : zero8();
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) acc = mfma32(af[u], xf[u], acc);
+            }
+            for (; s < nsteps; s += nch) {
+                const b8v af = j_ok ? load8(ar + 32 * s) : zero8();
+                const b8v xf = in ? load8(xr + 32 * s) : zero8();
+                acc = mfma32(af, xf, acc);
+            }
+            if (in) *reinterpret_cast<float4*>(&part[q][c][4 * g]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        }
+    });
+    __syncthreads();
+    const int j0 = blockIdx.y * 16 + 4 * g;
+    if (wave == 0 && mine >= 0 && j0 < R) {
+        float4 sum = *reinterpret_cast<const float4*>(&part[0][c][4 * g]);
+        for (int q = 1; q < nch; ++q) {
+            const float4 p = *reinterpret_cast<const float4*>(&part[q][c][4 * g]);
+            sum.x += p.x; sum.y += p.y; sum.z += p.z; sum.w += p.w;
+        }
+        *reinterpret_cast<v2u*>(a.xa + row * R + j0) = v2u{pack_bf2(sum.x, sum.y), pack_bf2(sum.z, sum.w)};
+    }
+}
+
+// ---- expand: y = bf16(fmaf(scale[a], xa B[a]^T, y)).  One workgroup per tile of 16 rows and share of the N / 64 column blocks; wave w
+// serves the tile's groups w, w + 4, ...  MFMA rows = n, columns = tokens, contraction over j: one step of 32 for R <= 32 (for R = 8 and
+// 16 the lanes whose 8 j lie past R hold literal zeros in both operands), two for R = 64.  MFMA row rho of tile i stands for column
+// n0 + 16 (rho >> 2) + 4 i + (rho & 3), so that lane (c, g) ends with the 16 CONSECUTIVE columns n0 + 16 g .. + 15 of its token: the
+// read-modify-write of y is two 16-byte accesses per lane, 128 contiguous bytes per token.  Only the lanes of the group's rows touch y.
+template <int R>
+__global__ void __launch_bounds__(EXPAND_WAVES * 64) lora_expand_kernel(const LoraArgs a)
+{
+    constexpr int STEPS = R == 64 ? 2 : 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const long row = (long)blockIdx.x * TILE + c;
+    const int mine = row_adapter(a, row);
+    const bool j_ok = 8 * g < R;                         // (R >= 32: every lane)
+    const int nblocks = a.N / EXPAND_NB;
+    for_each_group(mine, [&](int gi, int ad, bool in) {
+        if (gi % EXPAND_WAVES != wave) return;
+        const float sc = a.scale[ad];
+        b8v xf[STEPS];
+#pragma unroll
+        for (int st = 0; st < STEPS; ++st) xf[st] = in && j_ok ? load8(a.xa + row * R + 32 * st + 8 * g) : zero8();
+        const bf16_t* bp = a.B + (long)ad * a.N * R + 8 * g;
+        for (int nb = blockIdx.y; nb < nblocks; nb += gridDim.y) {
+            const int n0 = nb * EXPAND_NB;
+            f4v acc[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int n = n0 + 16 * (c >> 2) + 4 * i + (c & 3);
+                acc[i] = f4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int st = 0; st < STEPS; ++st) {
+                    const b8v bf = j_ok ? load8(bp + (long)n * R + 32 * st) : zero8();
+                    acc[i] = mfma32(bf, xf[st], acc[i]);
+                }
+            }
+            if (in) {
+                v4u* yp = reinterpret_cast<v4u*>(a.y + row * a.N + n0 + 16 * g);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const v4u old = yp[h];
+                    v4u out;
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {        // word p of half h: columns 8 h + 2 p, + 1 = tile i = 2 h + (p >> 1), rows 2 (p & 1), + 1
+                        const int i = 2 * h + (p >> 1), q = 2 * (p & 1);
+                        out[p] = pack_bf2(fmaf(sc, acc[i][q], bf_lo(old[p])), fmaf(sc, acc[i][q + 1], bf_hi(old[p])));
+                    }
+                    yp[h] = out;
+                }
+            }
+        }
+    });
+}
+
+template <int R> hipError_t launch_lora(const LoraArgs& a, hipStream_t st)
+{
+    const unsigned tiles = (unsigned)(((long)a.total_T + TILE - 1) / TILE);
+    if (hipError_t e = launch<lora_shrink_kernel<R>>(dim3(tiles, (R + 15) / 16), dim3(SHRINK_WAVES * 64), 0, st, a)) return e;
+    return launch<lora_expand_kernel<R>>(dim3(tiles, min(a.N / EXPAND_NB, EXPAND_GRID_Y)), dim3(EXPAND_WAVES * 64), 0, st, a);
+}
+
+// shrink, then expand, in stream order
+hipError_t launch_lora_packed(const LoraArgs& a, hipStream_t st)
+{
+    if (!lora_arrays_ok(a) || !lora_sizes_ok(a)) return hipErrorInvalidValue;
+    switch (a.R) {
+    case 8: return launch_lora<8>(a, st);
+    case 16: return launch_lora<16>(a, st);
+    case 32: return launch_lora<32>(a, st);
+    default: return launch_lora<64>(a, st);
+    }
+}
+
+bool overlap(const void* p, size_t pn, const void* q, size_t qn)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + qn && b < a + pn;
+}
+bool rank_ok(int R) { return R == 8 || R == 16 || R == 32 || R == 64; }
+
+}  // namespace
+}  // namespace wkv6
+
+using namespace wkv6;
+
+extern "C" {
+
+size_t wkv6_lora_packed_workspace_bytes(long total_T, int R)
+{
+    if (total_T < 1 || total_T > 0x7fffffffL || !rank_ok(R)) return 0;
+    return ((size_t)total_T * R * 2 + 255) & ~(size_t)255;
+}
+
+int wkv6_lora_packed_bf16(long total_T, int n_seq, int K, int N, int R, int n_adapters, const int* cu_seqlens, const int* adapter,
+                          const void* x, const void* A_pool, const void* B_pool, const float* scale, void* y, void* workspace,
+                          size_t workspace_bytes, void* stream)
+{
+    // the order of the refusals is part of the contract (include/wkv6_amd.h)
+    if (total_T < 1 || n_seq < 1 || n_adapters < 1 || R < 1) return WKV6_EINVAL;
+    if (K < 64 || K % 64 || K > 16384 || N < 64 || N % 64 || N > 16384) return WKV6_EINVAL;
+    if (!rank_ok(R) || total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;           // cu_seqlens is int32
+    if (!cu_seqlens || !adapter || !x || !A_pool || !B_pool || !scale || !y || !workspace) return WKV6_ENULL;
+    if (((uintptr_t)x | (uintptr_t)A_pool | (uintptr_t)B_pool | (uintptr_t)y | (uintptr_t)workspace) & 15) return WKV6_EINVAL;
+    if (((uintptr_t)cu_seqlens | (uintptr_t)adapter | (uintptr_t)scale) & 3) return WKV6_EINVAL;
+    const size_t y_bytes = (size_t)total_T * N * 2, need = wkv6_lora_packed_workspace_bytes(total_T, R);
+    if (overlap(y, y_bytes, x, (size_t)total_T * K * 2) || overlap(y, y_bytes, A_pool, (size_t)n_adapters * R * K * 2) ||
+        overlap(y, y_bytes, B_pool, (size_t)n_adapters * N * R * 2))
+        return WKV6_EINVAL;
+    if (workspace_bytes < need) return WKV6_EWORKSPACE;
+    LoraArgs a = {};
+    a.total_T = (int)total_T; a.n_seq = n_seq; a.K = K; a.N = N; a.R = R; a.n_adapters = n_adapters;
+    a.cu = cu_seqlens; a.adapter = adapter;
+    a.x = (const bf16_t*)x; a.A = (const bf16_t*)A_pool; a.B = (const bf16_t*)B_pool; a.scale = scale;
+    a.y = (bf16_t*)y; a.xa = (bf16_t*)workspace;
+    const hipError_t e = launch_lora_packed(a, (hipStream_t)stream);
+    return e == hipSuccess ? WKV6_OK : (int)e;
+}
+
+}  // extern "C"

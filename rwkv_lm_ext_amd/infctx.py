@@ -252,7 +252,12 @@ def block_forward_packed(block, x, cu_seqlens, max_seqlen, pools, layer, slots, 
 
 
 def step_packed(blocks, x, cu_seqlens, max_seqlen, pools, slots, out_slots=None, snap=None, seg_len=0, pool_kernels=None):
-    """block_forward_packed over a stack of blocks, block i on layer i of the pools."""
+    """block_forward_packed over a stack of blocks, block i on layer i of the pools.
+
+    Per-sequence LoRA adapters need nothing here: under adapters.inject_adapters the blocks' linears are MultiLoraLinear modules, and
+    adapters.set_adapters(blocks, cu_seqlens, adapter) binds the batch on them before the call -- this function, block_forward_packed and
+    the sub-layer functions reach the linears through the modules.  The two tensors are bound by reference, so a captured step is
+    re-routed by refilling them in place."""
     for layer, block in enumerate(blocks):
         x = block_forward_packed(block, x, cu_seqlens, max_seqlen, pools, layer, slots, out_slots=out_slots, snap=snap, seg_len=seg_len,
                                  pool_kernels=pool_kernels)

@@ -298,6 +298,57 @@ def shift_keep(x, cu_seqlens, max_seqlen, shift_pool, slot_out, snap=None):
     _lib.check(rc, "shift keep")
 
 
+# ---- per-sequence LoRA adapters on a packed batch (include/wkv6_amd.h: wkv6_lora_packed_bf16); inference only: no autograd.  Shapes and
+# types are judged first, the device last (there is no CPU path here: adapters.MultiLoraLinear has the eager one).
+LORA_RANKS = (8, 16, 32, 64)
+
+
+def lora_packed(x, y, A_pool, B_pool, scale, adapter, cu_seqlens):
+    """y[t] += scale[a] * (bf16(x[t] A_pool[a]^T)) B_pool[a]^T for every row t of a sequence whose a = adapter[s] lies in the pool, in place
+    on y (which holds the base GEMM's x W^T); every other row keeps its bits.  x bf16 [.., total_T, K] and y bf16 [.., total_T, N] (leading
+    dimensions of size 1 only, as a packed batch has), A_pool bf16 [n_adapters, R, K], B_pool bf16 [n_adapters, N, R], scale fp32
+    [n_adapters], adapter int32 [n_seq], cu_seqlens int32 [n_seq + 1]; R in LORA_RANKS.  Returns y.  The workspace is a torch tensor, so a
+    graph capture owns it.  Raises when a gradient is required."""
+    bf = torch.bfloat16
+    if not (isinstance(x, torch.Tensor) and x.dtype == bf and x.dim() in (2, 3) and (x.dim() == 2 or x.shape[0] == 1) and x.is_contiguous()):
+        raise RuntimeError("x must be a contiguous bf16 tensor [1, total_T, K] (or [total_T, K])")
+    K, total = x.shape[-1], x.shape[-2]
+    if not (isinstance(y, torch.Tensor) and y.dtype == bf and y.dim() == x.dim() and tuple(y.shape[:-1]) == tuple(x.shape[:-1])
+            and y.is_contiguous()):
+        raise RuntimeError(f"y must be a contiguous bf16 tensor {list(x.shape[:-1]) + ['N']} (it is updated in place, never copied)")
+    N = y.shape[-1]
+    if not (isinstance(A_pool, torch.Tensor) and A_pool.dtype == bf and A_pool.dim() == 3 and A_pool.shape[2] == K and A_pool.is_contiguous()):
+        raise RuntimeError(f"A_pool must be a contiguous bf16 tensor [n_adapters, R, K = {K}]")
+    n_adapters, R = A_pool.shape[0], A_pool.shape[1]
+    if not (isinstance(B_pool, torch.Tensor) and B_pool.dtype == bf and tuple(B_pool.shape) == (n_adapters, N, R) and B_pool.is_contiguous()):
+        raise RuntimeError(f"B_pool must be a contiguous bf16 tensor [n_adapters = {n_adapters}, N = {N}, R = {R}]")
+    if not (isinstance(scale, torch.Tensor) and scale.dtype == torch.float32 and tuple(scale.shape) == (n_adapters,) and scale.is_contiguous()):
+        raise RuntimeError(f"scale must be a contiguous fp32 tensor [n_adapters = {n_adapters}]")
+    if R not in LORA_RANKS:
+        raise RuntimeError(f"lora_packed: R must be one of {LORA_RANKS} (zero-pad a lower rank), got {R}")
+    if total < 1 or n_adapters < 1 or K % 64 or N % 64 or not (64 <= K <= 16384 and 64 <= N <= 16384):
+        raise RuntimeError("lora_packed: total_T and n_adapters must be >= 1, K and N multiples of 64 in [64, 16384]")
+    if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
+            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2):
+        raise RuntimeError("cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of x")
+    n_seq = cu_seqlens.numel() - 1
+    _check_ints(adapter, (n_seq,), "adapter")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, A_pool, B_pool, scale)):
+        raise RuntimeError("lora_packed has no backward: call it under torch.no_grad() (adapters.MultiLoraLinear's eager path has autograd)")
+    if not x.is_cuda:
+        raise RuntimeError("x must be on the GPU (lora_packed has no CPU path)")
+    if any(t.device != x.device for t in (y, A_pool, B_pool, scale, adapter, cu_seqlens)):
+        raise RuntimeError("y, A_pool, B_pool, scale, adapter and cu_seqlens must be on the device of x")
+    lib = _lib.load()
+    nbytes = lib.wkv6_lora_packed_workspace_bytes(total, R)
+    work = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    with torch.cuda.device(x.device):
+        rc = lib.wkv6_lora_packed_bf16(total, n_seq, K, N, R, n_adapters, _ptr(cu_seqlens), _ptr(adapter), _ptr(x), _ptr(A_pool), _ptr(B_pool),
+                                       _ptr(scale), _ptr(y), _ptr(work), nbytes, _stream_ptr())
+    _lib.check(rc, "lora packed")
+    return y
+
+
 def gn_gate_forward(y, g, gamma, beta, H, eps):
     """(out, stats): out = GroupNorm_H(y) * g on [rows, C]; stats fp32 [rows, H, 2] = mean, rstd (for gn_gate_backward)."""
     y, g, gamma, beta = _require(y, "y"), _require(g, "g"), _require(gamma, "gamma"), _require(beta, "beta")
