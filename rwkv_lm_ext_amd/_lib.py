@@ -138,17 +138,18 @@ def load():
 _selftested = set()
 
 
-def selftest_once(device_index, stream_ptr):
+def selftest_once(device_index, on_device):
     """Run wkv6_selftest the first time a device is used (cross-lane primitives, then the chunked MFMA kernels against
     the exact scan kernels): a mis-scheduled build fails loudly here instead of training silently wrong.
-    RWKV_AMD_NO_SELFTEST=1 skips it."""
+    RWKV_AMD_NO_SELFTEST=1 skips it.  on_device(device_index, fn) calls fn(stream) with that device current and returns its result; it is
+    used on a device's first call only, every later one returns from the test below without a lock."""
     if device_index in _selftested:
         return
     with _lock:
         if device_index in _selftested:
             return
         if os.environ.get("RWKV_AMD_NO_SELFTEST", "0") != "1":
-            rc = _lib.wkv6_selftest(stream_ptr)
+            rc = on_device(device_index, _lib.wkv6_selftest)
             if rc != 0:
                 raise RuntimeError(f"librwkv6_amd.so failed its device self-test on cuda:{device_index} (code {rc}); "
                                    "the build is unusable on this device")

@@ -8,7 +8,9 @@ forward and backward are one HIP kernel each; parameter gradients come back as f
 import torch
 
 from . import _lib
-from .wkv6_op import _ptr, _stream_ptr                   # same pointer / stream conventions as the operator
+from ._args import _AT_LEAST_2, _call, _ints, _ptr, _ptrs          # same pointer / stream / checking conventions as the operator
+
+_CU_SEQLENS = "cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of x"
 
 _NPARTS = 1024
 
@@ -29,15 +31,11 @@ class _DDLerp(torch.autograd.Function):
         m = None if m is None else _require(m, "m")
         shifted0 = None if shifted0 is None else _require(shifted0, "shifted0")
         B, T, C = x.shape
-        if rev_n is not None and not (rev_n.dtype == torch.int32 and rev_n.is_contiguous() and tuple(rev_n.shape) == (B,)
-                                      and rev_n.device == x.device):
-            raise RuntimeError("rev_n must be a contiguous int32 [B] tensor on the device of x")
+        if rev_n is not None:
+            _ints(rev_n, (B,), x.device, "rev_n must be a contiguous int32 [B] tensor on the device of x")
         NS = maa.shape[0]
         out = torch.empty((NS, B, T, C), device=x.device, dtype=x.dtype)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().wkv6_ddlerp_rev_forward(B, T, C, NS, _ptr(x), _ptr(shifted0), _ptr(m), _ptr(maa), _ptr(rev_n),
-                                                     _ptr(out), _stream_ptr())
-        _lib.check(rc, "ddlerp forward")
+        _call("wkv6_ddlerp_rev_forward", "ddlerp forward", x.device, B, T, C, NS, *_ptrs(x, shifted0, m, maa, rev_n, out))
         ctx.save_for_backward(x, maa, m, shifted0, rev_n)
         return out
 
@@ -51,10 +49,7 @@ class _DDLerp(torch.autograd.Function):
         dx = torch.empty_like(x)
         dm = None if m is None else torch.empty_like(m)
         part = torch.empty((nparts, NS, C), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().wkv6_ddlerp_rev_backward(B, T, C, NS, _ptr(x), _ptr(shifted0), _ptr(m), _ptr(maa), _ptr(rev_n),
-                                                      _ptr(dout), _ptr(dx), _ptr(dm), _ptr(part), nparts, _stream_ptr())
-        _lib.check(rc, "ddlerp backward")
+        _call("wkv6_ddlerp_rev_backward", "ddlerp backward", x.device, B, T, C, NS, *_ptrs(x, shifted0, m, maa, rev_n, dout, dx, dm, part), nparts)
         dshift = None
         if shifted0 is not None and ctx.needs_input_grad[3]:
             # The token in front of the row (the infctx carry: the previous chunk's last token, src/model.py:1134-1190 passes the
@@ -72,90 +67,34 @@ class _DDLerp(torch.autograd.Function):
         return dx, part.sum(0).to(maa.dtype), dm, dshift, None
 
 
-def _check_cu(cu_seqlens, device):
-    if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
-            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2 and cu_seqlens.device == device):
-        raise RuntimeError("cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of x")
-    return cu_seqlens.numel() - 1
-
-
 class _DDLerpVarlen(torch.autograd.Function):
     """_DDLerp on a packed variable-length batch: x [1,total_T,C] (or [total_T,C]), m [NS,*x.shape] or None, cu_seqlens int32
-    [n_seq + 1]; the token in front of sequence s is shifted0[s] ([n_seq,C], None: zero), never the last token of sequence s - 1."""
-
-    @staticmethod
-    def forward(ctx, x, maa, m, shifted0, cu_seqlens):
-        x, maa = _require(x, "x"), _require(maa, "maa")
-        m = None if m is None else _require(m, "m")
-        shifted0 = None if shifted0 is None else _require(shifted0, "shifted0")
-        n_seq = _check_cu(cu_seqlens, x.device)
-        C = x.shape[-1]
-        total = x.numel() // C
-        if x.dim() == 3 and x.shape[0] != 1:
-            raise RuntimeError("a packed batch is [1, total_T, C] (or [total_T, C])")
-        if shifted0 is not None and tuple(shifted0.shape) != (n_seq, C):
-            raise RuntimeError(f"shifted0 must be [n_seq, C] = {(n_seq, C)}")
-        NS = maa.shape[0]
-        out = torch.empty((NS,) + tuple(x.shape), device=x.device, dtype=x.dtype)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().wkv6_ddlerp_varlen_forward(total, n_seq, C, NS, _ptr(cu_seqlens), _ptr(x), _ptr(shifted0), _ptr(m),
-                                                        _ptr(maa), _ptr(out), _stream_ptr())
-        _lib.check(rc, "ddlerp varlen forward")
-        ctx.save_for_backward(x, maa, m, shifted0, cu_seqlens)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, maa, m, shifted0, cu = ctx.saved_tensors
-        dout = _require(dout, "dout")
-        C = x.shape[-1]
-        total = x.numel() // C
-        n_seq = cu.numel() - 1
-        NS = maa.shape[0]
-        nparts = min(_NPARTS, total)
-        dx = torch.empty_like(x)
-        dm = None if m is None else torch.empty_like(m)
-        part = torch.empty((nparts, NS, C), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().wkv6_ddlerp_varlen_backward(total, n_seq, C, NS, _ptr(cu), _ptr(x), _ptr(shifted0), _ptr(m), _ptr(maa),
-                                                         _ptr(dout), _ptr(dx), _ptr(dm), _ptr(part), nparts, _stream_ptr())
-        _lib.check(rc, "ddlerp varlen backward")
-        dshift = None
-        if shifted0 is not None and ctx.needs_input_grad[3]:
-            # shifted0[s] enters only the first token of a non-empty sequence s (no host read of cu_seqlens: index arithmetic on the device)
-            first = cu[:-1].long().clamp(0, total - 1)
-            alive = (cu[1:] > cu[:-1]).view(1, n_seq, 1).float()
-            d0 = dout.reshape(NS, total, C)[:, first].float()
-            wgt = maa.float().view(NS, 1, C) + (0.0 if m is None else m.reshape(NS, total, C)[:, first].float())
-            dshift = ((d0 * wgt) * alive).sum(0).to(shifted0.dtype)
-        return dx, part.sum(0).to(maa.dtype), dm, dshift, None
-
-
-class _DDLerpVarlenRev(torch.autograd.Function):
-    """_DDLerpVarlen with the shift of sequence s taken over the stream "its first rev_n[s] tokens reversed, the rest in place"
-    (rev_n int32 [n_seq], clamped to the sequence's length on the device)."""
+    [n_seq + 1]; the token in front of sequence s is shifted0[s] ([n_seq,C], None: zero), never the last token of sequence s - 1.
+    rev_n (int32 [n_seq], clamped to the sequence's length on the device, or None): the shift of sequence s is taken over the stream
+    "its first rev_n[s] tokens reversed, the rest in place".  Without rev_n the plain entry points are called, not the rev ones with a
+    null map."""
 
     @staticmethod
     def forward(ctx, x, maa, m, shifted0, cu_seqlens, rev_n):
         x, maa = _require(x, "x"), _require(maa, "maa")
         m = None if m is None else _require(m, "m")
         shifted0 = None if shifted0 is None else _require(shifted0, "shifted0")
-        n_seq = _check_cu(cu_seqlens, x.device)
+        n_seq = _ints(cu_seqlens, _AT_LEAST_2, x.device, _CU_SEQLENS).numel() - 1
         C = x.shape[-1]
         total = x.numel() // C
         if x.dim() == 3 and x.shape[0] != 1:
             raise RuntimeError("a packed batch is [1, total_T, C] (or [total_T, C])")
         if shifted0 is not None and tuple(shifted0.shape) != (n_seq, C):
             raise RuntimeError(f"shifted0 must be [n_seq, C] = {(n_seq, C)}")
-        if not (isinstance(rev_n, torch.Tensor) and rev_n.dtype == torch.int32 and rev_n.is_contiguous()
-                and tuple(rev_n.shape) == (n_seq,) and rev_n.device == x.device):
-            raise RuntimeError("rev_n must be a contiguous int32 [n_seq] tensor on the device of x")
+        if rev_n is not None:
+            _ints(rev_n, (n_seq,), x.device, "rev_n must be a contiguous int32 [n_seq] tensor on the device of x")
         NS = maa.shape[0]
         out = torch.empty((NS,) + tuple(x.shape), device=x.device, dtype=x.dtype)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().wkv6_ddlerp_varlen_rev_forward(total, n_seq, C, NS, _ptr(cu_seqlens), _ptr(x), _ptr(shifted0), _ptr(m),
-                                                            _ptr(maa), _ptr(rev_n), _ptr(out), _stream_ptr())
-        _lib.check(rc, "ddlerp varlen rev forward")
+        if rev_n is None:
+            _call("wkv6_ddlerp_varlen_forward", "ddlerp varlen forward", x.device, total, n_seq, C, NS, *_ptrs(cu_seqlens, x, shifted0, m, maa, out))
+        else:
+            _call("wkv6_ddlerp_varlen_rev_forward", "ddlerp varlen rev forward", x.device, total, n_seq, C, NS,
+                  *_ptrs(cu_seqlens, x, shifted0, m, maa, rev_n, out))
         ctx.save_for_backward(x, maa, m, shifted0, cu_seqlens, rev_n)
         return out
 
@@ -171,23 +110,29 @@ class _DDLerpVarlenRev(torch.autograd.Function):
         dx = torch.empty_like(x)
         dm = None if m is None else torch.empty_like(m)
         part = torch.empty((nparts, NS, C), device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().wkv6_ddlerp_varlen_rev_backward(total, n_seq, C, NS, _ptr(cu), _ptr(x), _ptr(shifted0), _ptr(m), _ptr(maa),
-                                                             _ptr(rev_n), _ptr(dout), _ptr(dx), _ptr(dm), _ptr(part), nparts,
-                                                             _stream_ptr())
-        _lib.check(rc, "ddlerp varlen rev backward")
+        if rev_n is None:
+            _call("wkv6_ddlerp_varlen_backward", "ddlerp varlen backward", x.device, total, n_seq, C, NS,
+                  *_ptrs(cu, x, shifted0, m, maa, dout, dx, dm, part), nparts)
+        else:
+            _call("wkv6_ddlerp_varlen_rev_backward", "ddlerp varlen rev backward", x.device, total, n_seq, C, NS,
+                  *_ptrs(cu, x, shifted0, m, maa, rev_n, dout, dx, dm, part), nparts)
         dshift = None
         if shifted0 is not None and ctx.needs_input_grad[3]:
             # shifted0[s] enters only the stream's first token of a non-empty sequence s: cu[s] + rev_n[s] - 1 where a reversed span opens
-            # the stream, else cu[s] (device index arithmetic only: nobody reads cu_seqlens or rev_n on the host)
-            start = cu[:-1].long().clamp(0, total)
-            length = (cu[1:].long().clamp(0, total) - start).clamp_min(0)
-            nrev = torch.minimum(rev_n.long().clamp_min(0), length)
-            first = (start + (nrev - 1).clamp_min(0)).clamp(0, total - 1)
-            alive = (length > 0).view(1, n_seq, 1).float()
+            # the stream, else cu[s] (device index arithmetic only: nobody reads cu_seqlens or rev_n on the host).  The two forms agree on
+            # every cu_seqlens the kernels accept and clamp a malformed one differently, so each keeps its own.
+            if rev_n is None:
+                first = cu[:-1].long().clamp(0, total - 1)
+                alive = cu[1:] > cu[:-1]
+            else:
+                start = cu[:-1].long().clamp(0, total)
+                length = (cu[1:].long().clamp(0, total) - start).clamp_min(0)
+                nrev = torch.minimum(rev_n.long().clamp_min(0), length)
+                first = (start + (nrev - 1).clamp_min(0)).clamp(0, total - 1)
+                alive = length > 0
             d0 = dout.reshape(NS, total, C)[:, first].float()
             wgt = maa.float().view(NS, 1, C) + (0.0 if m is None else m.reshape(NS, total, C)[:, first].float())
-            dshift = ((d0 * wgt) * alive).sum(0).to(shifted0.dtype)
+            dshift = ((d0 * wgt) * alive.view(1, n_seq, 1).float()).sum(0).to(shifted0.dtype)
         return dx, part.sum(0).to(maa.dtype), dm, dshift, None, None
 
 
@@ -196,9 +141,7 @@ def ddlerp(x, maa, m=None, shifted0=None, rev_n=None, cu_seqlens=None):
     variable-length batch [1,total_T,C] and the shift does not cross a sequence boundary (shifted0 is then [n_seq,C]); rev_n is then
     int32 [n_seq]: the reversed span of every sequence's stream."""
     if cu_seqlens is not None:
-        if rev_n is not None:
-            return _DDLerpVarlenRev.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, cu_seqlens, rev_n)
-        return _DDLerpVarlen.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, cu_seqlens)
+        return _DDLerpVarlen.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, cu_seqlens, rev_n)
     return _DDLerp.apply(x, maa.reshape(-1, x.shape[-1]), m, shifted0, rev_n)
 
 
@@ -206,9 +149,7 @@ def ddlerp(x, maa, m=None, shifted0=None, rev_n=None, cu_seqlens=None):
 # inference only: no autograd.  Shapes and types are judged first, the device last (there is no CPU path).
 def _check_ints(t, shape, name):
     """shape None: any 1-d length.  The device is judged by the caller, behind every shape."""
-    if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous()
-            and (t.dim() == 1 if shape is None else tuple(t.shape) == shape)):
-        raise RuntimeError(f"{name} must be a contiguous int32 {'1-d' if shape is None else list(shape)} tensor on the device of x")
+    _ints(t, shape, None, f"{name} must be a contiguous int32 {'1-d' if shape is None else list(shape)} tensor on the device of x")
 
 
 def _check_packed(x, shift_pool, cu_seqlens):
@@ -221,10 +162,7 @@ def _check_packed(x, shift_pool, cu_seqlens):
     if not (isinstance(shift_pool, torch.Tensor) and shift_pool.dtype == torch.bfloat16 and shift_pool.dim() == 2
             and shift_pool.shape[1] == C and shift_pool.is_contiguous()):
         raise RuntimeError(f"shift_pool must be a contiguous bf16 tensor [n_slots, C = {C}] (it is used in place, never copied)")
-    if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
-            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2):
-        raise RuntimeError("cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of x")
-    return x.numel() // C, C, cu_seqlens.numel() - 1, shift_pool.shape[0]
+    return x.numel() // C, C, _ints(cu_seqlens, _AT_LEAST_2, None, _CU_SEQLENS).numel() - 1, shift_pool.shape[0]
 
 
 def _check_gpu(x, shift_pool, cu_seqlens):
@@ -258,10 +196,8 @@ def ddlerp_slots(x, maa, m, shift_pool, slots, cu_seqlens):
         raise RuntimeError("maa, m and slots must be on the device of x")
     x, m = x.contiguous(), None if m is None else m.contiguous()
     out = torch.empty((NS,) + tuple(x.shape), device=x.device, dtype=x.dtype)
-    with torch.cuda.device(x.device):
-        rc = _lib.load().wkv6_ddlerp_slots_forward(total, n_seq, C, NS, _ptr(cu_seqlens), _ptr(x), _ptr(shift_pool), n_slots, _ptr(slots),
-                                                   _ptr(m), _ptr(maa), _ptr(out), _stream_ptr())
-    _lib.check(rc, "ddlerp slots forward")
+    _call("wkv6_ddlerp_slots_forward", "ddlerp slots forward", x.device, total, n_seq, C, NS, *_ptrs(cu_seqlens, x, shift_pool), n_slots,
+          *_ptrs(slots, m, maa, out))
     return out
 
 
@@ -292,10 +228,8 @@ def shift_keep(x, cu_seqlens, max_seqlen, shift_pool, slot_out, snap=None):
         if t is not None and t.device != x.device:
             raise RuntimeError(f"{name} must be a contiguous int32 tensor on the device of x")
     x, n_snap = x.contiguous(), 0 if snap_slots is None else snap_slots.numel()
-    with torch.cuda.device(x.device):
-        rc = _lib.load().wkv6_shift_keep(total, n_seq, min(max_seqlen, 0x7fffffff), C, _ptr(cu_seqlens), _ptr(x), _ptr(shift_pool), n_slots,
-                                         _ptr(slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slots), n_snap, _stream_ptr())
-    _lib.check(rc, "shift keep")
+    _call("wkv6_shift_keep", "shift keep", x.device, total, n_seq, min(max_seqlen, 0x7fffffff), C, *_ptrs(cu_seqlens, x, shift_pool), n_slots,
+          _ptr(slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slots), n_snap)
 
 
 # ---- per-sequence LoRA adapters on a packed batch (include/wkv6_amd.h: wkv6_lora_packed_bf16); inference only: no autograd.  Shapes and
@@ -328,10 +262,7 @@ def lora_packed(x, y, A_pool, B_pool, scale, adapter, cu_seqlens):
         raise RuntimeError(f"lora_packed: R must be one of {LORA_RANKS} (zero-pad a lower rank), got {R}")
     if total < 1 or n_adapters < 1 or K % 64 or N % 64 or not (64 <= K <= 16384 and 64 <= N <= 16384):
         raise RuntimeError("lora_packed: total_T and n_adapters must be >= 1, K and N multiples of 64 in [64, 16384]")
-    if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
-            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2):
-        raise RuntimeError("cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of x")
-    n_seq = cu_seqlens.numel() - 1
+    n_seq = _ints(cu_seqlens, _AT_LEAST_2, None, _CU_SEQLENS).numel() - 1
     _check_ints(adapter, (n_seq,), "adapter")
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, A_pool, B_pool, scale)):
         raise RuntimeError("lora_packed has no backward: call it under torch.no_grad() (adapters.MultiLoraLinear's eager path has autograd)")
@@ -339,13 +270,10 @@ def lora_packed(x, y, A_pool, B_pool, scale, adapter, cu_seqlens):
         raise RuntimeError("x must be on the GPU (lora_packed has no CPU path)")
     if any(t.device != x.device for t in (y, A_pool, B_pool, scale, adapter, cu_seqlens)):
         raise RuntimeError("y, A_pool, B_pool, scale, adapter and cu_seqlens must be on the device of x")
-    lib = _lib.load()
-    nbytes = lib.wkv6_lora_packed_workspace_bytes(total, R)
+    nbytes = _lib.load().wkv6_lora_packed_workspace_bytes(total, R)
     work = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-    with torch.cuda.device(x.device):
-        rc = lib.wkv6_lora_packed_bf16(total, n_seq, K, N, R, n_adapters, _ptr(cu_seqlens), _ptr(adapter), _ptr(x), _ptr(A_pool), _ptr(B_pool),
-                                       _ptr(scale), _ptr(y), _ptr(work), nbytes, _stream_ptr())
-    _lib.check(rc, "lora packed")
+    _call("wkv6_lora_packed_bf16", "lora packed", x.device, total, n_seq, K, N, R, n_adapters,
+          *_ptrs(cu_seqlens, adapter, x, A_pool, B_pool, scale, y, work), nbytes)
     return y
 
 
@@ -356,10 +284,7 @@ def gn_gate_forward(y, g, gamma, beta, H, eps):
     rows = y.numel() // C
     out = torch.empty_like(y)
     stats = torch.empty((rows, H, 2), device=y.device, dtype=torch.float32)
-    with torch.cuda.device(y.device):
-        rc = _lib.load().wkv6_gn_gate_forward(rows, C, H, _ptr(y), _ptr(g), _ptr(gamma), _ptr(beta), float(eps),
-                                              _ptr(out), _ptr(stats), _stream_ptr())
-    _lib.check(rc, "gn_gate forward")
+    _call("wkv6_gn_gate_forward", "gn_gate forward", y.device, rows, C, H, *_ptrs(y, g, gamma, beta), float(eps), _ptr(out), _ptr(stats))
     return out, stats
 
 
@@ -372,10 +297,7 @@ def gn_gate_backward(y, g, gamma, beta, stats, dout, H):
     dy, dg = torch.empty_like(y), torch.empty_like(g)
     pg = torch.empty((nparts, C), device=y.device, dtype=torch.float32)
     pb = torch.empty((nparts, C), device=y.device, dtype=torch.float32)
-    with torch.cuda.device(y.device):
-        rc = _lib.load().wkv6_gn_gate_backward(rows, C, H, _ptr(y), _ptr(g), _ptr(gamma), _ptr(beta), _ptr(stats),
-                                               _ptr(dout), _ptr(dy), _ptr(dg), _ptr(pg), _ptr(pb), nparts, _stream_ptr())
-    _lib.check(rc, "gn_gate backward")
+    _call("wkv6_gn_gate_backward", "gn_gate backward", y.device, rows, C, H, *_ptrs(y, g, gamma, beta, stats, dout, dy, dg, pg, pb), nparts)
     return dy, dg, pg.sum(0).to(gamma.dtype), pb.sum(0).to(beta.dtype)
 
 
@@ -407,9 +329,7 @@ class _SqRelu(torch.autograd.Function):
     def forward(ctx, x):
         x = _require(x, "x")
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().wkv6_sqrelu_forward(x.numel(), _ptr(x), _ptr(out), _stream_ptr())
-        _lib.check(rc, "sqrelu forward")
+        _call("wkv6_sqrelu_forward", "sqrelu forward", x.device, x.numel(), _ptr(x), _ptr(out))
         ctx.save_for_backward(x)
         return out
 
@@ -418,9 +338,7 @@ class _SqRelu(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         dout = _require(dout, "dout")
         dx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            rc = _lib.load().wkv6_sqrelu_backward(x.numel(), _ptr(x), _ptr(dout), _ptr(dx), _stream_ptr())
-        _lib.check(rc, "sqrelu backward")
+        _call("wkv6_sqrelu_backward", "sqrelu backward", x.device, x.numel(), _ptr(x), _ptr(dout), _ptr(dx))
         return dx
 
 
@@ -433,9 +351,7 @@ class _SigMul(torch.autograd.Function):
         if r.shape != kv.shape:
             raise RuntimeError("sigmoid_mul: r and kv must have the same shape")
         out = torch.empty_like(r)
-        with torch.cuda.device(r.device):
-            rc = _lib.load().wkv6_sigmul_forward(r.numel(), _ptr(r), _ptr(kv), _ptr(out), _stream_ptr())
-        _lib.check(rc, "sigmul forward")
+        _call("wkv6_sigmul_forward", "sigmul forward", r.device, r.numel(), _ptr(r), _ptr(kv), _ptr(out))
         ctx.save_for_backward(r, kv)
         return out
 
@@ -444,9 +360,7 @@ class _SigMul(torch.autograd.Function):
         r, kv = ctx.saved_tensors
         dout = _require(dout, "dout")
         dr, dkv = torch.empty_like(r), torch.empty_like(kv)
-        with torch.cuda.device(r.device):
-            rc = _lib.load().wkv6_sigmul_backward(r.numel(), _ptr(r), _ptr(kv), _ptr(dout), _ptr(dr), _ptr(dkv), _stream_ptr())
-        _lib.check(rc, "sigmul backward")
+        _call("wkv6_sigmul_backward", "sigmul backward", r.device, r.numel(), *_ptrs(r, kv, dout, dr, dkv))
         return dr, dkv
 
 

@@ -17,22 +17,21 @@ in-place output convention and dtypes:
 They are also registered as ``torch.ops.wkv6.forward`` etc. (the reference's TORCH_LIBRARY blocks,
 cuda/wkv6_op.cpp:19-22).  Unlike the reference shims (which check nothing) every call validates
 device, dtype, contiguity and shape and launches on the current stream of the tensors' device.
+
+Every wrapper is made of the pieces of _args.py (whose docstring states what must not change): `_named` builds the table that
+`_check_tensors` judges, `_ints` judges an int32 array, `_flags` builds the flag word and `_call` is the one way into the library.
 """
 import contextlib
+import ctypes
 
 import torch
 
 from . import _lib
+from ._args import (_AT_LEAST_2, HEAD_SIZE, _call, _flags, _ints, _io_of, _named, _on_device, _ptr, _ptrs, _s0_entry, _stream_ptr,   # noqa: F401
+                    _workspace_or_ckpt)
 
-HEAD_SIZE = 64
-
-
-def _stream_ptr():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_SUFFIX = {torch.bfloat16: "bf16", torch.float16: "fp16", torch.float32: "fp32"}      # of the rwkv6_* symbols
+_CU_SEQLENS = "cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of r"
 
 
 def _check_tensors(B, T, C, H, named, dtype=torch.bfloat16):
@@ -54,9 +53,7 @@ def _check_tensors(B, T, C, H, named, dtype=torch.bfloat16):
     if C != H * HEAD_SIZE:
         raise RuntimeError(f"C ({C}) must equal H*{HEAD_SIZE} ({H * HEAD_SIZE})")   # reference: assert(H*_N_ == C)
     _lib.load()
-    if dev.index not in _lib._selftested:
-        with torch.cuda.device(dev):
-            _lib.selftest_once(dev.index, _stream_ptr())
+    _lib.selftest_once(dev.index, _on_device)
     return dev
 
 
@@ -65,27 +62,17 @@ class _Wkv6:
 
     @staticmethod
     def forward(B, T, C, H, r, k, v, w, u, y):
-        btc = (B, T, C)
-        dev = _check_tensors(B, T, C, H, dict(r=(r, btc, None), k=(k, btc, None), v=(v, btc, None),
-                                              w=(w, btc, torch.float32), u=(u, None, None), y=(y, btc, None)))
-        with torch.cuda.device(dev):
-            rc = _lib.load().wkv6_cuda_forward(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y),
-                                               _stream_ptr())
-        _lib.check(rc, "wkv6 forward")
+        dev = _check_tensors(B, T, C, H, _named((B, T, C), None, r, k, v, w, u, wdt=torch.float32, y=y))
+        _call("wkv6_cuda_forward", "wkv6 forward", dev, B, T, C, H, *_ptrs(r, k, v, w, u, y))
 
     @staticmethod
     def backward(B, T, C, H, r, k, v, w, u, gy, gr, gk, gv, gw, gu):
-        btc = (B, T, C)
-        dev = _check_tensors(B, T, C, H, dict(
-            r=(r, btc, None), k=(k, btc, None), v=(v, btc, None), w=(w, btc, torch.float32), u=(u, None, None),
-            gy=(gy, btc, None), gr=(gr, btc, None), gk=(gk, btc, None), gv=(gv, btc, None), gw=(gw, btc, None),
-            gu=(gu, (B, C), None)))
-        ws = torch.empty(_lib.load().wkv6_backward_workspace_bytes(B, T, C, H), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().wkv6_backward_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), None,
-                                              _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu), None,
-                                              _ptr(ws), ws.numel(), _lib.W_EW_F32, _stream_ptr())
-        _lib.check(rc, "wkv6 backward")
+        named = _named((B, T, C), None, r, k, v, w, u, wdt=torch.float32, gy=gy, gr=gr, gk=gk, gv=gv, gw=gw)
+        named["gu"] = (gu, (B, C), None)
+        dev = _check_tensors(B, T, C, H, named)
+        ws = new_checkpoint(B, T, C, H, dev)
+        _call("wkv6_backward_ex", "wkv6 backward", dev, B, T, C, H, *_ptrs(r, k, v, w, u, None, gy, gr, gk, gv, gw, gu, None, ws),
+              ws.numel(), _lib.W_EW_F32)
 
 
 class _Wkv6Bi:
@@ -93,29 +80,19 @@ class _Wkv6Bi:
 
     @staticmethod
     def forward(B, T, C, H, mask, r, k, v, w, u, y):
-        btc = (B, T, C)
-        dev = _check_tensors(B, T, C, H, dict(mask=(mask, (B, T), torch.int32), r=(r, btc, None), k=(k, btc, None),
-                                              v=(v, btc, None), w=(w, btc, torch.float32), u=(u, None, None),
-                                              y=(y, btc, None)))
-        ws = torch.empty(_lib.load().wkv6bi_workspace_bytes(B, T, C, H), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().wkv6bi_forward_ex(B, T, C, H, _ptr(mask), None, _ptr(r), _ptr(k), _ptr(v), _ptr(w),
-                                               _ptr(u), _ptr(y), _ptr(ws), ws.numel(), _lib.W_EW_F32, _stream_ptr())
-        _lib.check(rc, "wkv6_bi forward")
+        named = {"mask": (mask, (B, T), torch.int32), **_named((B, T, C), None, r, k, v, w, u, wdt=torch.float32, y=y)}
+        dev = _check_tensors(B, T, C, H, named)
+        ws = bi_new_workspace(B, T, C, H, dev)
+        _call("wkv6bi_forward_ex", "wkv6_bi forward", dev, B, T, C, H, *_ptrs(mask, None, r, k, v, w, u, y, ws), ws.numel(), _lib.W_EW_F32)
 
     @staticmethod
     def backward(B, T, C, H, mask, r, k, v, w, u, gy, gr, gk, gv, gw, gu):
-        btc = (B, T, C)
-        dev = _check_tensors(B, T, C, H, dict(
-            mask=(mask, (B, T), torch.int32), r=(r, btc, None), k=(k, btc, None), v=(v, btc, None),
-            w=(w, btc, torch.float32), u=(u, None, None), gy=(gy, btc, None), gr=(gr, btc, None),
-            gk=(gk, btc, None), gv=(gv, btc, None), gw=(gw, btc, None), gu=(gu, (B, C), None)))
-        ws = torch.empty(_lib.load().wkv6bi_workspace_bytes(B, T, C, H), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().wkv6bi_backward_ex(B, T, C, H, _ptr(mask), None, _ptr(r), _ptr(k), _ptr(v), _ptr(w),
-                                                _ptr(u), _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw),
-                                                _ptr(gu), _ptr(ws), ws.numel(), _lib.W_EW_F32, _stream_ptr())
-        _lib.check(rc, "wkv6_bi backward")
+        named = {"mask": (mask, (B, T), torch.int32),
+                 **_named((B, T, C), None, r, k, v, w, u, wdt=torch.float32, gy=gy, gr=gr, gk=gk, gv=gv, gw=gw), "gu": (gu, (B, C), None)}
+        dev = _check_tensors(B, T, C, H, named)
+        ws = bi_new_workspace(B, T, C, H, dev)
+        _call("wkv6bi_backward_ex", "wkv6_bi backward", dev, B, T, C, H, *_ptrs(mask, None, r, k, v, w, u, gy, gr, gk, gv, gw, gu, ws),
+              ws.numel(), _lib.W_EW_F32)
 
 
 class _Wkv6State:
@@ -124,34 +101,22 @@ class _Wkv6State:
     _name = "wkv6state"
 
     @classmethod
-    def _s_shape(cls, B, H):
-        return (B, H, HEAD_SIZE, HEAD_SIZE) if cls._per_batch else (H, HEAD_SIZE, HEAD_SIZE)
+    def _s(cls, s, B, H):
+        return {"s": (s, (B, H, HEAD_SIZE, HEAD_SIZE) if cls._per_batch else (H, HEAD_SIZE, HEAD_SIZE), None)}
 
     @classmethod
     def forward(cls, B, T, C, H, r, k, v, w, u, s, y):
-        btc = (B, T, C)
-        dev = _check_tensors(B, T, C, H, dict(r=(r, btc, None), k=(k, btc, None), v=(v, btc, None), w=(w, btc, None),
-                                              u=(u, None, None), s=(s, cls._s_shape(B, H), None), y=(y, btc, None)))
-        fn = getattr(_lib.load(), cls._name + "_cuda_forward")
-        with torch.cuda.device(dev):
-            rc = fn(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(s), _ptr(y), _stream_ptr())
-        _lib.check(rc, cls._name + " forward")
+        dev = _check_tensors(B, T, C, H, _named((B, T, C), None, r, k, v, w, u, then=cls._s(s, B, H), y=y))
+        _call(cls._name + "_cuda_forward", cls._name + " forward", dev, B, T, C, H, *_ptrs(r, k, v, w, u, s, y))
 
     @classmethod
     def backward(cls, B, T, C, H, r, k, v, w, u, s, gy, gr, gk, gv, gw, gu, gs):
-        btc = (B, T, C)
-        dev = _check_tensors(B, T, C, H, dict(
-            r=(r, btc, None), k=(k, btc, None), v=(v, btc, None), w=(w, btc, None), u=(u, None, None),
-            s=(s, cls._s_shape(B, H), None), gy=(gy, btc, None), gr=(gr, btc, None), gk=(gk, btc, None),
-            gv=(gv, btc, None), gw=(gw, btc, None), gu=(gu, (B, C), None),
-            gs=(gs, (B, H, HEAD_SIZE, HEAD_SIZE), None)))
-        flags = _lib.W_RAW | (_lib.S0_PER_BATCH if cls._per_batch else 0)
-        ws = torch.empty(_lib.load().wkv6_backward_workspace_bytes(B, T, C, H), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().wkv6_backward_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(s),
-                                              _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu), _ptr(gs),
-                                              _ptr(ws), ws.numel(), flags, _stream_ptr())
-        _lib.check(rc, cls._name + " backward")
+        named = _named((B, T, C), None, r, k, v, w, u, then=cls._s(s, B, H), gy=gy, gr=gr, gk=gk, gv=gv, gw=gw)
+        named["gu"], named["gs"] = (gu, (B, C), None), (gs, (B, H, HEAD_SIZE, HEAD_SIZE), None)
+        dev = _check_tensors(B, T, C, H, named)
+        ws = new_checkpoint(B, T, C, H, dev)
+        _call("wkv6_backward_ex", cls._name + " backward", dev, B, T, C, H, *_ptrs(r, k, v, w, u, s, gy, gr, gk, gv, gw, gu, gs, ws),
+              ws.numel(), _lib.W_RAW | (_lib.S0_PER_BATCH if cls._per_batch else 0))
 
 
 class _Wkv6Infctx(_Wkv6State):
@@ -166,32 +131,25 @@ class _Rwkv6:
     forward_bf16 / forward_fp32 (B,T,C,H, state[f32], r,k,v, eew[f32 decay], u, y); state updated in place."""
 
     @staticmethod
-    def _call(B, T, C, H, state, r, k, v, w, u, y, io):
-        btc = (B, T, C)
+    def _forward(B, T, C, H, state, r, k, v, w, u, y, io):
         sshape = None if state.numel() == B * H * HEAD_SIZE * HEAD_SIZE else (-1,)
-        dev = _check_tensors(B, T, C, H, dict(state=(state, sshape, torch.float32), r=(r, btc, io), k=(k, btc, io),
-                                              v=(v, btc, io), w=(w, btc, torch.float32), u=(u, None, io), y=(y, btc, io)),
-                             dtype=io)
-        lib = _lib.load()
-        fn = {torch.bfloat16: lib.rwkv6_cuda_forward_bf16, torch.float16: lib.rwkv6_cuda_forward_fp16,
-              torch.float32: lib.rwkv6_cuda_forward_fp32}[io]
-        with torch.cuda.device(dev):
-            rc = fn(B, T, C, H, _ptr(state), _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _stream_ptr())
-        _lib.check(rc, "rwkv6 forward")
+        named = {"state": (state, sshape, torch.float32), **_named((B, T, C), io, r, k, v, w, u, wdt=torch.float32, y=y)}
+        dev = _check_tensors(B, T, C, H, named, dtype=io)
+        _call("rwkv6_cuda_forward_" + _SUFFIX[io], "rwkv6 forward", dev, B, T, C, H, *_ptrs(state, r, k, v, w, u, y))
 
     @staticmethod
     def forward_bf16(B, T, C, H, state, r, k, v, w, u, y):
-        _Rwkv6._call(B, T, C, H, state, r, k, v, w, u, y, torch.bfloat16)
+        _Rwkv6._forward(B, T, C, H, state, r, k, v, w, u, y, torch.bfloat16)
 
     @staticmethod
     def forward_fp32(B, T, C, H, state, r, k, v, w, u, y):
-        _Rwkv6._call(B, T, C, H, state, r, k, v, w, u, y, torch.float32)
+        _Rwkv6._forward(B, T, C, H, state, r, k, v, w, u, y, torch.float32)
 
     @staticmethod
     def forward_fp16(B, T, C, H, state, r, k, v, w, u, y):
         """cuda/rwkv6_op.cpp:16-19: r, k, v, u, y in fp16; the kernel widens the inputs to fp32 (exact), computes and carries the
         state in fp32 and rounds y to fp16 once (cuda/rwkv6.cu:8-71)."""
-        _Rwkv6._call(B, T, C, H, state, r, k, v, w, u, y, torch.float16)
+        _Rwkv6._forward(B, T, C, H, state, r, k, v, w, u, y, torch.float16)
 
     # ---- packed batches with a state-slot pool (include/wkv6_amd.h: rwkv6_forward_varlen_*) ----
     @staticmethod
@@ -207,9 +165,8 @@ class _Rwkv6:
         seg_len (0, or a multiple of 64; bf16 on the chunked route only): every sequence longer than seg_len tokens is cut at multiples of
         seg_len and served by one workgroup per (segment, head) (include/wkv6_amd.h: rwkv6_forward_varlen_split_bf16); ws is then a
         new_rwkv6_varlen_split_workspace() buffer.  seg_len > 0 or force_split: the split entry point."""
-        tc = (total_T, C)
-        named = dict(state_pool=(state_pool, None, torch.float32), r=(r, tc, io), k=(k, tc, io), v=(v, tc, io),
-                     w=(w, tc, torch.float32), u=(u, (H, HEAD_SIZE), io), y=(y, tc, io))
+        named = {"state_pool": (state_pool, None, torch.float32),
+                 **_named((total_T, C), io, r, k, v, w, u, wdt=torch.float32, ushape=(H, HEAD_SIZE), y=y)}
         for name, (t, _, dt) in named.items():      # (types first: what is wrong with a tensor is reported whatever device it is on)
             if not isinstance(t, torch.Tensor):
                 raise TypeError(f"{name} must be a tensor")
@@ -223,22 +180,15 @@ class _Rwkv6:
         if state_pool.dim() != 4 or tuple(state_pool.shape[1:]) != (H, HEAD_SIZE, HEAD_SIZE) or state_pool.shape[0] < 1:
             raise RuntimeError(f"state_pool has shape {tuple(state_pool.shape)}, expected (n_slots, {H}, {HEAD_SIZE}, {HEAD_SIZE})")
         n_slots = state_pool.numel() // per_slot
-        n_seq = _check_cu_seqlens(cu_seqlens, r.device)
+        n_seq = _ints(cu_seqlens, _AT_LEAST_2, r.device, _CU_SEQLENS).numel() - 1
         if state_slot is None:
             if n_slots < n_seq:
                 raise RuntimeError(f"state_slot=None names slot s for sequence s: the pool has {n_slots} slots for {n_seq} sequences")
-        elif not (isinstance(state_slot, torch.Tensor) and state_slot.dtype == torch.int32 and state_slot.is_contiguous()
-                  and tuple(state_slot.shape) == (n_seq,) and state_slot.device == r.device):
-            raise RuntimeError("state_slot must be a contiguous int32 [n_seq] tensor on the device of r, or None")
+        else:
+            _ints(state_slot, (n_seq,), r.device, "state_slot must be a contiguous int32 [n_seq] tensor on the device of r, or None")
         if ws is not None and not (isinstance(ws, torch.Tensor) and ws.dtype == torch.uint8 and ws.is_contiguous()
                                    and ws.device == r.device):
             raise RuntimeError("ws must be a new_rwkv6_varlen_workspace() buffer on the device of r")
-
-        def int_array(name, t, shape, what):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1
-                    and (shape is None or tuple(t.shape) == shape) and t.device == r.device):
-                raise RuntimeError(f"{name} must be a contiguous int32 {what} tensor on the device of r")
-
         if not isinstance(seg_len, int) or isinstance(seg_len, bool) or seg_len < 0 or seg_len % 64 != 0:
             raise RuntimeError(f"seg_len must be 0 or a multiple of 64, got {seg_len!r}")
         if seg_len > 0 and algo == "scan":
@@ -252,78 +202,65 @@ class _Rwkv6:
             if not isinstance(snap_every, int) or snap_every < 0 or snap_every % 64 != 0:
                 raise RuntimeError(f"snap_every must be 0 or a multiple of 64, got {snap_every!r}")
             if state_slot_out is not None:
-                int_array("state_slot_out", state_slot_out, (n_seq,), "[n_seq]")
+                _ints(state_slot_out, (n_seq,), r.device, "state_slot_out must be a contiguous int32 [n_seq] tensor on the device of r")
             if snap_every == 0:
                 if cu_snap is not None or snap_slot is not None:
                     raise RuntimeError("cu_snap and snap_slot belong to snap_every > 0")
             else:
-                int_array("cu_snap", cu_snap, (n_seq + 1,), "[n_seq + 1]")
-                int_array("snap_slot", snap_slot, None, "[n_snap]")
+                _ints(cu_snap, (n_seq + 1,), r.device, "cu_snap must be a contiguous int32 [n_seq + 1] tensor on the device of r")
+                _ints(snap_slot, None, r.device, "snap_slot must be a contiguous int32 [n_snap] tensor on the device of r")
         dev = _check_tensors(n_seq, total_T, C, H, named, dtype=io)
-        lib = _lib.load()
-        base = (int(total_T), n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(state_slot), n_slots, _ptr(state_pool), _ptr(r),
-                _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _ptr(ws), 0 if ws is None else ws.numel(),
-                _lib.ALGO_SCAN if algo == "scan" else 0)
-        with torch.cuda.device(dev):
-            if split:
-                rc = lib.rwkv6_forward_varlen_split_bf16(*base, _stream_ptr(), _ptr(state_slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slot),
-                                                         0 if snap_slot is None else snap_slot.numel(), seg_len)
-            elif snap:
-                fn = {torch.bfloat16: lib.rwkv6_forward_varlen_snap_bf16, torch.float16: lib.rwkv6_forward_varlen_snap_fp16,
-                      torch.float32: lib.rwkv6_forward_varlen_snap_fp32}[io]
-                rc = fn(*base, _stream_ptr(), _ptr(state_slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slot),
-                        0 if snap_slot is None else snap_slot.numel())
-            else:
-                fn = {torch.bfloat16: lib.rwkv6_forward_varlen_bf16, torch.float16: lib.rwkv6_forward_varlen_fp16,
-                      torch.float32: lib.rwkv6_forward_varlen_fp32}[io]
-                rc = fn(*base, _stream_ptr())
-        _lib.check(rc, "rwkv6 forward_varlen")
+        base = (int(total_T), n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(state_slot), n_slots, *_ptrs(state_pool, r, k, v, w, u, y, ws),
+                0 if ws is None else ws.numel(), _lib.ALGO_SCAN if algo == "scan" else 0)
+        if not snap:
+            _call("rwkv6_forward_varlen_" + _SUFFIX[io], "rwkv6 forward_varlen", dev, *base)
+            return
+        tail = (_ptr(state_slot_out), snap_every, _ptr(cu_snap), _ptr(snap_slot), 0 if snap_slot is None else snap_slot.numel())   # behind the stream
+        if split:
+            _call("rwkv6_forward_varlen_split_bf16", "rwkv6 forward_varlen", dev, *base, tail=tail + (seg_len,))
+        else:
+            _call("rwkv6_forward_varlen_snap_" + _SUFFIX[io], "rwkv6 forward_varlen", dev, *base, tail=tail)
 
-    @staticmethod
-    def forward_varlen_bf16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None,
-                            state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None, seg_len=0):
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.bfloat16,
-                            state_slot_out, snap_every, cu_snap, snap_slot, seg_len=seg_len)
 
-    @staticmethod
-    def forward_varlen_split_bf16(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
-                                  cu_snap, snap_slot, seg_len, ws=None):
+# rwkv6.forward_varlen_{bf16,fp16,fp32}, forward_varlen_snap_{bf16,fp16,fp32} and forward_varlen_split_bf16: one definition per kind, made once
+# per I/O type.  Only bf16 can cut sequences, so only its plain form has a seg_len (the others refuse the keyword as any unknown one).
+def _varlen_plain(io):
+    if io == torch.bfloat16:
+        def fn(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None, state_slot_out=None,
+               snap_every=0, cu_snap=None, snap_slot=None, seg_len=0):
+            _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, io, state_slot_out,
+                                snap_every, cu_snap, snap_slot, seg_len=seg_len)
+    else:
+        def fn(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None, state_slot_out=None,
+               snap_every=0, cu_snap=None, snap_slot=None):
+            _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, io, state_slot_out,
+                                snap_every, cu_snap, snap_slot)
+    return fn
+
+
+def _varlen_snap(io):
+    def fn(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every, cu_snap, snap_slot):
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, None, io, state_slot_out,
+                            snap_every, cu_snap, snap_slot, force_snap=True)
+    fn.__doc__ = f"torch.ops.rwkv6.forward_varlen_snap_{_SUFFIX[io]}: always the snap entry point of the library, defaults included."
+    return fn
+
+
+def _varlen_split(io):
+    def fn(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every, cu_snap, snap_slot,
+           seg_len, ws=None):
         """torch.ops.rwkv6.forward_varlen_split_bf16: always the split entry point of the library, seg_len = 0 included."""
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, ws, torch.bfloat16,
-                            state_slot_out, snap_every, cu_snap, snap_slot, seg_len=seg_len, force_split=True)
+        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, ws, io, state_slot_out,
+                            snap_every, cu_snap, snap_slot, seg_len=seg_len, force_split=True)
+    return fn
 
-    @staticmethod
-    def forward_varlen_snap_bf16(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
-                                 cu_snap, snap_slot):
-        """torch.ops.rwkv6.forward_varlen_snap_bf16: always the snap entry point of the library, defaults included."""
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, None, torch.bfloat16,
-                            state_slot_out, snap_every, cu_snap, snap_slot, force_snap=True)
 
-    @staticmethod
-    def forward_varlen_fp16(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None,
-                            state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None):
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.float16,
-                            state_slot_out, snap_every, cu_snap, snap_slot)
-
-    @staticmethod
-    def forward_varlen_snap_fp16(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
-                                 cu_snap, snap_slot):
-        """torch.ops.rwkv6.forward_varlen_snap_fp16: always the snap entry point of the library, defaults included."""
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, None, torch.float16,
-                            state_slot_out, snap_every, cu_snap, snap_slot, force_snap=True)
-
-    @staticmethod
-    def forward_varlen_fp32(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo=None, ws=None,
-                            state_slot_out=None, snap_every=0, cu_snap=None, snap_slot=None):
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, algo, ws, torch.float32,
-                            state_slot_out, snap_every, cu_snap, snap_slot)
-
-    @staticmethod
-    def forward_varlen_snap_fp32(total_T, C, H, state_pool, state_slot, state_slot_out, r, k, v, w, u, y, cu_seqlens, max_seqlen, snap_every,
-                                 cu_snap, snap_slot):
-        """torch.ops.rwkv6.forward_varlen_snap_fp32: always the snap entry point of the library, defaults included."""
-        _Rwkv6._call_varlen(total_T, C, H, state_pool, state_slot, r, k, v, w, u, y, cu_seqlens, max_seqlen, None, None, torch.float32,
-                            state_slot_out, snap_every, cu_snap, snap_slot, force_snap=True)
+for _kind, _make, _ios in (("", _varlen_plain, _SUFFIX), ("snap_", _varlen_snap, _SUFFIX), ("split_", _varlen_split, (torch.bfloat16,))):
+    for _io in _ios:
+        _fn = _make(_io)
+        _fn.__name__ = f"forward_varlen_{_kind}{_SUFFIX[_io]}"
+        _fn.__qualname__ = "_Rwkv6." + _fn.__name__          # as a method written out in the class would read in a TypeError
+        setattr(_Rwkv6, _fn.__name__, staticmethod(_fn))
 
 
 class _Wkv5:
@@ -333,24 +270,18 @@ class _Wkv5:
 
     @staticmethod
     def forward(B, T, C, H, r, k, v, w, u, y):
-        btc, hn = (B, T, C), (H, HEAD_SIZE)
-        dev = _check_tensors(B, T, C, H, dict(r=(r, btc, None), k=(k, btc, None), v=(v, btc, None),
-                                              w=(w, hn, torch.float32), u=(u, hn, None), y=(y, btc, None)))
-        with torch.cuda.device(dev):
-            rc = _lib.load().wkv5_cuda_forward(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _stream_ptr())
-        _lib.check(rc, "wkv5 forward")
+        hn = (H, HEAD_SIZE)
+        dev = _check_tensors(B, T, C, H, _named((B, T, C), None, r, k, v, w, u, wdt=torch.float32, wshape=hn, ushape=hn, y=y))
+        _call("wkv5_cuda_forward", "wkv5 forward", dev, B, T, C, H, *_ptrs(r, k, v, w, u, y))
 
     @staticmethod
     def backward(B, T, C, H, r, k, v, w, ww, u, gy, gr, gk, gv, gw, gu):
         btc, hn = (B, T, C), (H, HEAD_SIZE)
-        dev = _check_tensors(B, T, C, H, dict(
+        dev = _check_tensors(B, T, C, H, dict(        # (ww stands between w and u: not the head of _named)
             r=(r, btc, None), k=(k, btc, None), v=(v, btc, None), w=(w, hn, torch.float32), ww=(ww, hn, torch.float32),
             u=(u, hn, None), gy=(gy, btc, None), gr=(gr, btc, None), gk=(gk, btc, None), gv=(gv, btc, None),
             gw=(gw, (B, C), None), gu=(gu, (B, C), None)))
-        with torch.cuda.device(dev):
-            rc = _lib.load().wkv5_cuda_backward(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(ww), _ptr(u), _ptr(gy),
-                                                _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu), _stream_ptr())
-        _lib.check(rc, "wkv5 backward")
+        _call("wkv5_cuda_backward", "wkv5 backward", dev, B, T, C, H, *_ptrs(r, k, v, w, ww, u, gy, gr, gk, gv, gw, gu))
 
 
 rwkv6 = _Rwkv6
@@ -371,33 +302,23 @@ def new_checkpoint(B, T, C, H, device):
 def forward_ex(r, k, v, w, u, H, s0=None, s_out=None, w_is_ew=False, y=None, algo=None, ckpt=None):
     """y = WKV6(r,k,v,w,u[,s0]) with the I/O type of `r` (bf16, or fp32 for numerics tests).
     algo: None (library default: chunked MFMA kernel for bf16 I/O) or "scan" (exact token-serial kernels)."""
-    B, T, C = r.shape
-    io = r.dtype
-    if io not in (torch.bfloat16, torch.float32):
-        raise RuntimeError(f"unsupported I/O dtype {io}")
-    btc = (B, T, C)
-    wdt = torch.float32 if w_is_ew else io
-    named = dict(r=(r, btc, io), k=(k, btc, io), v=(v, btc, io), w=(w, btc, wdt), u=(u, (H, HEAD_SIZE), io))
-    flags = (_lib.W_EW_F32 if w_is_ew else _lib.W_RAW) | (_lib.IO_F32 if io == torch.float32 else 0)
-    flags |= _lib.ALGO_SCAN if algo == "scan" else 0
+    B, T, C = btc = r.shape
+    io = _io_of(r)
+    named = _named(btc, io, r, k, v, w, u, wdt=torch.float32 if w_is_ew else io, ushape=(H, HEAD_SIZE))
+    flags = _flags(io, w_is_ew, algo)
     if s0 is not None:
-        per_batch = s0.dim() == 4
-        named["s0"] = (s0, (B, H, HEAD_SIZE, HEAD_SIZE) if per_batch else (H, HEAD_SIZE, HEAD_SIZE), io)
-        flags |= _lib.S0_PER_BATCH if per_batch else 0
+        named["s0"], per_batch = _s0_entry(s0, B, H, io)
+        flags |= per_batch
     if s_out is not None:
         named["s_out"] = (s_out, (B, H, HEAD_SIZE, HEAD_SIZE), io)
     if y is None:
         y = torch.empty(btc, device=r.device, dtype=io)
     named["y"] = (y, btc, io)
     dev = _check_tensors(B, T, C, H, named, dtype=io)
-    with torch.cuda.device(dev):
-        if ckpt is not None:       # training forward: also store the per-group state checkpoints for the backward
-            rc = _lib.load().wkv6_forward_ckpt_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(s0),
-                                                  _ptr(s_out), _ptr(y), _ptr(ckpt), ckpt.numel(), flags, _stream_ptr())
-        else:
-            rc = _lib.load().wkv6_forward_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(s0),
-                                             _ptr(s_out), _ptr(y), flags, _stream_ptr())
-    _lib.check(rc, "wkv6 forward_ex")
+    if ckpt is not None:       # training forward: also store the per-group state checkpoints for the backward
+        _call("wkv6_forward_ckpt_ex", "wkv6 forward_ex", dev, B, T, C, H, *_ptrs(r, k, v, w, u, s0, s_out, y, ckpt), ckpt.numel(), flags)
+    else:
+        _call("wkv6_forward_ex", "wkv6 forward_ex", dev, B, T, C, H, *_ptrs(r, k, v, w, u, s0, s_out, y), flags)
     return y
 
 
@@ -405,19 +326,16 @@ def forward_gn_ex(r, k, v, w, u, H, gate, gamma, beta, eps, ckpt=None, want_y=Tr
     """The operator with the time-mix block's GroupNorm(H) * gate epilogue fused into its store (src/model.py:462-468, SURVEY.md
     row n1).  Returns (out, y or None, stats or None), or None where the library cannot fuse (so few (batch, head) pairs that
     two workgroups share one): the caller then runs the two kernels."""
-    B, T, C = r.shape
+    B, T, C = btc = r.shape
     bf = torch.bfloat16
-    btc = (B, T, C)
-    named = dict(r=(r, btc, bf), k=(k, btc, bf), v=(v, btc, bf), w=(w, btc, bf), u=(u, (H, HEAD_SIZE), bf),
-                 gate=(gate, btc, bf), gamma=(gamma, (C,), bf), beta=(beta, (C,), bf))
+    named = _named(btc, bf, r, k, v, w, u, ushape=(H, HEAD_SIZE), gate=gate)
+    named["gamma"], named["beta"] = (gamma, (C,), bf), (beta, (C,), bf)
     dev = _check_tensors(B, T, C, H, named, dtype=bf)
     out = torch.empty(btc, device=dev, dtype=bf)
     y = torch.empty(btc, device=dev, dtype=bf) if want_y else None
     stats = torch.empty((B * T, H, 2), device=dev, dtype=torch.float32) if want_stats else None
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_forward_gn_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), None, None, _ptr(y),
-                                            _ptr(ckpt), 0 if ckpt is None else ckpt.numel(), _ptr(gate), _ptr(gamma), _ptr(beta),
-                                            float(eps), _ptr(out), _ptr(stats), _lib.W_RAW, _stream_ptr())
+    rc = _call("wkv6_forward_gn_ex", "wkv6 forward_gn_ex", dev, B, T, C, H, *_ptrs(r, k, v, w, u, None, None, y, ckpt),
+               0 if ckpt is None else ckpt.numel(), *_ptrs(gate, gamma, beta), float(eps), _ptr(out), _ptr(stats), _lib.W_RAW, check=False)
     if rc == _lib.EUNSUPPORTED:
         return None
     _lib.check(rc, "wkv6 forward_gn_ex")
@@ -427,45 +345,27 @@ def forward_gn_ex(r, k, v, w, u, H, gate, gamma, beta, eps, ckpt=None, want_y=Tr
 def backward_ex(r, k, v, w, u, gy, H, s0=None, w_is_ew=False, want_gs=False, algo=None, ckpt=None):
     """Returns (gr, gk, gv, gw, gu[B,C], gs[B,H,N,N] or None): gradients in the I/O type of `r`, the per-batch partials gu / gs
     in fp32 (WKV6_PARTIALS_F32)."""
-    B, T, C = r.shape
+    B, T, C = btc = r.shape
     io = r.dtype
-    btc = (B, T, C)
-    wdt = torch.float32 if w_is_ew else io
-    named = dict(r=(r, btc, io), k=(k, btc, io), v=(v, btc, io), w=(w, btc, wdt), u=(u, (H, HEAD_SIZE), io),
-                 gy=(gy, btc, io))
-    flags = (_lib.W_EW_F32 if w_is_ew else _lib.W_RAW) | (_lib.IO_F32 if io == torch.float32 else 0)
-    flags |= _lib.ALGO_SCAN if algo == "scan" else 0
+    named = _named(btc, io, r, k, v, w, u, wdt=torch.float32 if w_is_ew else io, ushape=(H, HEAD_SIZE), gy=gy)
+    # gu / gs are per-batch partial sums the caller reduces: always fp32, so that the parameter gradient is rounded once
+    flags = _flags(io, w_is_ew, algo) | _lib.PARTIALS_F32
     if s0 is not None:
-        per_batch = s0.dim() == 4
-        named["s0"] = (s0, (B, H, HEAD_SIZE, HEAD_SIZE) if per_batch else (H, HEAD_SIZE, HEAD_SIZE), io)
-        flags |= _lib.S0_PER_BATCH if per_batch else 0
+        named["s0"], per_batch = _s0_entry(s0, B, H, io)
+        flags |= per_batch
     dev = _check_tensors(B, T, C, H, named, dtype=io)
     gr, gk, gv, gw = (torch.empty(btc, device=dev, dtype=io) for _ in range(4))
-    # gu / gs are per-batch partial sums the caller reduces: always fp32, so that the parameter gradient is rounded once
-    flags |= _lib.PARTIALS_F32
     gu = torch.empty((B, C), device=dev, dtype=torch.float32)
     gs = torch.empty((B, H, HEAD_SIZE, HEAD_SIZE), device=dev, dtype=torch.float32) if want_gs else None
-    if ckpt is not None:           # checkpoints written by forward_ex(..., ckpt=ckpt) on the same inputs
-        ws = ckpt
-        flags |= _lib.CKPT_VALID
-    else:
-        ws = torch.empty(_lib.load().wkv6_backward_workspace_bytes(B, T, C, H), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_backward_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(s0),
-                                          _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu), _ptr(gs),
-                                          _ptr(ws), ws.numel(), flags, _stream_ptr())
-    _lib.check(rc, "wkv6 backward_ex")
+    # ckpt: the checkpoints written by forward_ex(..., ckpt=ckpt) on the same inputs.  Here, unlike in every other backward, a ckpt alone
+    # marks them valid, whatever the I/O type and the algorithm
+    ws, valid = _workspace_or_ckpt(ckpt, True, io, algo, new_checkpoint, B, T, C, H, dev, chunked_only=False)
+    _call("wkv6_backward_ex", "wkv6 backward_ex", dev, B, T, C, H, *_ptrs(r, k, v, w, u, s0, gy, gr, gk, gv, gw, gu, gs, ws), ws.numel(),
+          flags | valid)
     return gr, gk, gv, gw, gu, gs
 
 
 # ---- packed variable-length batches (include/wkv6_amd.h: wkv6_*_varlen_ex) ----
-def _check_cu_seqlens(cu_seqlens, dev):
-    if not (isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_contiguous()
-            and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2 and cu_seqlens.device == dev):
-        raise RuntimeError("cu_seqlens must be a contiguous int32 [n_seq + 1] tensor on the device of r")
-    return cu_seqlens.numel() - 1
-
-
 def new_varlen_workspace(total_T, n_seq, C, H, device):
     """Workspace of the packed pair: the per-sequence int arrays and the state checkpoints that `forward_varlen_ex(..., ws=)` fills and
     `backward_varlen_ex(..., ws=, ckpt_valid=True)` consumes.  Sized from the host-side bound, no device data needed."""
@@ -492,45 +392,51 @@ def new_rwkv6_varlen_split_workspace(total_T, n_seq, seg_len, C, H, device):
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
-def _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo, extra):
+def _packed_dims(r, cu_seqlens, io_too=False):
+    """(total_T, C, n_seq) of a packed call, judged in this order: r is 2-d, [its I/O type,] cu_seqlens."""
     if r.dim() != 2:
         raise RuntimeError("packed tensors are [total_T, C]")
-    total, C = r.shape
-    io = r.dtype
-    if io not in (torch.bfloat16, torch.float32):
-        raise RuntimeError(f"unsupported I/O dtype {io}")
-    tc = (total, C)
-    wdt = torch.float32 if w_is_ew else io
-    named = dict(r=(r, tc, io), k=(k, tc, io), v=(v, tc, io), w=(w, tc, wdt), u=(u, (H, HEAD_SIZE), io))
-    for name, t in extra.items():
-        named[name] = (t, tc, io)
-    flags = (_lib.W_EW_F32 if w_is_ew else _lib.W_RAW) | (_lib.IO_F32 if io == torch.float32 else 0)
-    flags |= _lib.ALGO_SCAN if algo == "scan" else 0
-    n_seq = _check_cu_seqlens(cu_seqlens, r.device)
-    if s0 is not None:
-        per_seq = s0.dim() == 4
-        named["s0"] = (s0, (n_seq, H, HEAD_SIZE, HEAD_SIZE) if per_seq else (H, HEAD_SIZE, HEAD_SIZE), io)
-        flags |= _lib.S0_PER_BATCH if per_seq else 0
+    if io_too:
+        _io_of(r)
+    return r.shape[0], r.shape[1], _ints(cu_seqlens, _AT_LEAST_2, r.device, _CU_SEQLENS).numel() - 1
+
+
+def _check_max_seqlen(max_seqlen):
     if int(max_seqlen) < 1:
         raise RuntimeError("max_seqlen must be >= 1")
+
+
+def _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo, **same):
+    """(total_T, C, io, n_seq, named, flags) of the packed wrappers; same: further [total_T, C] tensors of the I/O type."""
+    total, C, n_seq = _packed_dims(r, cu_seqlens, io_too=True)
+    io = r.dtype
+    named = _named((total, C), io, r, k, v, w, u, wdt=torch.float32 if w_is_ew else io, ushape=(H, HEAD_SIZE), **same)
+    flags = _flags(io, w_is_ew, algo)
+    if s0 is not None:
+        named["s0"], per_seq = _s0_entry(s0, n_seq, H, io)
+        flags |= per_seq
+    _check_max_seqlen(max_seqlen)
     return total, C, io, n_seq, named, flags
+
+
+def _varlen_backward_workspace(ws, ckpt_valid, io, algo, total, n_seq, C, H, dev):
+    if ckpt_valid and ws is None:
+        raise RuntimeError("ckpt_valid needs the workspace the forward filled")
+    return _workspace_or_ckpt(ws, ckpt_valid, io, algo, new_varlen_workspace, total, n_seq, C, H, dev)
 
 
 def forward_varlen_ex(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0=None, s_out=None, w_is_ew=False, y=None, algo=None, ws=None):
     """y [total_T,C] = WKV6 of every sequence of a packed batch on its own (sequence s = rows cu_seqlens[s] .. cu_seqlens[s+1]-1, each
     from s0).  ws: a new_varlen_workspace() buffer that keeps the state checkpoints for backward_varlen_ex(..., ws=ws, ckpt_valid=True)."""
-    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo, {})
+    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo)
     if s_out is not None:
         named["s_out"] = (s_out, (n_seq, H, HEAD_SIZE, HEAD_SIZE), io)
     if y is None:
         y = torch.empty((total, C), device=r.device, dtype=io)
     named["y"] = (y, (total, C), io)
     dev = _check_tensors(n_seq, total, C, H, named, dtype=io)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_forward_varlen_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(r), _ptr(k), _ptr(v),
-                                                _ptr(w), _ptr(u), _ptr(s0), _ptr(s_out), _ptr(y), _ptr(ws),
-                                                0 if ws is None else ws.numel(), flags, _stream_ptr())
-    _lib.check(rc, "wkv6 forward_varlen_ex")
+    _call("wkv6_forward_varlen_ex", "wkv6 forward_varlen_ex", dev, total, n_seq, int(max_seqlen), C, H,
+          *_ptrs(cu_seqlens, r, k, v, w, u, s0, s_out, y, ws), 0 if ws is None else ws.numel(), flags)
     return y
 
 
@@ -538,70 +444,50 @@ def backward_varlen_ex(r, k, v, w, u, gy, H, cu_seqlens, max_seqlen, s0=None, w_
                        ckpt_valid=False):
     """Returns (gr, gk, gv, gw [total_T,C], gu [n_seq,C], gs [n_seq,H,N,N] or None); gu / gs are fp32 per-sequence partials
     (WKV6_PARTIALS_F32) for the caller to sum.  ckpt_valid: `ws` was filled by forward_varlen_ex(..., ws=ws) on the same inputs."""
-    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo, {"gy": gy})
+    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, s0, w_is_ew, algo, gy=gy)
     dev = _check_tensors(n_seq, total, C, H, named, dtype=io)
     gr, gk, gv, gw = (torch.empty((total, C), device=dev, dtype=io) for _ in range(4))
-    flags |= _lib.PARTIALS_F32
     gu = torch.empty((n_seq, C), device=dev, dtype=torch.float32)
     gs = torch.empty((n_seq, H, HEAD_SIZE, HEAD_SIZE), device=dev, dtype=torch.float32) if want_gs else None
-    if ckpt_valid:
-        if ws is None:
-            raise RuntimeError("ckpt_valid needs the workspace the forward filled")
-        if io == torch.bfloat16 and algo != "scan":
-            flags |= _lib.CKPT_VALID
-    if ws is None:
-        ws = new_varlen_workspace(total, n_seq, C, H, dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_backward_varlen_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(r), _ptr(k), _ptr(v),
-                                                 _ptr(w), _ptr(u), _ptr(s0), _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw),
-                                                 _ptr(gu), _ptr(gs), _ptr(ws), ws.numel(), flags, _stream_ptr())
-    _lib.check(rc, "wkv6 backward_varlen_ex")
+    ws, valid = _varlen_backward_workspace(ws, ckpt_valid, io, algo, total, n_seq, C, H, dev)
+    _call("wkv6_backward_varlen_ex", "wkv6 backward_varlen_ex", dev, total, n_seq, int(max_seqlen), C, H,
+          *_ptrs(cu_seqlens, r, k, v, w, u, s0, gy, gr, gk, gv, gw, gu, gs, ws), ws.numel(), flags | _lib.PARTIALS_F32 | valid)
     return gr, gk, gv, gw, gu, gs
 
 
 def wkv5_forward_ex(r, k, v, w, u, H, y=None):
     """y = WKV5(r,k,v,w,u): w, u [H,N] raw parameters in the I/O type of `r` (bf16, or fp32 for numerics tests)."""
-    B, T, C = r.shape
-    io = r.dtype
-    if io not in (torch.bfloat16, torch.float32):
-        raise RuntimeError(f"unsupported I/O dtype {io}")
-    btc, hn = (B, T, C), (H, HEAD_SIZE)
+    B, T, C = btc = r.shape
+    io = _io_of(r)
+    hn = (H, HEAD_SIZE)
     if y is None:
         y = torch.empty(btc, device=r.device, dtype=io)
-    dev = _check_tensors(B, T, C, H, dict(r=(r, btc, io), k=(k, btc, io), v=(v, btc, io), w=(w, hn, io), u=(u, hn, io),
-                                          y=(y, btc, io)), dtype=io)
-    flags = _lib.W_RAW | (_lib.IO_F32 if io == torch.float32 else 0)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv5_forward_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), flags, _stream_ptr())
-    _lib.check(rc, "wkv5 forward_ex")
+    dev = _check_tensors(B, T, C, H, _named(btc, io, r, k, v, w, u, wshape=hn, ushape=hn, y=y), dtype=io)
+    _call("wkv5_forward_ex", "wkv5 forward_ex", dev, B, T, C, H, *_ptrs(r, k, v, w, u, y), _flags(io))
     return y
 
 
 def wkv5_backward_ex(r, k, v, w, u, gy, H):
     """Returns (gr, gk, gv, gw[B,C], gu[B,C]): gradients in the I/O type of `r`, the per-batch partials gw (with respect to the raw
     w) and gu in fp32 (WKV6_PARTIALS_F32), for the caller to sum over the batch and round once."""
-    B, T, C = r.shape
+    B, T, C = btc = r.shape
     io = r.dtype
-    btc, hn = (B, T, C), (H, HEAD_SIZE)
-    dev = _check_tensors(B, T, C, H, dict(r=(r, btc, io), k=(k, btc, io), v=(v, btc, io), w=(w, hn, io), u=(u, hn, io),
-                                          gy=(gy, btc, io)), dtype=io)
+    hn = (H, HEAD_SIZE)
+    dev = _check_tensors(B, T, C, H, _named(btc, io, r, k, v, w, u, wshape=hn, ushape=hn, gy=gy), dtype=io)
     gr, gk, gv = (torch.empty(btc, device=dev, dtype=io) for _ in range(3))
     gw, gu = (torch.empty((B, C), device=dev, dtype=torch.float32) for _ in range(2))
-    flags = _lib.W_RAW | _lib.PARTIALS_F32 | (_lib.IO_F32 if io == torch.float32 else 0)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv5_backward_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), None, _ptr(u), _ptr(gy), _ptr(gr),
-                                          _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu), flags, _stream_ptr())
-    _lib.check(rc, "wkv5 backward_ex")
+    _call("wkv5_backward_ex", "wkv5 backward_ex", dev, B, T, C, H, *_ptrs(r, k, v, w, None, u, gy, gr, gk, gv, gw, gu),
+          _flags(io) | _lib.PARTIALS_F32)
     return gr, gk, gv, gw, gu
 
 
 REV_R, REV_K, REV_V, REV_W, REV_Y, REV_ALL = _lib.REV_R, _lib.REV_K, _lib.REV_V, _lib.REV_W, _lib.REV_Y, _lib.REV_ALL
 
 
-def _check_rev(B, rev_n, rev_mask, dev):
-    if not (isinstance(rev_n, torch.Tensor) and rev_n.dtype == torch.int32 and rev_n.is_contiguous() and
-            tuple(rev_n.shape) == (B,) and rev_n.device == dev):
-        raise RuntimeError("rev_n must be a contiguous int32 [B] tensor on the device of r")
+def _check_rev(n, what, rev_n, rev_mask, dev, or_none=False):
+    """rev_n: int32 [n] (`what` names n in the message) on dev; or_none: the packed wrappers take None for "no map"."""
+    if rev_n is not None or not or_none:
+        _ints(rev_n, (n,), dev, f"rev_n must be a contiguous int32 [{what}] tensor on the device of r")
     if rev_mask & ~REV_ALL:
         raise RuntimeError(f"rev_mask {rev_mask} has unknown bits")
 
@@ -611,46 +497,41 @@ def forward_rev_ex(r, k, v, w, u, H, rev_n, rev_mask, y=None, ckpt=None, algo=No
     tokens [0, rev_n[b]) of the tensors named in `rev_mask` (REV_R | REV_K | REV_V | REV_W | REV_Y) are taken in reverse
     order, the rest in place.  I/O type of `r`: bf16 (chunked MFMA kernels; algo="scan" forces the exact ones) or fp32 (exact
     scan kernels)."""
-    B, T, C = r.shape
-    btc, io = (B, T, C), r.dtype
-    if io not in (torch.bfloat16, torch.float32):
-        raise RuntimeError(f"unsupported I/O dtype {io}")
+    B, T, C = btc = r.shape
+    io = _io_of(r)
     if y is None:
         y = torch.empty(btc, device=r.device, dtype=io)
-    named = dict(r=(r, btc, io), k=(k, btc, io), v=(v, btc, io), w=(w, btc, io), u=(u, (H, HEAD_SIZE), io), y=(y, btc, io))
-    dev = _check_tensors(B, T, C, H, named, dtype=io)
-    _check_rev(B, rev_n, rev_mask, dev)
-    flags = _lib.W_RAW | (_lib.IO_F32 if io == torch.float32 else 0) | (_lib.ALGO_SCAN if algo == "scan" else 0)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_forward_rev_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(y), _ptr(ckpt),
-                                             0 if ckpt is None else ckpt.numel(), _ptr(rev_n), rev_mask, flags,
-                                             _stream_ptr())
-    _lib.check(rc, "wkv6 forward_rev_ex")
+    dev = _check_tensors(B, T, C, H, _named(btc, io, r, k, v, w, u, ushape=(H, HEAD_SIZE), y=y), dtype=io)
+    _check_rev(B, "B", rev_n, rev_mask, dev)
+    _call("wkv6_forward_rev_ex", "wkv6 forward_rev_ex", dev, B, T, C, H, *_ptrs(r, k, v, w, u, y, ckpt), 0 if ckpt is None else ckpt.numel(),
+          _ptr(rev_n), rev_mask, _flags(io, algo=algo))
     return y
 
 
-def _pair_sets(B, T, C, H, sets, u, bwd):
-    """Check and pack the two problems of a pair launch.  sets: two dicts with r, k, v, w (+ y | gy), ckpt, rev_n, rev_mask."""
+def _pair_sets(n, shape, C, H, sets, u, bwd, packed):
+    """Check and pack the two problems of a pair launch.  sets: two dicts with r, k, v, w (+ y | gy) [shape], ckpt, rev_n [n], rev_mask.
+    Dense (n = B): ckpt is a new_checkpoint() buffer, and a problem without rev_n is not judged by its rev_mask.  packed (n = n_seq): ckpt is
+    one new_varlen_workspace() buffer per problem, and the rev_mask is judged with or without rev_n."""
     bf = torch.bfloat16
-    btc = (B, T, C)
     arr = (_lib.SeqSet * 2)()
     keep = []                                   # tensors the packed pointers refer to
     dev = None
     for i, q in enumerate(sets):
-        named = {n: (q[n], btc, bf) for n in ("r", "k", "v", "w") + (("gy",) if bwd else ("y",))}
+        named = {name: (q[name], shape, bf) for name in ("r", "k", "v", "w") + (("gy",) if bwd else ("y",))}
         named["u"] = (u, (H, HEAD_SIZE), bf)
-        dev = _check_tensors(B, T, C, H, named, dtype=bf)
+        dev = _check_tensors(n, shape[-2], C, H, named, dtype=bf)
         rev_n, rev_mask = q.get("rev_n"), q.get("rev_mask", 0)
-        if rev_n is not None:
-            _check_rev(B, rev_n, rev_mask, dev)
+        if packed or rev_n is not None:
+            _check_rev(n, "n_seq" if packed else "B", rev_n, rev_mask, dev, or_none=packed)
         ckpt = q.get("ckpt")
         if bwd and ckpt is None:
-            raise RuntimeError("wkv6 pair backward: both problems need the checkpoints their forward wrote")
+            raise RuntimeError("wkv6 packed pair backward: both problems need the workspaces their forward wrote" if packed else
+                               "wkv6 pair backward: both problems need the checkpoints their forward wrote")
         e = arr[i]
-        e.r, e.k, e.v, e.w = _ptr(q["r"]), _ptr(q["k"]), _ptr(q["v"]), _ptr(q["w"])
+        e.r, e.k, e.v, e.w = _ptrs(q["r"], q["k"], q["v"], q["w"])
         if bwd:
-            outs = [torch.empty(btc, device=dev, dtype=bf) for _ in range(4)] + [torch.empty((B, C), device=dev, dtype=torch.float32)]
-            e.gy, e.gr, e.gk, e.gv, e.gw, e.gu = (_ptr(t) for t in [q["gy"]] + outs)
+            outs = [torch.empty(shape, device=dev, dtype=bf) for _ in range(4)] + [torch.empty((n, C), device=dev, dtype=torch.float32)]
+            e.gy, e.gr, e.gk, e.gv, e.gw, e.gu = _ptrs(q["gy"], *outs)
             keep.append(outs)
         else:
             e.y = _ptr(q["y"])
@@ -659,80 +540,58 @@ def _pair_sets(B, T, C, H, sets, u, bwd):
     return arr, keep, dev
 
 
+def _pair_outputs(sets, shape):
+    for q in sets:
+        if q.get("y") is None:
+            q["y"] = torch.empty(shape, device=q["r"].device, dtype=torch.bfloat16)
+
+
 def forward_pair_ex(H, u, sets):
     """Both operator calls of a bidirectional time-mix layer in one launch (include/wkv6_amd.h, wkv6_forward_pair_ex; SURVEY.md
     row n2): `sets` = two dicts {r, k, v, w, [y], [ckpt], [rev_n, rev_mask]} of one shape.  Returns (y0, y1)."""
-    B, T, C = sets[0]["r"].shape
-    for q in sets:
-        if q.get("y") is None:
-            q["y"] = torch.empty((B, T, C), device=q["r"].device, dtype=torch.bfloat16)
-    arr, _, dev = _pair_sets(B, T, C, H, sets, u, bwd=False)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_forward_pair_ex(B, T, C, H, _ptr(u), arr, _lib.W_RAW, _stream_ptr())
-    _lib.check(rc, "wkv6 forward_pair_ex")
+    B, T, C = btc = tuple(sets[0]["r"].shape)
+    _pair_outputs(sets, btc)
+    arr, _, dev = _pair_sets(B, btc, C, H, sets, u, bwd=False, packed=False)
+    _call("wkv6_forward_pair_ex", "wkv6 forward_pair_ex", dev, B, T, C, H, _ptr(u), arr, _lib.W_RAW)
     return sets[0]["y"], sets[1]["y"]
 
 
 def backward_pair_ex(H, u, sets):
     """Gradients of forward_pair_ex: two tuples (gr, gk, gv, gw, gu[B,C] fp32), one per problem; `sets` as in the forward plus gy."""
-    B, T, C = sets[0]["r"].shape
-    arr, keep, dev = _pair_sets(B, T, C, H, sets, u, bwd=True)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_backward_pair_ex(B, T, C, H, _ptr(u), arr, _lib.W_RAW | _lib.PARTIALS_F32, _stream_ptr())
-    _lib.check(rc, "wkv6 backward_pair_ex")
+    B, T, C = btc = tuple(sets[0]["r"].shape)
+    arr, keep, dev = _pair_sets(B, btc, C, H, sets, u, bwd=True, packed=False)
+    _call("wkv6_backward_pair_ex", "wkv6 backward_pair_ex", dev, B, T, C, H, _ptr(u), arr, _lib.W_RAW | _lib.PARTIALS_F32)
     return tuple(keep[0]), tuple(keep[1])
 
 
 def backward_rev_ex(r, k, v, w, u, gy, H, rev_n, rev_mask, ckpt=None, algo=None):
     """Gradients of forward_rev_ex: (gr, gk, gv, gw, gu[B,C]); each gradient is laid out like its tensor."""
-    B, T, C = r.shape
-    btc, io = (B, T, C), r.dtype
-    if io not in (torch.bfloat16, torch.float32):
-        raise RuntimeError(f"unsupported I/O dtype {io}")
-    named = dict(r=(r, btc, io), k=(k, btc, io), v=(v, btc, io), w=(w, btc, io), u=(u, (H, HEAD_SIZE), io), gy=(gy, btc, io))
-    dev = _check_tensors(B, T, C, H, named, dtype=io)
-    _check_rev(B, rev_n, rev_mask, dev)
+    B, T, C = btc = r.shape
+    io = _io_of(r)
+    dev = _check_tensors(B, T, C, H, _named(btc, io, r, k, v, w, u, ushape=(H, HEAD_SIZE), gy=gy), dtype=io)
+    _check_rev(B, "B", rev_n, rev_mask, dev)
     gr, gk, gv, gw = (torch.empty(btc, device=dev, dtype=io) for _ in range(4))
     gu = torch.empty((B, C), device=dev, dtype=torch.float32)
-    exact = io == torch.float32 or algo == "scan"
-    flags = _lib.W_RAW | _lib.PARTIALS_F32 | (_lib.IO_F32 if io == torch.float32 else 0) | (_lib.ALGO_SCAN if algo == "scan" else 0)
-    if ckpt is not None and not exact:
-        ws = ckpt
-        flags |= _lib.CKPT_VALID
-    else:
-        ws = torch.empty(_lib.load().wkv6_backward_workspace_bytes(B, T, C, H), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_backward_rev_ex(B, T, C, H, _ptr(r), _ptr(k), _ptr(v), _ptr(w), _ptr(u), _ptr(gy), _ptr(gr),
-                                              _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu), _ptr(ws), ws.numel(), _ptr(rev_n),
-                                              rev_mask, flags, _stream_ptr())
-    _lib.check(rc, "wkv6 backward_rev_ex")
+    exact = io == torch.float32 or algo == "scan"           # the exact kernels read no checkpoints: a ckpt is left alone, not used as workspace
+    ws, valid = _workspace_or_ckpt(None if exact else ckpt, True, io, algo, new_checkpoint, B, T, C, H, dev)
+    _call("wkv6_backward_rev_ex", "wkv6 backward_rev_ex", dev, B, T, C, H, *_ptrs(r, k, v, w, u, gy, gr, gk, gv, gw, gu, ws), ws.numel(),
+          _ptr(rev_n), rev_mask, _flags(io, algo=algo) | _lib.PARTIALS_F32 | valid)
     return gr, gk, gv, gw, gu
 
 
 # ---- reversal maps and the pair launch on packed batches (include/wkv6_amd.h: wkv6_*_varlen_rev_ex, wkv6_*_varlen_pair_ex) ----
-def _check_rev_varlen(n_seq, rev_n, rev_mask, dev):
-    if rev_n is not None and not (isinstance(rev_n, torch.Tensor) and rev_n.dtype == torch.int32 and rev_n.is_contiguous() and
-                                  tuple(rev_n.shape) == (n_seq,) and rev_n.device == dev):
-        raise RuntimeError("rev_n must be a contiguous int32 [n_seq] tensor on the device of r")
-    if rev_mask & ~REV_ALL:
-        raise RuntimeError(f"rev_mask {rev_mask} has unknown bits")
-
-
 def forward_varlen_rev_ex(r, k, v, w, u, H, cu_seqlens, max_seqlen, rev_n, rev_mask, y=None, algo=None, ws=None, w_is_ew=False):
     """forward_varlen_ex with the per-tensor reversal map of forward_rev_ex applied within every sequence: rev_n int32 [n_seq] (clamped to
     the sequence's length on the device; None: no map).  No initial state.  ws: a new_varlen_workspace() buffer that keeps the checkpoints
     for backward_varlen_rev_ex(..., ws=ws, ckpt_valid=True)."""
-    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, None, w_is_ew, algo, {})
+    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, None, w_is_ew, algo)
     if y is None:
         y = torch.empty((total, C), device=r.device, dtype=io)
     named["y"] = (y, (total, C), io)
     dev = _check_tensors(n_seq, total, C, H, named, dtype=io)
-    _check_rev_varlen(n_seq, rev_n, rev_mask, dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_forward_varlen_rev_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(r), _ptr(k), _ptr(v),
-                                                    _ptr(w), _ptr(u), _ptr(y), _ptr(ws), 0 if ws is None else ws.numel(),
-                                                    _ptr(rev_n), rev_mask, flags, _stream_ptr())
-    _lib.check(rc, "wkv6 forward_varlen_rev_ex")
+    _check_rev(n_seq, "n_seq", rev_n, rev_mask, dev, or_none=True)
+    _call("wkv6_forward_varlen_rev_ex", "wkv6 forward_varlen_rev_ex", dev, total, n_seq, int(max_seqlen), C, H,
+          *_ptrs(cu_seqlens, r, k, v, w, u, y, ws), 0 if ws is None else ws.numel(), _ptr(rev_n), rev_mask, flags)
     return y
 
 
@@ -740,90 +599,37 @@ def backward_varlen_rev_ex(r, k, v, w, u, gy, H, cu_seqlens, max_seqlen, rev_n, 
                            w_is_ew=False):
     """Gradients of forward_varlen_rev_ex: (gr, gk, gv, gw [total_T,C], gu [n_seq,C] fp32 per-sequence partials); each gradient is laid
     out like its tensor.  ckpt_valid: `ws` was filled by forward_varlen_rev_ex(..., ws=ws) on the same inputs."""
-    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, None, w_is_ew, algo, {"gy": gy})
+    total, C, io, n_seq, named, flags = _varlen_common(r, k, v, w, u, H, cu_seqlens, max_seqlen, None, w_is_ew, algo, gy=gy)
     dev = _check_tensors(n_seq, total, C, H, named, dtype=io)
-    _check_rev_varlen(n_seq, rev_n, rev_mask, dev)
+    _check_rev(n_seq, "n_seq", rev_n, rev_mask, dev, or_none=True)
     gr, gk, gv, gw = (torch.empty((total, C), device=dev, dtype=io) for _ in range(4))
-    flags |= _lib.PARTIALS_F32
     gu = torch.empty((n_seq, C), device=dev, dtype=torch.float32)
-    if ckpt_valid:
-        if ws is None:
-            raise RuntimeError("ckpt_valid needs the workspace the forward filled")
-        if io == torch.bfloat16 and algo != "scan":
-            flags |= _lib.CKPT_VALID
-    if ws is None:
-        ws = new_varlen_workspace(total, n_seq, C, H, dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_backward_varlen_rev_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(r), _ptr(k), _ptr(v),
-                                                     _ptr(w), _ptr(u), _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu),
-                                                     _ptr(ws), ws.numel(), _ptr(rev_n), rev_mask, flags, _stream_ptr())
-    _lib.check(rc, "wkv6 backward_varlen_rev_ex")
+    ws, valid = _varlen_backward_workspace(ws, ckpt_valid, io, algo, total, n_seq, C, H, dev)
+    _call("wkv6_backward_varlen_rev_ex", "wkv6 backward_varlen_rev_ex", dev, total, n_seq, int(max_seqlen), C, H,
+          *_ptrs(cu_seqlens, r, k, v, w, u, gy, gr, gk, gv, gw, gu, ws), ws.numel(), _ptr(rev_n), rev_mask, flags | _lib.PARTIALS_F32 | valid)
     return gr, gk, gv, gw, gu
-
-
-def _varlen_pair_sets(total, C, H, n_seq, sets, u, bwd):
-    """_pair_sets for packed problems: tensors [total_T, C], rev_n [n_seq], ckpt = a new_varlen_workspace() buffer per problem."""
-    bf = torch.bfloat16
-    tc = (total, C)
-    arr = (_lib.SeqSet * 2)()
-    keep = []
-    dev = None
-    for i, q in enumerate(sets):
-        named = {n: (q[n], tc, bf) for n in ("r", "k", "v", "w") + (("gy",) if bwd else ("y",))}
-        named["u"] = (u, (H, HEAD_SIZE), bf)
-        dev = _check_tensors(n_seq, total, C, H, named, dtype=bf)
-        rev_n, rev_mask = q.get("rev_n"), q.get("rev_mask", 0)
-        _check_rev_varlen(n_seq, rev_n, rev_mask, dev)
-        ckpt = q.get("ckpt")
-        if bwd and ckpt is None:
-            raise RuntimeError("wkv6 packed pair backward: both problems need the workspaces their forward wrote")
-        e = arr[i]
-        e.r, e.k, e.v, e.w = _ptr(q["r"]), _ptr(q["k"]), _ptr(q["v"]), _ptr(q["w"])
-        if bwd:
-            outs = [torch.empty(tc, device=dev, dtype=bf) for _ in range(4)] + [torch.empty((n_seq, C), device=dev, dtype=torch.float32)]
-            e.gy, e.gr, e.gk, e.gv, e.gw, e.gu = (_ptr(t) for t in [q["gy"]] + outs)
-            keep.append(outs)
-        else:
-            e.y = _ptr(q["y"])
-        e.ckpt, e.ckpt_bytes = _ptr(ckpt), 0 if ckpt is None else ckpt.numel()
-        e.rev_n, e.rev_mask = _ptr(rev_n), rev_mask if rev_n is not None else 0
-    return arr, keep, dev
 
 
 def forward_varlen_pair_ex(H, u, sets, cu_seqlens, max_seqlen):
     """forward_pair_ex on a packed batch: `sets` = two dicts {r, k, v, w [total_T,C], [y], [ckpt], [rev_n [n_seq], rev_mask]} over the
     same sequences; ckpt is one new_varlen_workspace() buffer per problem.  Returns (y0, y1)."""
-    if sets[0]["r"].dim() != 2:
-        raise RuntimeError("packed tensors are [total_T, C]")
-    total, C = sets[0]["r"].shape
-    n_seq = _check_cu_seqlens(cu_seqlens, sets[0]["r"].device)
-    if int(max_seqlen) < 1:
-        raise RuntimeError("max_seqlen must be >= 1")
-    for q in sets:
-        if q.get("y") is None:
-            q["y"] = torch.empty((total, C), device=q["r"].device, dtype=torch.bfloat16)
-    arr, _, dev = _varlen_pair_sets(total, C, H, n_seq, sets, u, bwd=False)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_forward_varlen_pair_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(u), arr, _lib.W_RAW,
-                                                     _stream_ptr())
-    _lib.check(rc, "wkv6 forward_varlen_pair_ex")
+    total, C, n_seq = _packed_dims(sets[0]["r"], cu_seqlens)
+    _check_max_seqlen(max_seqlen)
+    _pair_outputs(sets, (total, C))
+    arr, _, dev = _pair_sets(n_seq, (total, C), C, H, sets, u, bwd=False, packed=True)
+    _call("wkv6_forward_varlen_pair_ex", "wkv6 forward_varlen_pair_ex", dev, total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(u), arr,
+          _lib.W_RAW)
     return sets[0]["y"], sets[1]["y"]
 
 
 def backward_varlen_pair_ex(H, u, sets, cu_seqlens, max_seqlen):
     """Gradients of forward_varlen_pair_ex: two tuples (gr, gk, gv, gw, gu [n_seq,C] fp32), one per problem; `sets` as in the forward
     (with the workspaces it filled) plus gy."""
-    if sets[0]["r"].dim() != 2:
-        raise RuntimeError("packed tensors are [total_T, C]")
-    total, C = sets[0]["r"].shape
-    n_seq = _check_cu_seqlens(cu_seqlens, sets[0]["r"].device)
-    if int(max_seqlen) < 1:
-        raise RuntimeError("max_seqlen must be >= 1")
-    arr, keep, dev = _varlen_pair_sets(total, C, H, n_seq, sets, u, bwd=True)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6_backward_varlen_pair_ex(total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(u), arr,
-                                                      _lib.W_RAW | _lib.PARTIALS_F32, _stream_ptr())
-    _lib.check(rc, "wkv6 backward_varlen_pair_ex")
+    total, C, n_seq = _packed_dims(sets[0]["r"], cu_seqlens)
+    _check_max_seqlen(max_seqlen)
+    arr, keep, dev = _pair_sets(n_seq, (total, C), C, H, sets, u, bwd=True, packed=True)
+    _call("wkv6_backward_varlen_pair_ex", "wkv6 backward_varlen_pair_ex", dev, total, n_seq, int(max_seqlen), C, H, _ptr(cu_seqlens), _ptr(u),
+          arr, _lib.W_RAW | _lib.PARTIALS_F32)
     return tuple(keep[0]), tuple(keep[1])
 
 
@@ -851,50 +657,33 @@ def _mask_or_lens(mask, lens, B, T):
 def bi_forward_ex(mask, r, k, v, w, u, H, w_is_ew=False, algo=None, ws=None, lens=None):
     """ws: a bi_new_workspace() buffer the caller keeps for bi_backward_ex(..., ws=ws): the forward then stores the state
     checkpoints of both scans in it and the backward skips its two state passes.  lens: row lengths instead of the mask."""
-    B, T, C = r.shape
+    B, T, C = btc = r.shape
     io = r.dtype
-    btc = (B, T, C)
-    wdt = torch.float32 if w_is_ew else io
-    named = dict(**_mask_or_lens(mask, lens, B, T), r=(r, btc, io), k=(k, btc, io), v=(v, btc, io),
-                 w=(w, btc, wdt), u=(u, (H, HEAD_SIZE), io))
-    flags = (_lib.W_EW_F32 if w_is_ew else _lib.W_RAW) | (_lib.IO_F32 if io == torch.float32 else 0)
-    flags |= _lib.ALGO_SCAN if algo == "scan" else 0
+    named = {**_mask_or_lens(mask, lens, B, T),
+             **_named(btc, io, r, k, v, w, u, wdt=torch.float32 if w_is_ew else io, ushape=(H, HEAD_SIZE))}
     dev = _check_tensors(B, T, C, H, named, dtype=io)
     y = torch.empty(btc, device=dev, dtype=io)
+    flags = _flags(io, w_is_ew, algo)
     if ws is not None:
         flags |= _lib.BI_KEEP_CKPT
     else:
         ws = bi_new_workspace(B, T, C, H, dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6bi_forward_ex(B, T, C, H, _ptr(mask), _ptr(lens), _ptr(r), _ptr(k), _ptr(v), _ptr(w),
-                                           _ptr(u), _ptr(y), _ptr(ws), ws.numel(), flags, _stream_ptr())
-    _lib.check(rc, "wkv6_bi forward_ex")
+    _call("wkv6bi_forward_ex", "wkv6_bi forward_ex", dev, B, T, C, H, *_ptrs(mask, lens, r, k, v, w, u, y, ws), ws.numel(), flags)
     return y
 
 
 def bi_backward_ex(mask, r, k, v, w, u, gy, H, w_is_ew=False, algo=None, ws=None, lens=None):
     """ws: the workspace a preceding bi_forward_ex(..., ws=ws) on the same inputs filled (checkpoints valid)."""
-    B, T, C = r.shape
+    B, T, C = btc = r.shape
     io = r.dtype
-    btc = (B, T, C)
-    wdt = torch.float32 if w_is_ew else io
-    named = dict(**_mask_or_lens(mask, lens, B, T), r=(r, btc, io), k=(k, btc, io), v=(v, btc, io),
-                 w=(w, btc, wdt), u=(u, (H, HEAD_SIZE), io), gy=(gy, btc, io))
-    flags = (_lib.W_EW_F32 if w_is_ew else _lib.W_RAW) | (_lib.IO_F32 if io == torch.float32 else 0)
-    flags |= _lib.ALGO_SCAN if algo == "scan" else 0
+    named = {**_mask_or_lens(mask, lens, B, T),
+             **_named(btc, io, r, k, v, w, u, wdt=torch.float32 if w_is_ew else io, ushape=(H, HEAD_SIZE), gy=gy)}
     dev = _check_tensors(B, T, C, H, named, dtype=io)
     gr, gk, gv, gw = (torch.empty(btc, device=dev, dtype=io) for _ in range(4))
     gu = torch.empty((B, C), device=dev, dtype=torch.float32)      # per-batch partials: fp32 (WKV6_PARTIALS_F32)
-    flags |= _lib.PARTIALS_F32
-    if ws is not None and io == torch.bfloat16 and algo != "scan":
-        flags |= _lib.CKPT_VALID
-    elif ws is None:
-        ws = bi_new_workspace(B, T, C, H, dev)
-    with torch.cuda.device(dev):
-        rc = _lib.load().wkv6bi_backward_ex(B, T, C, H, _ptr(mask), _ptr(lens), _ptr(r), _ptr(k), _ptr(v), _ptr(w),
-                                            _ptr(u), _ptr(gy), _ptr(gr), _ptr(gk), _ptr(gv), _ptr(gw), _ptr(gu),
-                                            _ptr(ws), ws.numel(), flags, _stream_ptr())
-    _lib.check(rc, "wkv6_bi backward_ex")
+    ws, valid = _workspace_or_ckpt(ws, True, io, algo, bi_new_workspace, B, T, C, H, dev)
+    _call("wkv6bi_backward_ex", "wkv6_bi backward_ex", dev, B, T, C, H, *_ptrs(mask, lens, r, k, v, w, u, gy, gr, gk, gv, gw, gu, ws),
+          ws.numel(), _flags(io, w_is_ew, algo) | _lib.PARTIALS_F32 | valid)
     return gr, gk, gv, gw, gu
 
 
@@ -966,7 +755,6 @@ class ClockProbe:
             pass
 
     def counts(self):
-        import ctypes
         f, b = ctypes.c_long(0), ctypes.c_long(0)
         self.lib.wkv6_clock_ring_counts(ctypes.byref(f), ctypes.byref(b))
         return f.value, b.value
