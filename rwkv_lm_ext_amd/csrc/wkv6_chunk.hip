@@ -52,6 +52,24 @@ constexpr int CONSUMER_STAGGER = 3;         // s_sleep units (64 cycles) by whic
 constexpr int YRS = 144;                    // staged y row: 128 B + 16 B pad (16-byte row reads stay aligned; writes are 2-way at most)
 constexpr int YS_BYTES = GRP * YRS;
 
+// The modes of chunk_fwd_body<MODE> (and of fwd_request_group<MODE>, which reads three of them), one bit each.  A call site ORs the bits it
+// switches on and names nothing else; a bit that follows a kernel's own template parameter goes through bit().  (FWD_: the backward has
+// BWD_ bits of its own, wkv6_chunk_bwd12k.hip.)  The notes below and above the body call a bit by its name without the prefix, which is
+// also the constant the body reads it into.
+enum : unsigned {
+    FWD_W_RAW = 1u << 0,         // the decay input is the raw bf16 w (else: the fp32 ew)
+    FWD_STATE_ONLY = 1u << 1,    // no outputs, only the state recurrence (and its checkpoints)
+    FWD_ACC = 1u << 2,           // add into y instead of overwriting: the reverse half of wkv6_bi
+    FWD_GN = 1u << 3,            // per-head GroupNorm and gate multiply in the store epilogue
+    FWD_AFF = 1u << 4,           // no per-tensor reversal map: affine token addressing (wkv6_scan.h: TokAddr)
+    FWD_CLK = 1u << 5,           // the in-run clock probe: the plain kernel only
+    FWD_CHAIN = 1u << 6,         // a call of the persistent wkv6_bi launch (FwdRaw, FwdChain below)
+    FWD_VARLEN = 1u << 7,        // packed batch: row b is sequence b of a [total_T, C] tensor
+    FWD_SLOTS = 1u << 8,         // the fp32 state lives in a slot of a pool, updated in place (VARLEN only)
+    FWD_SNAP = 1u << 9,          // a separate output slot and state snapshots every a.snap_every tokens (SLOTS only)
+    FWD_SEG = 1u << 10,          // row b is an item: a sequence, or one segment of a long one (VARLEN only)
+};
+constexpr unsigned bit(bool on, unsigned b) { return on ? b : 0u; }
 // STATE_ONLY: no outputs, only the state recurrence (first half of the self-contained backward).
 // With a.ckpt the state is dumped every CKPT_TOK = 64 tokens (fp32, in the register order of the backward's row waves:
 // wkv6_scan.h) for the backward kernel.
@@ -72,10 +90,11 @@ struct FwdRaw {
 };
 // group `grp` of problem (a, slot), block wv, requested into raw -- the one definition of "which bytes": the body's own requests and the
 // previous call's early one must agree
-template <bool W_RAW, bool STATE_ONLY, bool AFF>
+template <unsigned MODE>
 __device__ __forceinline__ void fwd_request_group(const ScanArgs& a, const int b, const int h, const int ntok, const int rev, const int grp, const int wv,
                                                   const int lane, FwdRaw& raw)   // rev: the row reversed (a's own reversal fields are not read)
 {
+    constexpr bool W_RAW = (MODE & FWD_W_RAW) != 0, STATE_ONLY = (MODE & FWD_STATE_ONLY) != 0, AFF = (MODE & FWD_AFF) != 0;
     const int c4 = lane & 15, tq = lane >> 4;
     const long base = (long)b * a.T * a.C + (long)h * HEAD;
     const TokAddr<AFF> tok(ntok, rev != 0);
@@ -125,11 +144,21 @@ __device__ __forceinline__ bool fwd_hw_wave_produces(int hw) { return hw >= 4; }
 // instantiations: the state pass of every item that has a successor (STATE_ONLY: from zero, a.s_out / a.dsum indexed by the item), and the
 // forward per item (SNAP): entry state from the pool or from sg.sin, final state from a sequence's last item only, snapshot positions
 // counted from the sequence's first token.  All of it in front of and behind the group loops, which it leaves alone.
-template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF, bool CLK = false, bool CHAIN = false, bool VARLEN = false, bool SLOTS = false,
-          bool SNAP = false, bool SEG = false>
+template <unsigned MODE>
 __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned slot, const unsigned sslot, FwdRaw& raw, const FwdChain& ch = FwdChain{},
                                                const SegArgs& sg = SegArgs{})
 {
+    constexpr bool W_RAW = (MODE & FWD_W_RAW) != 0;
+    constexpr bool STATE_ONLY = (MODE & FWD_STATE_ONLY) != 0;
+    constexpr bool ACC = (MODE & FWD_ACC) != 0;
+    constexpr bool GN = (MODE & FWD_GN) != 0;
+    constexpr bool AFF = (MODE & FWD_AFF) != 0;
+    constexpr bool CLK = (MODE & FWD_CLK) != 0;
+    constexpr bool CHAIN = (MODE & FWD_CHAIN) != 0;
+    constexpr bool VARLEN = (MODE & FWD_VARLEN) != 0;
+    constexpr bool SLOTS = (MODE & FWD_SLOTS) != 0;
+    constexpr bool SNAP = (MODE & FWD_SNAP) != 0;
+    constexpr bool SEG = (MODE & FWD_SEG) != 0;
     [[maybe_unused]] const bool nxvalid = ch.nx_valid, chained_in = ch.chained_in, nx_use_u = ch.nx_use_u;
     [[maybe_unused]] const unsigned nxbh = ch.nx_bh;
     [[maybe_unused]] const int nxrev = ch.nx_rev, b_known = ch.b, ntok_known = ch.ntok, nxb = ch.nx_b, nxntok = ch.nx_ntok, pb = CHAIN ? ch.pb : 0;
@@ -386,8 +415,8 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
             // the consumers are busy with this call's last group: the raw registers are dead, the next call's first inputs can fly
             if (nxvalid) {
                 const int nxh = (int)(nxbh % (unsigned)a.H);
-                fwd_request_group<W_RAW, STATE_ONLY, AFF>(a, nxb, nxh, nxntok, nxrev, 0, wv, lane, raw);
-                prep_group(0, (ngrp + pb) & 1, nxntok, uu_nx, [&]() { fwd_request_group<W_RAW, STATE_ONLY, AFF>(a, nxb, nxh, nxntok, nxrev, 1, wv, lane, raw); });
+                fwd_request_group<MODE>(a, nxb, nxh, nxntok, nxrev, 0, wv, lane, raw);
+                prep_group(0, (ngrp + pb) & 1, nxntok, uu_nx, [&]() { fwd_request_group<MODE>(a, nxb, nxh, nxntok, nxrev, 1, wv, lane, raw); });
             }
         }
         if (ngrp > 0) __syncthreads();                        // the last group is consumed
@@ -768,7 +797,8 @@ template <bool W_RAW, bool STATE_ONLY, bool ACC, bool GN, bool AFF>
 __global__ __launch_bounds__(512) void chunk_fwd_kernel(const ScanArgs a)
 {
     FwdRaw raw;
-    chunk_fwd_body<W_RAW, STATE_ONLY, ACC, GN, AFF, !STATE_ONLY && !ACC && !GN>(a, blockIdx.x, 0u, raw);
+    chunk_fwd_body<bit(W_RAW, FWD_W_RAW) | bit(STATE_ONLY, FWD_STATE_ONLY) | bit(ACC, FWD_ACC) | bit(GN, FWD_GN) | bit(AFF, FWD_AFF) |
+                   bit(!STATE_ONLY && !ACC && !GN, FWD_CLK)>(a, blockIdx.x, 0u, raw);
 }
 
 // Packed variable-length batch: one workgroup per (sequence, head), the sequences longest first (a.order).  Instantiations of their own, so
@@ -777,7 +807,7 @@ template <bool W_RAW, bool STATE_ONLY>
 __global__ __launch_bounds__(512) void chunk_fwd_varlen_kernel(const ScanArgs a)
 {
     FwdRaw raw;
-    chunk_fwd_body<W_RAW, STATE_ONLY, false, false, true, false, false, true>(a, blockIdx.x, 0u, raw);
+    chunk_fwd_body<bit(W_RAW, FWD_W_RAW) | bit(STATE_ONLY, FWD_STATE_ONLY) | FWD_AFF | FWD_VARLEN>(a, blockIdx.x, 0u, raw);
 }
 
 // Packed stateful inference (rwkv6_forward_varlen_bf16): the fp32 decay itself as input (a.wkind == 2), the state in a slot of a pool.  A kernel
@@ -785,7 +815,7 @@ __global__ __launch_bounds__(512) void chunk_fwd_varlen_kernel(const ScanArgs a)
 __global__ __launch_bounds__(512) void chunk_fwd_varlen_slots_kernel(const ScanArgs a)
 {
     FwdRaw raw;
-    chunk_fwd_body<false, false, false, false, true, false, false, true, true>(a, blockIdx.x, 0u, raw);
+    chunk_fwd_body<FWD_AFF | FWD_VARLEN | FWD_SLOTS>(a, blockIdx.x, 0u, raw);
 }
 
 // ... with a separate output slot and state snapshots (rwkv6_forward_varlen_snap_bf16).  A kernel of its own: the one above keeps its
@@ -793,7 +823,7 @@ __global__ __launch_bounds__(512) void chunk_fwd_varlen_slots_kernel(const ScanA
 __global__ __launch_bounds__(512) void chunk_fwd_varlen_snap_kernel(const ScanArgs a)
 {
     FwdRaw raw;
-    chunk_fwd_body<false, false, false, false, true, false, false, true, true, true>(a, blockIdx.x, 0u, raw);
+    chunk_fwd_body<FWD_AFF | FWD_VARLEN | FWD_SLOTS | FWD_SNAP>(a, blockIdx.x, 0u, raw);
 }
 
 // ... with the long sequences cut into segments (rwkv6_forward_varlen_split_bf16; SEG above): the state pass of the items that have a
@@ -801,12 +831,12 @@ __global__ __launch_bounds__(512) void chunk_fwd_varlen_snap_kernel(const ScanAr
 __global__ __launch_bounds__(512) void chunk_fwd_varlen_seg_state_kernel(const ScanArgs a, const SegArgs sg)
 {
     FwdRaw raw;
-    chunk_fwd_body<false, true, false, false, true, false, false, true, false, false, true>(a, blockIdx.x, 0u, raw, FwdChain{}, sg);
+    chunk_fwd_body<FWD_STATE_ONLY | FWD_AFF | FWD_VARLEN | FWD_SEG>(a, blockIdx.x, 0u, raw, FwdChain{}, sg);
 }
 __global__ __launch_bounds__(512) void chunk_fwd_varlen_seg_kernel(const ScanArgs a, const SegArgs sg)
 {
     FwdRaw raw;
-    chunk_fwd_body<false, false, false, false, true, false, false, true, true, true, true>(a, blockIdx.x, 0u, raw, FwdChain{}, sg);
+    chunk_fwd_body<FWD_AFF | FWD_VARLEN | FWD_SLOTS | FWD_SNAP | FWD_SEG>(a, blockIdx.x, 0u, raw, FwdChain{}, sg);
 }
 
 // Packed rows under a per-tensor reversal map (a.rev_n, indexed by the sequence): general token addressing from the sequence's first token --
@@ -816,7 +846,7 @@ template <bool W_RAW, bool STATE_ONLY>
 __global__ __launch_bounds__(512) void chunk_fwd_varlen_rev_kernel(const ScanArgs a)
 {
     FwdRaw raw;
-    chunk_fwd_body<W_RAW, STATE_ONLY, false, false, false, false, false, true>(a, blockIdx.x, 0u, raw);
+    chunk_fwd_body<bit(W_RAW, FWD_W_RAW) | bit(STATE_ONLY, FWD_STATE_ONLY) | FWD_VARLEN>(a, blockIdx.x, 0u, raw);
 }
 
 // chunk_fwd_pair_kernel on packed rows: slots [0, n_seq H) serve a0, the rest a1; both problems share lens / tok_off / ck_off / order
@@ -826,7 +856,7 @@ __global__ __launch_bounds__(512) void chunk_fwd_varlen_pair_kernel(const ScanAr
     const unsigned n = (unsigned)(a0.B * a0.H);
     const bool second = blockIdx.x >= n;
     FwdRaw raw;
-    chunk_fwd_body<W_RAW, false, false, false, false, false, false, true>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, 0u, raw);
+    chunk_fwd_body<bit(W_RAW, FWD_W_RAW) | FWD_VARLEN>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, 0u, raw);
 }
 
 // Two problems of the same shape in one grid of 2 B H workgroups: slots [0, B H) serve a0, the rest a1 (src/model_bi.py:331-348,
@@ -837,7 +867,7 @@ __global__ __launch_bounds__(512) void chunk_fwd_pair_kernel(const ScanArgs a0, 
     const unsigned n = (unsigned)(a0.B * a0.H);
     const bool second = blockIdx.x >= n;                      // workgroup-uniform: the argument block is read through one of two
     FwdRaw raw;
-    chunk_fwd_body<W_RAW, false, false, false, false>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, 0u, raw);   // kernarg addresses; per-tensor reversal maps: general addressing
+    chunk_fwd_body<bit(W_RAW, FWD_W_RAW)>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, 0u, raw);   // kernarg addresses; per-tensor reversal maps: general addressing
 }
 
 // Both halves of wkv6_bi in one persistent launch (cuda/wkv6_bi_cuda.cu:363-368 is one launch too): workgroup slot s walks the rows
@@ -884,8 +914,8 @@ __global__ __launch_bounds__(512) void chunk_fwd_bi_kernel(const ScanArgs a1_, f
         {
             ScanArgs a1;
             load_kernargs(a1);
-            chunk_fwd_body<W_RAW, false, false, false, true, false, true>(a1, row, blockIdx.x, raw,
-                                                                          FwdChain{b_cur, ntok_cur, pb, chained, true, row, b_cur, ntok_cur, true, false});
+            chunk_fwd_body<bit(W_RAW, FWD_W_RAW) | FWD_AFF | FWD_CHAIN>(a1, row, blockIdx.x, raw,
+                                                                         FwdChain{b_cur, ntok_cur, pb, chained, true, row, b_cur, ntok_cur, true, false});
         }
         pb = (pb + ngrp_cur) & 1;
         if (!producer_wave) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -895,8 +925,8 @@ __global__ __launch_bounds__(512) void chunk_fwd_bi_kernel(const ScanArgs a1_, f
             ScanArgs a2;
             load_kernargs(a2);
             a2.reverse = 1; a2.use_u = 0; a2.accumulate = 1; a2.zero_tail = 0; a2.ckpt = ckpt2;
-            chunk_fwd_body<W_RAW, false, true, false, true, false, true>(a2, row, blockIdx.x, raw,
-                                                                         FwdChain{b_cur, ntok_cur, pb, true, row_nx < n, row_nx, b_nx, ntok_nx, false, use_u_ != 0});
+            chunk_fwd_body<bit(W_RAW, FWD_W_RAW) | FWD_ACC | FWD_AFF | FWD_CHAIN>(a2, row, blockIdx.x, raw,
+                                                                                   FwdChain{b_cur, ntok_cur, pb, true, row_nx < n, row_nx, b_nx, ntok_nx, false, use_u_ != 0});
         }
         pb = (pb + ngrp_cur) & 1;
         chained = true;

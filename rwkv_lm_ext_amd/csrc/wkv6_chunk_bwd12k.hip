@@ -105,6 +105,19 @@ __device__ __forceinline__ void split8(const float (&t0)[4], const float (&t1)[4
     lo = __builtin_bit_cast(b8v, make_uint4(l0.x, l0.y, l1.x, l1.y));
 }
 
+// The modes of chunk_bwd12k_body<MODE, GEN, ROLE>, one bit each.  A call site ORs the bits it switches on and names nothing else; a bit that
+// follows a kernel's own template parameter goes through bit().  (BWD_: the forward has FWD_ bits of its own, wkv6_chunk.hip.)  GEN and ROLE
+// are numbers and stay template parameters of their own.  The notes below call a bit by its name without the prefix, which is also the
+// constant the body reads it into.
+enum : unsigned {
+    BWD_W_RAW = 1u << 0,         // the decay input is the raw bf16 w (else: the fp32 ew)
+    BWD_SPLIT = 1u << 1,         // row role and column role as two workgroups on two CUs (ScanArgs::split)
+    BWD_AFF = 1u << 2,           // no per-tensor reversal map: affine token addressing (wkv6_scan.h: TokAddr)
+    BWD_CLK = 1u << 3,           // the in-run clock probe: the plain kernel only
+    BWD_CHAIN = 1u << 4,         // a call of the persistent wkv6_bi launch (BwdChain, BwdCarry below)
+    BWD_VARLEN = 1u << 5,        // packed batch: row b is sequence b of [total_T, C] tensors
+};
+constexpr unsigned bit(bool on, unsigned b) { return on ? b : 0u; }
 // GEN = 0: gradients are plain bf16 stores (buffer stores, tokens past the end dropped by the hardware): no store-mode
 // branches at all.  GEN = 1: the first half of wkv6_bi (fp32 side buffers instead of the outputs, tail zeroing) -- stores only.
 // GEN = 2: the second half (adds the first half and rounds once); the addends are requested ahead of the work whose result
@@ -157,9 +170,15 @@ struct BwdCarry {
 // that what one role carries from call to call (BwdCarry) is not live through the other roles' paths.
 // VARLEN (packed batches, chunk_bwd12k_varlen_kernel): row b is sequence b of [total_T, C] tensors -- tokens from a.tok_off[b], checkpoints from
 // slot a.ck_off[b] of its head's a.ck_stride slots (wkv6_scan.h)
-template <bool W_RAW, int GEN, bool SPLIT, bool AFF, bool CLK = false, bool CHAIN = false, int ROLE = 0, bool VARLEN = false>
+template <unsigned MODE, int GEN = 0, int ROLE = 0>
 __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsigned slot, BwdCarry& cy, const unsigned sslot = 0, const BwdChain& ch = BwdChain{})
 {
+    constexpr bool W_RAW = (MODE & BWD_W_RAW) != 0;
+    constexpr bool SPLIT = (MODE & BWD_SPLIT) != 0;
+    constexpr bool AFF = (MODE & BWD_AFF) != 0;
+    constexpr bool CLK = (MODE & BWD_CLK) != 0;
+    constexpr bool CHAIN = (MODE & BWD_CHAIN) != 0;
+    constexpr bool VARLEN = (MODE & BWD_VARLEN) != 0;
     [[maybe_unused]] const bool chained_in = CHAIN && ch.chained_in, nx_chain = CHAIN && ch.nx_chain;
     [[maybe_unused]] const int ko = CHAIN ? ch.ko : 0, ro = CHAIN ? ch.ro : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];          // [2][SBLK][RBLK_BYTES] | [3][SBLK][KBLK_BYTES] | tiles | G operand
@@ -1335,7 +1354,7 @@ template <bool W_RAW, int GEN, bool SPLIT, bool AFF>
 __global__ __launch_bounds__(SPLIT ? 512 : 768) void chunk_bwd12k_kernel(const ScanArgs a)
 {
     BwdCarry cy;       // (registers that outlive a call only in the persistent wkv6_bi launch: plain locals here)
-    chunk_bwd12k_body<W_RAW, GEN, SPLIT, AFF, GEN == 0>(a, blockIdx.x, cy);
+    chunk_bwd12k_body<bit(W_RAW, BWD_W_RAW) | bit(SPLIT, BWD_SPLIT) | bit(AFF, BWD_AFF) | bit(GEN == 0, BWD_CLK), GEN>(a, blockIdx.x, cy);
 }
 
 // Packed variable-length batch: one workgroup per (sequence, head), longest first (a.order); instantiations of their own (wkv6_chunk.hip)
@@ -1343,7 +1362,7 @@ template <bool W_RAW>
 __global__ __launch_bounds__(768) void chunk_bwd12k_varlen_kernel(const ScanArgs a)
 {
     BwdCarry cy;
-    chunk_bwd12k_body<W_RAW, 0, false, true, false, false, 0, true>(a, blockIdx.x, cy);
+    chunk_bwd12k_body<bit(W_RAW, BWD_W_RAW) | BWD_AFF | BWD_VARLEN>(a, blockIdx.x, cy);
 }
 
 // ... under a per-tensor reversal map (a.rev_n, indexed by the sequence): general token addressing, kernels of their own (wkv6_chunk.hip)
@@ -1351,7 +1370,7 @@ template <bool W_RAW>
 __global__ __launch_bounds__(768) void chunk_bwd12k_varlen_rev_kernel(const ScanArgs a)
 {
     BwdCarry cy;
-    chunk_bwd12k_body<W_RAW, 0, false, false, false, false, 0, true>(a, blockIdx.x, cy);
+    chunk_bwd12k_body<bit(W_RAW, BWD_W_RAW) | BWD_VARLEN>(a, blockIdx.x, cy);
 }
 
 // the backward of chunk_fwd_varlen_pair_kernel: slots [0, n_seq H) serve a0, the rest a1
@@ -1361,7 +1380,7 @@ __global__ __launch_bounds__(768) void chunk_bwd12k_varlen_pair_kernel(const Sca
     const unsigned n = (unsigned)(a0.B * a0.H);
     const bool second = blockIdx.x >= n;
     BwdCarry cy;
-    chunk_bwd12k_body<W_RAW, 0, false, false, false, false, 0, true>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, cy);
+    chunk_bwd12k_body<bit(W_RAW, BWD_W_RAW) | BWD_VARLEN>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, cy);
 }
 
 // the backward of chunk_fwd_pair_kernel (wkv6_chunk.hip): two problems of one shape, slots [0, B H) serve a0, the rest a1
@@ -1371,7 +1390,7 @@ __global__ __launch_bounds__(768) void chunk_bwd12k_pair_kernel(const ScanArgs a
     const unsigned n = (unsigned)(a0.B * a0.H);
     const bool second = blockIdx.x >= n;
     BwdCarry cy;
-    chunk_bwd12k_body<W_RAW, 0, false, false>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, cy);   // (per-tensor reversal maps: general addressing)
+    chunk_bwd12k_body<bit(W_RAW, BWD_W_RAW)>(second ? a1 : a0, second ? blockIdx.x - n : blockIdx.x, cy);   // (per-tensor reversal maps: general addressing)
 }
 
 // Both halves of wkv6_bi in one persistent launch (cuda/wkv6_bi_cuda.cu:363-377 runs one forward and three backward launches): workgroup
@@ -1428,8 +1447,8 @@ __global__ __launch_bounds__(768) void chunk_bwd12k_bi_kernel(const ScanArgs a1_
             {
                 ScanArgs a1;
                 load_kernargs(a1);
-                chunk_bwd12k_body<W_RAW, 1, false, true, false, true, ROLE>(a1, row, cy, blockIdx.x,
-                                                                            BwdChain{b_cur, ntok_cur, ko, ro, chained, chain12, row, b_cur, ntok_cur, true, false, ckpt2});
+                chunk_bwd12k_body<bit(W_RAW, BWD_W_RAW) | BWD_AFF | BWD_CHAIN, 1, ROLE>(a1, row, cy, blockIdx.x,
+                                                                                       BwdChain{b_cur, ntok_cur, ko, ro, chained, chain12, row, b_cur, ntok_cur, true, false, ckpt2});
             }
             ko = mod3(ko - n_cur); ro = (ro - n_cur) & 1;               // (the call that starts next is this row's reversed half: as many stages)
             // (the producer waves write no global memory, and a chained call has left their next requests in flight: they take no part in the fences)
@@ -1440,8 +1459,8 @@ __global__ __launch_bounds__(768) void chunk_bwd12k_bi_kernel(const ScanArgs a1_
                 ScanArgs a2;
                 load_kernargs(a2);
                 a2.reverse = 1; a2.use_u = 0; a2.accumulate = 1; a2.zero_tail = 0; a2.gu = nullptr; a2.ckpt = ckpt2;
-                chunk_bwd12k_body<W_RAW, 2, false, true, false, true, ROLE>(a2, row, cy, blockIdx.x,
-                                                                            BwdChain{b_cur, ntok_cur, ko, ro, chain12, chain2n, row_nx, b_nx, ntok_nx, false, use_u_ != 0, ckpt1_});
+                chunk_bwd12k_body<bit(W_RAW, BWD_W_RAW) | BWD_AFF | BWD_CHAIN, 2, ROLE>(a2, row, cy, blockIdx.x,
+                                                                                       BwdChain{b_cur, ntok_cur, ko, ro, chain12, chain2n, row_nx, b_nx, ntok_nx, false, use_u_ != 0, ckpt1_});
             }
             ko = mod3(ko - n_nx); ro = (ro - n_nx) & 1;                 // (the call that starts next is the next row's first half)
             chained = chain2n;

@@ -11,8 +11,7 @@
 import os
 import re
 import shutil
-import subprocess
-import tempfile
+import sys
 
 import numpy as np
 import pytest
@@ -22,6 +21,9 @@ import wkv5_numpy as w5
 from conftest import max_norm_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import isa_listing                                                  # noqa: E402
+
 EINVAL, ENULL, EUNSUPPORTED = -1, -2, -4
 P = 1                                       # a non-NULL dummy pointer
 
@@ -142,24 +144,17 @@ def test_wkv5_wrappers_refuse_cpu_and_non_bf16_tensors():
 def wkv5_asm():
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not on PATH")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-w", "-S", "--cuda-device-only"]
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "wkv5_scan.s")
-        subprocess.check_call(["hipcc"] + flags + ["-o", out, os.path.join(ROOT, "rwkv_lm_ext_amd", "csrc", "wkv5_scan.hip")])
-        return open(out).read()
+    return isa_listing.listing("wkv5_scan.hip")
 
 
 BF16_KERNELS = ("wkv5_fwd_kernelItE", "wkv5_bwd_a_kernelItE", "wkv5_bwd_g_kernelItE")       # t = unsigned short = raw bf16
 
 
 def test_no_spill_and_no_scratch_in_the_wkv5_kernels(wkv5_asm):
-    names = re.findall(r"^\s+\.name:\s+(\S+)", wkv5_asm, re.M)
-    spills = dict(zip(names, (int(x) for x in re.findall(r"^\s+\.vgpr_spill_count:\s+(\d+)", wkv5_asm, re.M))))
-    private = dict(zip(names, (int(x) for x in re.findall(r"^\s+\.private_segment_fixed_size:\s+(\d+)", wkv5_asm, re.M))))
-    vgprs = dict(zip(names, (int(x) for x in re.findall(r"^\s+\.vgpr_count:\s+(\d+)", wkv5_asm, re.M))))
+    spills, private, vgprs = (isa_listing.kernel_meta(wkv5_asm, k) for k in ("vgpr_spill_count", "private_segment_fixed_size", "vgpr_count"))
     for want in BF16_KERNELS:
-        hit = [n for n in names if want in n]
-        assert len(hit) == 1, (want, names)
+        hit = [n for n in spills if want in n]
+        assert len(hit) == 1, (want, list(spills))
         assert spills[hit[0]] == 0 and private[hit[0]] == 0, (hit[0], spills[hit[0]], private[hit[0]])
         assert vgprs[hit[0]] <= 128, (hit[0], vgprs[hit[0]])            # 512 threads: two workgroups per CU stay possible
     assert all(v == 0 for v in spills.values()) and all(v == 0 for v in private.values())       # the fp32 flavour too
@@ -170,20 +165,13 @@ def test_no_decay_stream_and_no_exp_inside_the_token_loops(wkv5_asm):
     """The loops of the forward read three streams from memory (r, k, v) and those of the backward passes four (r, k, v, gy):
     a decay stream would be one more load per batch of tokens, and a per-token decay an exponential inside the loop."""
     seen = 0
-    for fn in re.split(r"\n(?=_Z[\w]+:)", wkv5_asm):
-        name = fn.split(":", 1)[0]
+    for name, fn in isa_listing.functions(wkv5_asm).items():
         if not any(k in name for k in BF16_KERNELS):
             continue
         seen += 1
-        in_loop, loads, stores = False, 0, 0
-        for line in fn.split("\n"):
-            m = re.match(r"^\.LBB\d+_\d+:\s*(;.*)?$", line)
-            if m:
-                in_loop = "Loop" in (m.group(1) or "")
-                continue
+        loads, stores = 0, 0
+        for line in (x for _, c, lines in isa_listing.blocks(fn) if "Loop" in c for x in lines):
             op = line.strip().split(" ")[0] if line.strip() else ""
-            if not in_loop:
-                continue
             assert not op.startswith("v_exp"), (name, line.strip())
             assert not op.startswith("s_load") and not op.startswith("s_buffer_load"), (name, line.strip())
             loads += bool(re.match(r"(global|buffer|flat)_load", op))

@@ -10,52 +10,44 @@ only with counted vmcnt(N > 0); the producers' loop legitimately drains its queu
 """
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "rwkv_lm_ext_amd", "csrc", "wkv6_chunk_bwd12k.hip")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-w", "-S", "--cuda-device-only"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import isa_listing                                                  # noqa: E402
+
 KERNELS = ("chunk_bwd12k_kernelILb1ELi0ELb0ELb1EEE", "chunk_bwd12k_kernelILb0ELi0ELb0ELb1EEE")    # raw-w / fp32-ew, plain stores, one workgroup per pair
 
 
 def stage_loops(asm, kernel_substr):
     """[(header label, #buffer stores, #buffer loads, [vmcnt values waited for])] of the depth-1 loops of one kernel."""
-    for f in re.split(r"\n(?=_Z[\w]+:)", asm):
-        name = f.split(":", 1)[0]
-        if kernel_substr in name and name.startswith("_Z"):
-            break
-    else:
-        raise SystemExit(f"no function matching {kernel_substr}")
-    parent = {m.group(1): m.group(2) for m in re.finditer(r"^\.L(BB\d+_\d+):\s*;\s*Parent Loop (BB\d+_\d+) Depth=1", f, re.M)}
-    loops, cur = {}, None
-    for line in f.split("\n"):
-        m = re.match(r"^\.L(BB\d+_\d+):\s*(;.*)?$", line)
-        if m:
-            label, c = m.group(1), m.group(2) or ""
-            hdr = re.search(r"Header=(BB\d+_\d+) Depth=(\d+)", c)
-            if "Loop Header: Depth=1" in c:
-                cur = label
-            elif label in parent:
-                cur = parent[label]
-            elif hdr:
-                cur = parent.get(hdr.group(1), hdr.group(1))
-            else:
-                cur = None
-            continue
-        if cur is None or not line.startswith("\t"):
+    _, f = isa_listing.function(asm, kernel_substr)
+    blocks = list(isa_listing.blocks(f))
+    # header of a depth-2 loop -> header of the depth-1 loop around it
+    parent = {label: m.group(1) for label, c, _ in blocks for m in [re.match(r";\s*Parent Loop (BB\d+_\d+) Depth=1", c)] if m}
+    loops = {}
+    for label, c, lines in blocks:
+        hdr = re.search(r"Header=(BB\d+_\d+) Depth=(\d+)", c)
+        if "Loop Header: Depth=1" in c:
+            cur = label
+        elif label in parent:
+            cur = parent[label]
+        elif hdr:
+            cur = parent.get(hdr.group(1), hdr.group(1))
+        else:
             continue
         d = loops.setdefault(cur, {"stores": 0, "loads": 0, "waits": []})
-        op = line.strip().split()[0]
-        if op.startswith("buffer_store"):
-            d["stores"] += 1
-        elif op.startswith("buffer_load"):
-            d["loads"] += 1
-        elif op == "s_waitcnt":
-            w = re.search(r"vmcnt\((\d+)\)", line)
-            if w:
-                d["waits"].append(int(w.group(1)))
+        for line in lines:
+            if not line.startswith("\t"):
+                continue
+            op = line.strip().split()[0]
+            if op.startswith("buffer_store"):
+                d["stores"] += 1
+            elif op.startswith("buffer_load"):
+                d["loads"] += 1
+            elif op == "s_waitcnt":
+                w = re.search(r"vmcnt\((\d+)\)", line)
+                if w:
+                    d["waits"].append(int(w.group(1)))
     return [(k, v["stores"], v["loads"], v["waits"]) for k, v in loops.items()]
 
 
@@ -66,13 +58,7 @@ RELEASE_TAG_OFFSETS = (176, 336)
 
 
 def release_order(asm, kernel_substr, window=80):
-    for f in re.split(r"\n(?=_Z[\w]+:)", asm):
-        name = f.split(":", 1)[0]
-        if kernel_substr in name and name.startswith("_Z"):
-            break
-    else:
-        raise SystemExit(f"no function matching {kernel_substr}")
-    lines = f.split("\n")
+    lines = isa_listing.function(asm, kernel_substr)[1].split("\n")
     out = []
     for i, line in enumerate(lines):
         m = re.search(r"ds_write_b32 .*offset:(\d+)\b", line)
@@ -83,10 +69,7 @@ def release_order(asm, kernel_substr, window=80):
 
 
 def check(verbose=False):
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "k.s")
-        subprocess.check_call(["hipcc"] + FLAGS + ["-o", out, SRC], stderr=subprocess.DEVNULL)
-        asm = open(out).read()
+    asm = isa_listing.listing("wkv6_chunk_bwd12k.hip", quiet=True)
     bad = []
     for kern in KERNELS + ("chunk_bwd12k_kernelILb1ELi1ELb0ELb1EEE", "chunk_bwd12k_kernelILb1ELi2ELb0ELb1EEE", "chunk_bwd12k_pair_kernelILb1EEE"):
         rel = release_order(asm, kern)

@@ -17,11 +17,11 @@ issue drops to one per 8 cycles: an MFMA leaves room for 2 VALU instructions in 
 import argparse
 import collections
 import os
-import subprocess
+import re
 import sys
-import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import isa_listing                                                  # noqa: E402
 import issue_model as im                                            # noqa: E402
 
 QUARTER = ("v_exp", "v_log", "v_rcp", "v_rsq", "v_sqrt", "v_sin", "v_cos", "v_permlane")
@@ -54,22 +54,8 @@ def price(op, line, full):
     return None, 0.0
 
 
-def loops_priced(asm, kernel_substr, full):
-    funcs = __import__("re").split(r"\n(?=_Z[\w]+:)", asm)
-    name, loops = im.loops_of(asm, kernel_substr)
-    # re-walk with prices: loops_of keeps only histograms, so price the opcode histogram plus a second pass for operand-dependent classes
-    return name, loops
-
-
 def walk(asm, kernel_substr, kind, full, show_ops):
-    import re
-    funcs = re.split(r"\n(?=_Z[\w]+:)", asm)
-    for f in funcs:
-        nm = f.split(":", 1)[0]
-        if kernel_substr in nm and nm.startswith("_Z"):
-            break
-    else:
-        raise SystemExit("no function " + kernel_substr)
+    nm, f = isa_listing.function(asm, kernel_substr)
     parent = {}
     for m in re.finditer(r"^\.L(BB\d+_\d+):\s*;\s*Parent Loop (BB\d+_\d+) Depth=1", f, re.M):
         parent[m.group(1)] = m.group(2)
@@ -149,17 +135,11 @@ def walk(asm, kernel_substr, kind, full, show_ops):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ops", action="store_true", help="opcode histogram per role")
-    ap.add_argument("--csrc", default=im.CSRC, help="source directory (default: the tree's csrc)")
+    ap.add_argument("--csrc", default=isa_listing.CSRC, help="source directory (default: the tree's csrc)")
     args = ap.parse_args()
-    with tempfile.TemporaryDirectory() as tmp:
-        res = {}
-        for src in ("wkv6_chunk.hip", "wkv6_chunk_bwd12k.hip"):
-            out = os.path.join(tmp, src + ".s")
-            subprocess.check_call(["hipcc"] + im.FLAGS + ["-o", out, os.path.join(args.csrc, src)], stderr=subprocess.DEVNULL)
-            res[src] = open(out).read()
     for label, src, sub, kind, tokens, waves, full in (("forward", "wkv6_chunk.hip", "chunk_fwd_kernelILb1ELb0ELb0ELb0ELb1EEE", "fwd", 64, 2, 2.2),
                                                        ("backward", "wkv6_chunk_bwd12k.hip", "chunk_bwd12k_kernelILb1ELi0ELb0ELb1EEE", "bwd", 32, 3, 2.7)):
-        nm, rows = walk(res[src], sub, kind, full, args.ops)
+        nm, rows = walk(isa_listing.listing(src, args.csrc, quiet=True), sub, kind, full, args.ops)
         print(f"\n== {label}: {nm[:90]}\n   per loop iteration = {tokens} tokens of one (batch, head); one SIMD hosts one wave of every role ({waves} waves per SIMD); "
               f"full-rate VALU priced at {full} cycles")
         print(f"   {'role':9s} | {'full':>5s} {'half':>5s} {'quart':>5s} = {'VALU':>5s} | {'MFMA':>4s} {'LDS':>4s} | cycles: {'VALU':>6s} {'MFMA':>6s} {'LDS(SIMD share)':>15s} | VALU + MFMA")

@@ -17,13 +17,10 @@ by a few per cent, which the comparison with SQ_INSTS_VALU (profiles/r04_final_p
 import collections
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv_lm_ext_amd", "csrc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-S", "--cuda-device-only"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import isa_listing                                                  # noqa: E402
 
 SLOW_VALU = ("v_exp", "v_log", "v_rcp", "v_rsq", "v_sqrt", "v_permlane", "v_pk_", "v_cvt_f32_bf16", "v_readlane", "v_readfirstlane",
              "v_perm_b32", "v_lshl", "v_lshr", "v_ashr", "v_bfe", "v_and_or", "v_lshl_or", "v_lshl_add", "v_mul_lo", "v_mul_hi", "v_mad_u")
@@ -61,13 +58,7 @@ MFMA_CYC = 16
 
 def loops_of(asm, kernel_substr):
     """{loop header label: Counter of classes, plus 'ops' Counter} for the first function whose name contains kernel_substr."""
-    funcs = re.split(r"\n(?=_Z[\w]+:)", asm)
-    for f in funcs:
-        name = f.split(":", 1)[0]
-        if kernel_substr in name and name.startswith("_Z"):
-            break
-    else:
-        raise SystemExit(f"no function matching {kernel_substr}")
+    name, f = isa_listing.function(asm, kernel_substr)
     # pass 1: which depth-2 loop headers sit in which depth-1 loop (asm printer comments)
     parent = {}
     for m in re.finditer(r"^\.L(BB\d+_\d+):\s*;\s*Parent Loop (BB\d+_\d+) Depth=1", f, re.M):
@@ -146,14 +137,8 @@ def table(asm, kernel_substr, kind, unit_tokens, blocks_per_iter=1):
 
 
 def main():
-    with tempfile.TemporaryDirectory() as tmp:
-        res = {}
-        for src in ("wkv6_chunk.hip", "wkv6_chunk_bwd12k.hip"):
-            out = os.path.join(tmp, src + ".s")
-            subprocess.check_call(["hipcc"] + FLAGS + ["-o", out, os.path.join(CSRC, src)], stderr=subprocess.DEVNULL)
-            res[src] = open(out).read()
-    fwd = table(res["wkv6_chunk.hip"], "chunk_fwd_kernelILb1ELb0ELb0ELb0ELb1EEE", "fwd", 64)
-    bwd = table(res["wkv6_chunk_bwd12k.hip"], "chunk_bwd12k_kernelILb1ELi0ELb0ELb1EEE", "bwd", 32)
+    fwd = table(isa_listing.listing("wkv6_chunk.hip", quiet=True), "chunk_fwd_kernelILb1ELb0ELb0ELb0ELb1EEE", "fwd", 64)
+    bwd = table(isa_listing.listing("wkv6_chunk_bwd12k.hip", quiet=True), "chunk_bwd12k_kernelILb1ELi0ELb0ELb1EEE", "bwd", 32)
     # a SIMD hosts one wave of every role: what it must issue per loop iteration
     for label, rows, tokens, waves in (("forward", fwd, 64, 2), ("backward", bwd, 32, 3)):
         by = {}
