@@ -483,6 +483,43 @@ int wkv6_lora_packed_bf16(long total_T, int n_seq, int K, int N, int R, int n_ad
                           const int* cu_seqlens, const int* adapter,
                           const void* x, const void* A_pool, const void* B_pool, const float* scale,
                           void* y, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- device-side token sampling with a penalty slot pool (forward only; csrc/wkv6_sample.hip): the reference samples on the host, one
+ * sequence at a time (src/model_run.py:1230-1304, src/logits_processors.py); here one launch turns the logits rows of a decode step into
+ * token ids, every sequence with its own parameters, and the host reads nothing.  The sequence's decaying token-occurrence counts are a
+ * fourth state under the slot number of its WKV state and shift tokens.
+ *   logits [n_seq,ld] in the entry point's type, only columns < V count (ld % 8 == 0, ld >= V, 1 <= V <= 65536: a padded head);
+ *   occ_pool fp32 [n_slots,ld], columns >= V never touched;  slot int32 [n_seq] or NULL (slot = sequence index, n_slots >= n_seq);
+ *   slot_out int32 [n_seq] or NULL (in place);  params fp32 [n_seq,8] = temperature, top_p, top_k, alpha_presence, alpha_frequency,
+ *   alpha_decay, repetition_penalty, 0 (top_k an integral value, 0 or >= V: off);  u fp32 [n_seq] in [0,1): the caller's uniform draw;
+ *   tokens int32 [n_seq];  logprob fp32 [n_seq] or NULL.
+ * Sequence s with o = occ_pool[slot[s]] (a slot outside the pool: o = 0), all values fp32, rows independent of each other:
+ *   1. z[n] = logits[n] - (alpha_presence + o[n] * alpha_frequency) where o[n] > 0, else logits[n].  -inf logits are never drawn.
+ *   2. the order is (z descending, n ascending); p = softmax(z).
+ *   3. nucleus: c = the first position of the order whose inclusive cumulative p is >= top_p; kept = {n : z[n] >= z[order[c]]}, every
+ *      tie at the cutoff included; top_p >= 1 keeps everything.
+ *   4. top-k: with 0 < top_k < V only the first top_k of the order stay among the kept (the intersection of the two rules).
+ *   5. repetition penalty (1: off): on kept n with o[n] > 0, z[n] = z[n] < 0 ? z[n] * pen : z[n] / pen.
+ *   6. w[n] = exp((z[n] - max_kept z) / temperature) on the kept set, W = sum w.  temperature == 0 is greedy: 5. on every n, the token is
+ *      argmax z with the lowest id among equals, logprob = 0.
+ *   7. the draw runs in token-id order: the token is the smallest kept n with sum_{kept m <= n} w[m] > u W (none by rounding: the largest
+ *      kept id); logprob = log(w[token] / W).
+ *   8. occ_pool[(slot_out or slot)[s]] = o * alpha_decay, + 1 at the token (fp32 multiply, then add); a slot outside the pool stores nothing.
+ * A row with a NaN or +inf among its V logits, no finite logit, or a non-finite or negative parameter is poisoned: token -1, logprob NaN,
+ * its destination row untouched, its neighbours unaffected.  Pool entries are expected finite and >= 0.
+ * Weights are held as integers floor(w * 2^46) and summed as integers, so every sum over a row is exact in any order: the same call gives
+ * the same bits every time, and against exact arithmetic the CDF of 7. is off by at most V * 2^-46 of the largest weight.
+ * Aliasing as rwkv6_forward_varlen_snap_*: any number of readers of a source slot; slot_out == slot (or NULL) is the defined in-place use;
+ * two writers of one slot, or a slot one sequence writes and another reads, are out of contract but memory-safe.  Slot numbers and top_k
+ * are judged on the device before an address is formed from them.  One launch, one workgroup per sequence, no workspace.
+ * Refused before any launch, in this order: (1) WKV6_EINVAL -- n_seq, V or n_slots < 1, ld < V or ld % 8, slot == NULL with
+ * n_slots < n_seq, logits or occ_pool not 16-byte aligned, any other pointer not 4-byte aligned, occ_pool overlapping logits;
+ * (2) WKV6_EUNSUPPORTED -- V > 65536; (3) WKV6_ENULL -- a NULL logits, occ_pool, params, u or tokens. */
+int rwkv6_sample_slots_bf16(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot,
+                            const int* slot_out, const float* params, const float* u, int* tokens, float* logprob, void* stream);
+int rwkv6_sample_slots_fp16(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot,
+                            const int* slot_out, const float* params, const float* u, int* tokens, float* logprob, void* stream);
+int rwkv6_sample_slots_fp32(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot,
+                            const int* slot_out, const float* params, const float* u, int* tokens, float* logprob, void* stream);
 /* gn_gate (src/model.py:462-468): out = GroupNorm_H(y; gamma, beta, eps) * g on rows of C = 64 H channels (nn.GroupNorm(H, C)
  * applied to [rows, C]); stats fp32 [rows,H,2] (mean, rstd) is written for the backward (may be NULL in inference).
  * backward: dy, dg [rows,C]; dgamma_part, dbeta_part fp32 [nparts,C] partial sums. */

@@ -1,0 +1,456 @@
+// Device-side token sampling with a penalty slot pool (include/wkv6_amd.h: rwkv6_sample_slots_*), hand-written for gfx950: one launch
+// turns the logits rows of a packed decode step into token ids, every sequence with its own temperature / top-p / top-k / penalties, and
+// keeps the sequence's decaying token-occurrence counts under its slot number.  The header states the operation; this is how it is done.
+//
+// One workgroup of 1024 threads (16 waves) per sequence.  The row is not sorted and nothing of size V leaves the chip except the
+// occurrence row itself: the kept set of the definition is a THRESHOLD on the penalised logit z, so it is found by radix selection over
+// the monotone 32-bit key of z -- four passes of 8 bits, most significant digit first, with one 256-bin histogram of probability MASS
+// (nucleus) and one of COUNTS (top-k) in LDS -- and the ties at the top-k boundary are cut by a second radix selection over the token id.
+//
+// Where the row lives: in neither registers nor LDS.  Every pass streams the row again as 16-byte loads (thread t takes the chunks of 8
+// tokens t, t + 1024, ...) and recomputes z; after the first pass the loads are served by L2 / Infinity Cache, so a logits row and an
+// occurrence row cross HBM once in each direction.  64 fp32 values per lane would fit the 128-VGPR budget of 16 waves only with every
+// pass unrolled 64 times; a bf16 row in LDS does not hold the PENALISED logits exactly.  DESIGN.md 4.21 has the numbers.
+//
+// No floating-point sum runs over the row at all.  A weight exp(.) in [0, 1] becomes the integer floor(w * 2^46) the moment it is formed,
+// and every sum over the row (softmax denominator, histogram masses, W, the CDF of the draw) is a sum of these 64-bit integers: exact,
+// so its value cannot depend on the order in which waves or LDS atomics arrive, and the call is bit-reproducible.  65536 terms of at most
+// 2^46 stay below 2^63.  The quantisation is 2^-46 of the largest weight per term.
+#include <cmath>
+#include "wkv6_sample.h"
+
+// the same expression must give the same bits wherever it is inlined (weights are formed once for W and once more for the draw)
+#pragma clang fp contract(off)
+
+namespace wkv6 {
+namespace {
+
+typedef unsigned long long u64;
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+
+constexpr int THREADS = 1024, WAVES = THREADS / 64;
+constexpr int PARTS = SAMPLE_MAX_V / 8 / 64;                  // 128: the chunks of 8 tokens come in blocks of 64 (one wave, one round)
+constexpr float FIX = 70368744177664.f;                      // 2^46
+constexpr float NEG_INF = -__builtin_inff();
+
+// ---- 8 consecutive elements of a row as fp32
+template <typename T> __device__ __forceinline__ void load8(const T* p, float (&x)[8]);
+template <> __device__ __forceinline__ void load8<float>(const float* p, float (&x)[8])
+{
+    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+}
+template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t* p, float (&x)[8])
+{
+    const v4u raw = *reinterpret_cast<const v4u*>(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { x[2 * i] = bf_lo(raw[i]); x[2 * i + 1] = bf_hi(raw[i]); }
+}
+template <> __device__ __forceinline__ void load8<f16_t>(const f16_t* p, float (&x)[8])
+{
+    typedef f16_t h8 __attribute__((ext_vector_type(8)));
+    const h8 raw = *reinterpret_cast<const h8*>(p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = (float)raw[i];
+}
+template <typename T> __device__ __forceinline__ float load1(const T* p) { return (float)*p; }
+template <> __device__ __forceinline__ float load1<bf16_t>(const bf16_t* p) { return __uint_as_float((unsigned)*p << 16); }
+
+// ---- the monotone key of a (non-NaN) float: a > b  <=>  key(a) > key(b)
+__device__ __forceinline__ unsigned key_of(float z)
+{
+    const unsigned b = __float_as_uint(z);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float z_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// ---- what a sequence's row is made of
+struct Row {
+    const float* src;         // the occurrence row read, null: all zero
+    int V, nch;               // tokens, chunks of 8
+    float ap, af, pen;        // alpha_presence, alpha_frequency, repetition_penalty
+};
+
+// step 1 of the definition.  -0 becomes +0 (equal values, one key); a NaN can only come from a non-finite pool entry and counts as -inf.
+__device__ __forceinline__ float penalise(float x, float o, const Row& r)
+{
+    float z = o > 0.f ? x - (r.ap + o * r.af) : x;
+    if (z == 0.f) z = 0.f;
+    return z == z ? z : NEG_INF;
+}
+// step 5
+__device__ __forceinline__ float repeat_penalty(float z, float o, const Row& r)
+{
+    if (!(o > 0.f) || r.pen == 1.f) return z;
+    float y = z < 0.f ? z * r.pen : z / r.pen;
+    if (y == 0.f) y = 0.f;
+    return y == y ? y : NEG_INF;
+}
+// floor(exp((z - top) / t) * 2^46): at most 2^46, 0 for z = -inf (and for a NaN, which only garbage parameters can make)
+__device__ __forceinline__ u64 weight(float z, float top, float t) { return (u64)(expf((z - top) / t) * FIX); }
+
+template <typename T> __device__ __forceinline__ void load_chunk(const T* lg, const Row& r, int c, float (&z)[8], float (&o)[8])
+{
+    float x[8];
+    load8<T>(lg + 8 * c, x);
+    if (r.src) load8<float>(r.src + 8 * c, o);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (!r.src) o[j] = 0.f;
+        z[j] = penalise(x[j], o[j], r);
+    }
+}
+// f(n, z, o) for every token n < V, thread t on the chunks t, t + 1024, ...
+template <typename T, typename F> __device__ __forceinline__ void for_each_token(const T* lg, const Row& r, F f)
+{
+    for (int c = threadIdx.x; c < r.nch; c += THREADS) {
+        float z[8], o[8];
+        load_chunk(lg, r, c, z, o);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (8 * c + j < r.V) f(8 * c + j, z[j], o[j]);
+    }
+}
+
+// ---- workgroup and wave primitives.  Integer maxima and sums: any order gives the same bits.
+__device__ __forceinline__ u64 block_max(u64 v, u64* red)
+{
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const u64 t = __shfl_xor(v, off);
+        v = t > v ? t : v;
+    }
+    __syncthreads();                                         // red may still be read from the call before
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 m = red[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) m = red[w] > m ? red[w] : m;
+    return m;
+}
+__device__ __forceinline__ u64 wave_sum(u64 v)
+{
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ u64 wave_inclusive_scan(u64 v, int lane)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const u64 t = __shfl_up(v, off);
+        if (lane >= off) v += t;
+    }
+    return v;
+}
+
+struct Pick { unsigned digit; u64 above, equal; };
+// One wave: the largest bin d of hist[256] with hist[d] > 0 and above + sum_{d' >= d} hist[d'] >= target; where rounding leaves none,
+// the smallest bin with hist[d] > 0 (an empty histogram: bin 0).  .above: `above` plus everything in the bins over d; .equal: hist[d].
+__device__ __forceinline__ Pick select_bin(const u64* hist, u64 above, u64 target)
+{
+    const int lane = threadIdx.x & 63;
+    u64 h[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = hist[255 - (4 * lane + j)];         // lane 0 holds the top four bins
+    const u64 mine = h[0] + h[1] + h[2] + h[3];
+    const u64 before = above + wave_inclusive_scan(mine, lane) - mine;
+    int first = -1, last = -1;
+    u64 first_above = 0, first_equal = 0, last_above = 0, last_equal = 0, acc = before;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (h[j] > 0) {
+            if (first < 0 && acc + h[j] >= target) { first = 255 - (4 * lane + j); first_above = acc; first_equal = h[j]; }
+            last = 255 - (4 * lane + j); last_above = acc; last_equal = h[j];
+        }
+        acc += h[j];
+    }
+    const u64 hit = __ballot(first >= 0), any = __ballot(last >= 0);
+    Pick p = {0u, above, 0};
+    if (hit) {
+        const int src = __ffsll((long long)hit) - 1;
+        p.digit = (unsigned)__shfl(first, src); p.above = __shfl(first_above, src); p.equal = __shfl(first_equal, src);
+    } else if (any) {
+        const int src = 63 - __clzll((long long)any);
+        p.digit = (unsigned)__shfl(last, src); p.above = __shfl(last_above, src); p.equal = __shfl(last_equal, src);
+    }
+    return p;
+}
+
+// a thread's run of equal digits is added to the histogram once (the top digit of a row's keys takes a handful of values)
+struct Run {
+    unsigned digit = 0;
+    u64 sum = 0;
+    __device__ __forceinline__ void add(u64* hist, unsigned d, u64 v)
+    {
+        if (d != digit) { flush(hist); digit = d; }
+        sum += v;
+    }
+    __device__ __forceinline__ void flush(u64* hist)
+    {
+        if (sum) atomicAdd(&hist[digit], sum);
+        sum = 0;
+    }
+};
+
+struct Shared {
+    u64 hist_p[256], hist_k[256];     // nucleus: mass per digit; top-k (and the id selection behind it): count per digit
+    u64 red[WAVES];
+    u64 part[PARTS];                  // W per (round, wave) = per 512 consecutive tokens
+    Pick pick_p, pick_k;
+    u64 base;                         // the draw: W in front of the block that holds the token, and the block
+    int block, token;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs a)
+{
+    __shared__ Shared sh;
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const T* lg = static_cast<const T*>(a.logits) + (long)s * a.ld;
+
+    // parameters and slots: judged before anything is addressed with them
+    float prm[8];
+    bool poisoned = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        prm[i] = a.params[(long)s * 8 + i];
+        poisoned |= !(prm[i] >= 0.f && prm[i] < __builtin_inff());
+    }
+    const float temperature = prm[0], top_p = prm[1], decay = prm[5];
+    const int from = a.slot ? a.slot[s] : s, to = a.slot_out ? a.slot_out[s] : from;
+    Row r;
+    r.src = from >= 0 && from < a.n_slots ? a.occ + (long)from * a.ld : nullptr;
+    float* const dst = to >= 0 && to < a.n_slots ? a.occ + (long)to * a.ld : nullptr;
+    r.V = a.V; r.nch = (a.V + 7) / 8;
+    r.ap = prm[3]; r.af = prm[4]; r.pen = prm[6];
+    const int k = prm[2] >= 1.f && prm[2] < (float)a.V ? (int)prm[2] : 0;            // 0: top-k is off
+    const bool use_p = top_p < 1.f, use_k = k > 0;
+
+    // ---- pass A: is the row sound, and max z.  (A logit of +inf has no softmax: it poisons the row like a NaN.)
+    int bad = 0, finite = 0;
+    unsigned kmax = 0;
+    for (int c = tid; c < r.nch; c += THREADS) {
+        float x[8], z[8], o[8];
+        load8<T>(lg + 8 * c, x);
+        load_chunk(lg, r, c, z, o);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (8 * c + j < r.V) {
+                bad |= !(x[j] < __builtin_inff());
+                finite |= x[j] > NEG_INF;
+                kmax = max(kmax, key_of(z[j]));
+            }
+    }
+    bad = __syncthreads_or(bad);
+    finite = __syncthreads_or(finite);
+    const float top = z_of((unsigned)block_max(kmax, sh.red));
+    if (poisoned || bad || !finite || !(top > NEG_INF)) {
+        if (tid == 0) {
+            a.tokens[s] = -1;
+            if (a.logprob) a.logprob[s] = __builtin_nanf("");
+        }
+        return;
+    }
+
+    int token;
+    float top_kept = 0.f;
+    u64 W = 0;
+    if (temperature == 0.f) {
+        // ---- greedy: argmax of the repetition-penalised z, the lowest id among equals
+        u64 best = 0;
+        for_each_token(lg, r, [&](int n, float z, float o) {
+            const u64 v = ((u64)key_of(repeat_penalty(z, o, r)) << 32) | (0xffffffffu - (unsigned)n);
+            best = v > best ? v : best;
+        });
+        token = (int)(0xffffffffu - (unsigned)block_max(best, sh.red));
+    } else {
+        // ---- radix selection, 8 bits a pass: key_p = the largest key whose mass {key >= key_p} reaches top_p of the total, key_k = the
+        // k-th largest key.  A pass adds to the histograms only the tokens that match the digits found so far.
+        unsigned key_p = 0, key_k = 0;
+        u64 above_p = 0, above_k = 0, equal_k = 0, target_p = 0;
+        for (int pass = 0; pass < 4 && (use_p || use_k); ++pass) {
+            const int shift = 24 - 8 * pass;
+            if (tid < 256) sh.hist_p[tid] = sh.hist_k[tid] = 0;
+            __syncthreads();
+            Run run_p, run_k;
+            for_each_token(lg, r, [&](int, float z, float) {
+                const unsigned key = key_of(z), digit = (key >> shift) & 255u;
+                if (use_p && (pass == 0 || (key ^ key_p) >> (shift + 8) == 0)) run_p.add(sh.hist_p, digit, weight(z, top, 1.f));
+                if (use_k && (pass == 0 || (key ^ key_k) >> (shift + 8) == 0)) run_k.add(sh.hist_k, digit, 1);
+            });
+            run_p.flush(sh.hist_p);
+            run_k.flush(sh.hist_k);
+            __syncthreads();
+            if (wave == 0 && use_p) {
+                if (pass == 0) {        // the softmax denominator is the whole first histogram
+                    const u64 S = wave_sum(sh.hist_p[lane] + sh.hist_p[lane + 64] + sh.hist_p[lane + 128] + sh.hist_p[lane + 192]);
+                    const double t = ceil((double)top_p * (double)S);
+                    target_p = t >= (double)S ? S : (u64)t;
+                }
+                const Pick p = select_bin(sh.hist_p, above_p, target_p);
+                if (lane == 0) sh.pick_p = p;
+            }
+            if (wave == 1 && use_k) {
+                const Pick p = select_bin(sh.hist_k, above_k, (u64)k);
+                if (lane == 0) sh.pick_k = p;
+            }
+            __syncthreads();
+            if (use_p) { key_p |= sh.pick_p.digit << shift; above_p = sh.pick_p.above; }
+            if (use_k) { key_k |= sh.pick_k.digit << shift; above_k = sh.pick_k.above; equal_k = sh.pick_k.equal; }
+        }
+        // ---- ties at the top-k boundary: of the equal_k tokens at key_k the k - above_k lowest ids stay.  Where that is not all of them,
+        // the same selection over 65535 - n (two passes) finds the last id that stays.
+        unsigned rid_cut = 0;                                 // tokens at key_k stay while 65535 - n >= rid_cut
+        if (use_k && (u64)k - above_k < equal_k) {
+            u64 above_id = 0;
+            for (int pass = 0; pass < 2; ++pass) {
+                const int shift = 8 - 8 * pass;
+                if (tid < 256) sh.hist_k[tid] = 0;
+                __syncthreads();
+                Run run;
+                for_each_token(lg, r, [&](int n, float z, float) {
+                    const unsigned rid = 65535u - (unsigned)n;
+                    if (key_of(z) == key_k && (pass == 0 || (rid ^ rid_cut) >> 8 == 0)) run.add(sh.hist_k, (rid >> shift) & 255u, 1);
+                });
+                run.flush(sh.hist_k);
+                __syncthreads();
+                if (wave == 0) {
+                    const Pick p = select_bin(sh.hist_k, above_id, (u64)k - above_k);
+                    if (lane == 0) sh.pick_k = p;
+                }
+                __syncthreads();
+                rid_cut |= sh.pick_k.digit << shift;
+                above_id = sh.pick_k.above;
+            }
+        }
+        const auto kept = [&](int n, float z) {
+            const unsigned key = key_of(z);
+            return key >= key_p && (!use_k || key > key_k || (key == key_k && 65535u - (unsigned)n >= rid_cut));
+        };
+
+        // ---- pass C: the largest repetition-penalised z of the kept set, and its largest id
+        unsigned ktop = 0, nmax = 0;
+        for_each_token(lg, r, [&](int n, float z, float o) {
+            if (kept(n, z)) { ktop = max(ktop, key_of(repeat_penalty(z, o, r))); nmax = (unsigned)n + 1; }
+        });
+        top_kept = z_of((unsigned)block_max(ktop, sh.red));
+        const int last_kept = (int)block_max(nmax, sh.red) - 1;
+
+        // ---- pass D: W, kept per block of 512 consecutive tokens (one wave, one round) for the draw
+        if (tid < PARTS) sh.part[tid] = 0;
+        if (tid == 0) { sh.block = -1; sh.token = last_kept; }
+        __syncthreads();
+        const int rounds = (r.nch + THREADS - 1) / THREADS;
+        const auto chunk_weights = [&](int c, u64 (&w)[8]) {
+            float z[8], o[8];
+            load_chunk(lg, r, c, z, o);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                w[j] = 8 * c + j < r.V && kept(8 * c + j, z[j]) ? weight(repeat_penalty(z[j], o[j], r), top_kept, temperature) : 0;
+        };
+        for (int i = 0; i < rounds; ++i) {
+            const int c = tid + THREADS * i;
+            u64 w[8], sum = 0;
+            if (c < r.nch) {
+                chunk_weights(c, w);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) sum += w[j];
+            }
+            sum = wave_sum(sum);
+            if (lane == 0) sh.part[i * WAVES + wave] = sum;
+        }
+        __syncthreads();
+        // ---- the draw, in token-id order: wave 0 finds the block of 512 tokens in which the CDF passes u W, that block's wave the token
+        u64 target = 0;
+        if (wave == 0) {
+            const u64 p0 = sh.part[2 * lane], p1 = sh.part[2 * lane + 1];
+            const u64 incl = wave_inclusive_scan(p0 + p1, lane), before = incl - (p0 + p1);
+            W = __shfl(incl, 63);
+            const float uu = a.u[s];
+            const double t = (double)(uu >= 0.f ? uu : 0.f) * (double)W;       // (a NaN u draws as 0)
+            target = W == 0 ? 0 : t >= (double)W ? W - 1 : (u64)t;
+            const int blk = before + p0 > target ? 2 * lane : incl > target ? 2 * lane + 1 : -1;
+            const u64 hit = __ballot(blk >= 0);
+            if (hit && lane == __ffsll((long long)hit) - 1) {
+                sh.block = blk;
+                sh.base = blk & 1 ? before + p0 : before;
+            }
+            if (lane == 0) { sh.red[0] = W; sh.red[1] = target; }
+        }
+        __syncthreads();
+        W = sh.red[0]; target = sh.red[1];
+        if (sh.block >= 0 && wave == (sh.block & (WAVES - 1))) {
+            const int c = tid + THREADS * (sh.block / WAVES);
+            u64 w[8] = {}, sum = 0;
+            if (c < r.nch) chunk_weights(c, w);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sum += w[j];
+            u64 acc = sh.base + wave_inclusive_scan(sum, lane) - sum;
+            int found = -1;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                acc += w[j];
+                if (found < 0 && acc > target) found = 8 * c + j;
+            }
+            const u64 hit = __ballot(found >= 0);
+            if (hit && lane == __ffsll((long long)hit) - 1) sh.token = found;
+        }
+        __syncthreads();
+        token = sh.token;                                    // (where rounding left none: the largest kept id)
+    }
+    if (token < 0 || token >= r.V) {                         // no kept token at all: only garbage in the pool or the parameters gets here
+        if (tid == 0) {
+            a.tokens[s] = -1;
+            if (a.logprob) a.logprob[s] = __builtin_nanf("");
+        }
+        return;
+    }
+    if (tid == 0) {
+        a.tokens[s] = token;
+        if (a.logprob) {
+            float lp = 0.f;                                  // greedy: the distribution is the one token
+            if (temperature != 0.f) {
+                const float o = r.src ? r.src[token] : 0.f;
+                const float z = repeat_penalty(penalise(load1<T>(lg + token), o, r), o, r);
+                lp = (float)((double)((z - top_kept) / temperature) - log((double)W / (double)FIX));
+            }
+            a.logprob[s] = lp;
+        }
+    }
+    __syncthreads();                                         // the row is read for the last time above: now it may be overwritten
+
+    // ---- the update: dst = o * alpha_decay, + 1 at the token; columns >= V are not touched
+    if (dst == nullptr) return;
+    for (int c = tid; c < r.nch; c += THREADS) {
+        float o[8];
+        if (r.src) load8<float>(r.src + 8 * c, o);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            o[j] = r.src ? o[j] * decay : 0.f;
+            if (8 * c + j == token) o[j] = o[j] + 1.f;
+        }
+        if (8 * c + 8 <= r.V) {
+            *reinterpret_cast<float4*>(dst + 8 * c) = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<float4*>(dst + 8 * c + 4) = make_float4(o[4], o[5], o[6], o[7]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (8 * c + j < r.V) dst[8 * c + j] = o[j];
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_sample_slots(const SampleArgs& a, int io, hipStream_t st)
+{
+    if (!(a.logits && a.occ && a.params && a.u && a.tokens)) return hipErrorInvalidValue;
+    if (a.n_seq < 1 || a.n_slots < 1 || a.V < 1 || a.V > SAMPLE_MAX_V || a.ld < a.V || a.ld % 8) return hipErrorInvalidValue;
+    const dim3 grid(a.n_seq), block(THREADS);
+    if (io == IO_F32) return launch<sample_slots_kernel<float>>(grid, block, 0, st, a);
+    if (io == IO_F16) return launch<sample_slots_kernel<f16_t>>(grid, block, 0, st, a);
+    return launch<sample_slots_kernel<bf16_t>>(grid, block, 0, st, a);
+}
+
+}  // namespace wkv6

@@ -271,3 +271,136 @@ def last_token_rows(x, cu_seqlens, max_seqlen):
     rows = torch.zeros((cu_seqlens.numel() - 1, x.shape[-1]), device=x.device, dtype=x.dtype)
     mix_op.shift_keep(x, cu_seqlens, int(max_seqlen), rows, None)
     return rows
+
+
+# ---- the last step of the serving loop: logits rows to token ids on the device.  The sequence's decaying token-occurrence counts are a
+# fourth state under the slot number of its WKV state and shift tokens, in a pool of its own so that PackedPools stays what it is.
+@dataclass
+class SamplingPool:
+    """occ fp32 [n_slots,ld]: row p holds the occurrence counts of the sequence in slot p over the first `vocab` columns; the others are
+    padding (ld: a multiple of 8, the row stride of the padded head's logits) and are never touched."""
+    occ: torch.Tensor
+    vocab: int
+
+    @staticmethod
+    def create(n_slots, vocab, device, ld=None):
+        ld = (vocab + 7) // 8 * 8 if ld is None else int(ld)
+        if ld < vocab or ld % 8:
+            raise ValueError(f"ld must be a multiple of 8 and at least vocab = {vocab}, got {ld}")
+        return SamplingPool(torch.zeros((n_slots, ld), device=device, dtype=torch.float32), int(vocab))
+
+
+def sampling_params(n_seq, device, temperature=1.0, top_p=1.0, top_k=0, alpha_presence=0.0, alpha_frequency=0.0, alpha_decay=1.0,
+                    repetition_penalty=1.0):
+    """params fp32 [n_seq,8] with every sequence on the given settings (the columns in the order of the arguments, then 0); a serving loop
+    then writes the rows of the sequences that differ."""
+    row = (temperature, top_p, top_k, alpha_presence, alpha_frequency, alpha_decay, repetition_penalty, 0.0)
+    return torch.tensor(row, dtype=torch.float32, device=device).repeat(n_seq, 1)
+
+
+def _first_true(mask, none):
+    """[rows]: the first column at which mask [rows,V] holds, `none` where it never does."""
+    V = mask.shape[1]
+    cols = torch.arange(V, device=mask.device).expand_as(mask)
+    first = torch.where(mask, cols, torch.full_like(cols, V)).amin(1)
+    return torch.where(first < V, first, none)
+
+
+def _sample_eager(logits, occ, slots, params, u, out_slots):
+    """The operation of include/wkv6_amd.h (rwkv6_sample_slots_*) restated with torch ops, on any device: fp32 z, one stable sort for the
+    order, fp64 sums.  Reads nothing on the host."""
+    n_seq, V = logits.shape
+    n_slots, dev = occ.shape[0], logits.device
+    x = logits.float()
+    src = torch.arange(n_seq, device=dev) if slots is None else slots.long()
+    dst = src if out_slots is None else out_slots.long()
+    src_ok, dst_ok = (src >= 0) & (src < n_slots), (dst >= 0) & (dst < n_slots)
+    o = occ[src.clamp(0, n_slots - 1)].masked_fill(~src_ok.unsqueeze(1), 0.0)
+    temp, top_p, top_k, ap, af, decay, pen = (params[:, i:i + 1] for i in range(7))
+    inf = float("inf")
+    poisoned = ~(x < inf).all(1) | ~(x > -inf).any(1) | ~((params >= 0) & (params < inf)).all(1)
+    z = torch.where(o > 0, x - (ap + o * af), x)
+    z = torch.where(z == 0, torch.zeros_like(z), z)
+    z = torch.where(z == z, z, torch.full_like(z, -inf))
+    # 2.-4.: the order, the nucleus threshold with its ties, the first top_k of the order
+    zs, order = torch.sort(z, dim=1, descending=True, stable=True)
+    cum = torch.softmax(zs.double(), 1).cumsum(1)
+    reach = cum >= top_p.double()
+    c = _first_true(reach, torch.full((n_seq,), V - 1, device=dev))
+    cut = torch.where((top_p < 1) & reach.any(1, keepdim=True), zs.gather(1, c.unsqueeze(1)), torch.full_like(top_p, -inf))
+    kept_sorted = zs >= cut
+    k_on = (top_k >= 1) & (top_k < V)
+    kept_sorted &= ~k_on | (torch.arange(V, device=dev).unsqueeze(0) < top_k.floor())
+    kept = torch.zeros_like(kept_sorted).scatter_(1, order, kept_sorted)
+    # 5.-7.
+    z2 = torch.where(z < 0, z * pen, z / pen)
+    z2 = torch.where(z2 == 0, torch.zeros_like(z2), z2)
+    z2 = torch.where((o > 0) & (pen != 1), torch.where(z2 == z2, z2, torch.full_like(z2, -inf)), z)
+    greedy = temp == 0
+    none = torch.full((n_seq,), -1, device=dev)
+    tok_greedy = _first_true(z2 == z2.amax(1, keepdim=True), none)
+    top = z2.masked_fill(~kept, -inf).amax(1, keepdim=True)
+    w = torch.where(kept, torch.exp(((z2 - top) / torch.where(greedy, torch.ones_like(temp), temp)).double()), torch.zeros_like(cum))
+    cdf = w.cumsum(1)
+    W = cdf[:, -1:]
+    last_kept = V - 1 - _first_true(kept.flip(1), torch.full((n_seq,), V, device=dev))
+    tok_drawn = _first_true(cdf > u.double().clamp_min(0).unsqueeze(1) * W, last_kept)
+    token = torch.where(greedy.squeeze(1), tok_greedy, tok_drawn)
+    poisoned = poisoned | (token < 0)
+    at = token.clamp(0, V - 1).unsqueeze(1)
+    logprob = torch.where(greedy, torch.zeros_like(W), torch.log(w.gather(1, at) / W)).squeeze(1).float()
+    # 8.: rows of poisoned sequences and of slots outside the pool go to a dummy row behind the pool
+    new = (o * decay).scatter_add_(1, at, torch.ones_like(at, dtype=torch.float32))
+    dest = torch.where(dst_ok & ~poisoned, dst, torch.full_like(dst, n_slots))
+    occ.copy_(torch.cat((occ, occ.new_zeros(1, V))).index_copy_(0, dest, new)[:n_slots])
+    nan = torch.full_like(logprob, float("nan"))
+    return torch.where(poisoned, none, token).int(), torch.where(poisoned, nan, logprob)
+
+
+def _sample_kernel(logits, occ, slots, params, u, out_slots, kernels):
+    """Whether mix_op.sample_slots serves this call (kernels as pool_kernels of _pool_kernels: None where it applies, False never, True it
+    must -- then mix_op says what is wrong)."""
+    if kernels is False:
+        return False
+    if kernels:
+        return True
+    def ints(t):
+        return t is None or (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and t.device == logits.device)
+    def floats(t, shape):
+        return t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == logits.device
+    n_seq, V = logits.shape
+    ld = logits.stride(0)
+    return (logits.is_cuda and logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and logits.stride(1) == 1 and ld >= V
+            and ld % 8 == 0 and V <= 65536 and occ.device == logits.device and occ.stride(1) == 1 and occ.stride(0) == ld
+            and logits.data_ptr() % 16 == 0 and occ.data_ptr() % 16 == 0 and ints(slots) and ints(out_slots) and floats(params, (n_seq, 8))
+            and floats(u, (n_seq,)) and (slots is not None or occ.shape[0] >= n_seq)
+            and not (torch.is_grad_enabled() and any(t.requires_grad for t in (logits, occ, params, u))))
+
+
+def sample_packed(logits, pool, slots, params, u, out_slots=None, kernels=None):
+    """(tokens int32 [n_seq], logprob fp32 [n_seq]): one token per row of logits [n_seq, >= pool.vocab] (the columns past the vocabulary are
+    a padded head's and are ignored), sequence s with params[s] (fp32 [n_seq,8]: see sampling_params) and the uniform draw u[s]; its
+    occurrence counts are read from pool.occ[slots[s]] (slots None: row s; a slot outside the pool: zero) and written, decayed and with the
+    token counted, to pool.occ[out_slots[s]] (None: in place).  A poisoned row (NaN or +inf logits, no finite logit, a negative or
+    non-finite parameter) gives -1 and NaN and keeps its counts.  include/wkv6_amd.h states the operation.
+    kernels None: one mix_op.sample_slots launch where it applies (GPU tensors, the row stride of logits a multiple of 8 and equal to the
+    pool's), else the eager restatement, which also serves the CPU; False: always the eager code; True: the kernel, or this raises."""
+    if not (isinstance(logits, torch.Tensor) and logits.dim() == 2 and logits.shape[1] >= pool.vocab):
+        raise RuntimeError(f"logits must be [n_seq, >= vocab = {pool.vocab}]")
+    lg, occ = logits[:, :pool.vocab], pool.occ[:, :pool.vocab]
+    if _sample_kernel(lg, occ, slots, params, u, out_slots, kernels):
+        from . import mix_op
+        return mix_op.sample_slots(lg, occ, slots, params, u, out_slots=out_slots, want_logprob=True)
+    with torch.no_grad():
+        return _sample_eager(lg, occ, slots, params, u, out_slots)
+
+
+def decode_step_packed(emb, blocks, ln_out, head, tokens, pools, sampling_pool, slots, params, u, cu_seqlens, pool_kernels=None, kernels=None):
+    """One decode step of every sequence of a serving batch, token ids in and token ids out: emb(tokens) -> step_packed (one token per
+    sequence: cu_seqlens is arange(n_seq + 1), int32 on the device) -> ln_out -> head -> sample_packed.  tokens int32 [n_seq]; returns the
+    new tokens int32 [n_seq] (-1 for a poisoned row; such an id is embedded as token 0 if it is fed back).  All four states of sequence s
+    live under slots[s], in place.  pool_kernels as in step_packed, kernels as in sample_packed.  Nothing is read on the host, so the step
+    can be captured in a graph and replayed with tokens and u refilled in place."""
+    x = emb(tokens.clamp_min(0)).unsqueeze(0)
+    x = step_packed(blocks, x, cu_seqlens, 1, pools, slots, pool_kernels=pool_kernels)
+    return sample_packed(head(ln_out(x[0])), sampling_pool, slots, params, u, kernels=kernels)[0]

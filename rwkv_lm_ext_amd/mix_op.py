@@ -277,6 +277,65 @@ def lora_packed(x, y, A_pool, B_pool, scale, adapter, cu_seqlens):
     return y
 
 
+# ---- device-side token sampling with a penalty slot pool (include/wkv6_amd.h: rwkv6_sample_slots_*); inference only: no autograd.  Shapes
+# and types are judged first, the device last (there is no CPU path here: infctx.sample_packed has the eager one).
+SAMPLE_MAX_VOCAB = 65536
+_SAMPLE_ENTRY = {torch.bfloat16: "rwkv6_sample_slots_bf16", torch.float16: "rwkv6_sample_slots_fp16", torch.float32: "rwkv6_sample_slots_fp32"}
+
+
+def _rows_in_storage(t, ld):
+    """Whether every row of the 2-d view t may be read up to the next multiple of 8 columns (the kernel's 16-byte accesses)."""
+    last = t.storage_offset() + (t.shape[0] - 1) * ld + (t.shape[1] + 7) // 8 * 8
+    return last * t.element_size() <= t.untyped_storage().nbytes()
+
+
+def sample_slots(logits, occ_pool, slots, params, u, out_slots=None, want_logprob=False):
+    """One token per row of logits [n_seq, V] (bf16, fp16 or fp32; a view of the first V columns of a contiguous [n_seq, ld] tensor, ld % 8
+    == 0, is taken as it is), every sequence with its own params[s] = (temperature, top_p, top_k, alpha_presence, alpha_frequency,
+    alpha_decay, repetition_penalty, 0) and uniform draw u[s]; the operation is stated in include/wkv6_amd.h.  occ_pool fp32 [n_slots, ld]
+    (or a view of the first V columns of one) holds the sequences' decaying occurrence counts: row slots[s] is read (slots None: row s), row
+    out_slots[s] (None: the same row) is written, in place.  Returns tokens int32 [n_seq], with want_logprob (tokens, logprob fp32 [n_seq]);
+    a poisoned row gives -1 and NaN.  Nothing is read on the host.  Raises when a gradient is required."""
+    if not (isinstance(logits, torch.Tensor) and logits.dtype in _SAMPLE_ENTRY and logits.dim() == 2 and logits.shape[0] >= 1
+            and logits.shape[1] >= 1 and logits.stride(1) == 1):
+        raise RuntimeError("logits must be a bf16, fp16 or fp32 tensor [n_seq, V] with unit stride along V")
+    n_seq, V = logits.shape
+    ld = logits.stride(0)
+    if ld < V or ld % 8 or not _rows_in_storage(logits, ld):
+        raise RuntimeError(f"logits rows must lie ld elements apart in memory, ld a multiple of 8 and >= V = {V}: pass the first V columns "
+                           f"of a padded [n_seq, ld] tensor (INTEGRATION.md), got a row stride of {ld}")
+    if V > SAMPLE_MAX_VOCAB:
+        raise RuntimeError(f"sample_slots: V must be at most {SAMPLE_MAX_VOCAB}, got {V}")
+    if not (isinstance(occ_pool, torch.Tensor) and occ_pool.dtype == torch.float32 and occ_pool.dim() == 2 and occ_pool.shape[0] >= 1
+            and occ_pool.shape[1] == V and occ_pool.stride(1) == 1 and occ_pool.stride(0) == ld and _rows_in_storage(occ_pool, ld)):
+        raise RuntimeError(f"occ_pool must be an fp32 tensor [n_slots, V = {V}] whose rows lie ld = {ld} elements apart, as the rows of "
+                           "logits do (it is used in place, never copied)")
+    n_slots = occ_pool.shape[0]
+    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and tuple(params.shape) == (n_seq, 8) and params.is_contiguous()):
+        raise RuntimeError(f"params must be a contiguous fp32 tensor [n_seq = {n_seq}, 8]")
+    if not (isinstance(u, torch.Tensor) and u.dtype == torch.float32 and tuple(u.shape) == (n_seq,) and u.is_contiguous()):
+        raise RuntimeError(f"u must be a contiguous fp32 tensor [n_seq = {n_seq}]")
+    if slots is None and n_slots < n_seq:
+        raise RuntimeError("slots = None means slot = sequence index: the pool must hold n_seq slots")
+    if slots is not None:
+        _check_ints(slots, (n_seq,), "slots")
+    if out_slots is not None:
+        _check_ints(out_slots, (n_seq,), "out_slots")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (logits, occ_pool, params, u)):
+        raise RuntimeError("sample_slots has no backward: call it under torch.no_grad()")
+    if not logits.is_cuda:
+        raise RuntimeError("logits must be on the GPU (sample_slots has no CPU path: infctx.sample_packed has the eager one)")
+    if any(t is not None and t.device != logits.device for t in (occ_pool, params, u, slots, out_slots)):
+        raise RuntimeError("occ_pool, params, u, slots and out_slots must be on the device of logits")
+    if logits.data_ptr() % 16 or occ_pool.data_ptr() % 16:
+        raise RuntimeError("logits and occ_pool must be 16-byte aligned")
+    tokens = torch.empty(n_seq, device=logits.device, dtype=torch.int32)
+    logprob = torch.empty(n_seq, device=logits.device, dtype=torch.float32) if want_logprob else None
+    _call(_SAMPLE_ENTRY[logits.dtype], "sample slots", logits.device, n_seq, V, ld, *_ptrs(logits, occ_pool), n_slots,
+          *_ptrs(slots, out_slots, params, u, tokens, logprob))
+    return (tokens, logprob) if want_logprob else tokens
+
+
 def gn_gate_forward(y, g, gamma, beta, H, eps):
     """(out, stats): out = GroupNorm_H(y) * g on [rows, C]; stats fp32 [rows, H, 2] = mean, rstd (for gn_gate_backward)."""
     y, g, gamma, beta = _require(y, "y"), _require(g, "g"), _require(gamma, "gamma"), _require(beta, "beta")

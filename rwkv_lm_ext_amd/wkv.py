@@ -504,7 +504,18 @@ class RWKV_6_VARLEN(torch.autograd.Function):
                 raise RuntimeError(f"unsupported dtype {r.dtype}")
             if seg_len != 0 and r.dtype != torch.bfloat16:
                 raise RuntimeError(f"seg_len is a bf16 option, got {r.dtype}")
-            fn(total_T, C, H, state_pool, state_slot, r, k, v, eew, u, y, cu_seqlens, max_seqlen, state_slot_out=state_slot_out,
+            # The workspace is a torch tensor, so that a graph capture owns it: without one the library takes stream-ordered scratch from a
+            # memory pool of its own (csrc/wkv6_api.hip: StreamScratch), which a capture turns into allocation and free nodes inside the
+            # graph -- what include/wkv6_amd.h tells callers that replay graphs not to rely on, and infctx.step_packed is replayed.  (Where
+            # the wrapper is going to refuse the arguments anyway it gets none and says what is wrong.)
+            ws = None
+            if isinstance(cu_seqlens, torch.Tensor) and cu_seqlens.dim() == 1 and cu_seqlens.numel() >= 2 and w.is_cuda:
+                n_seq = cu_seqlens.numel() - 1
+                if seg_len == 0:
+                    ws = wkv6_op.new_rwkv6_varlen_workspace(n_seq, w.device)
+                elif r.dtype == torch.bfloat16 and isinstance(seg_len, int) and seg_len > 0 and seg_len % 64 == 0:
+                    ws = wkv6_op.new_rwkv6_varlen_split_workspace(total_T, n_seq, seg_len, C, H, w.device)
+            fn(total_T, C, H, state_pool, state_slot, r, k, v, eew, u, y, cu_seqlens, max_seqlen, ws=ws, state_slot_out=state_slot_out,
                snap_every=snap_every, cu_snap=cu_snap, snap_slot=snap_slot, **(dict(seg_len=seg_len) if seg_len != 0 else {}))
             return y.view(shape), state_pool
 
