@@ -1,6 +1,6 @@
 // Exact-fp32 token-serial WKV5 (static decay) kernels for gfx950.  Design notes: wkv5_scan.h.
 #include "wkv5_scan.h"
-#include "wkv6_scan.h"                 // launch<>
+#include "wkv6_host.h"                 // launch<>, check_shape, to_rc
 
 namespace wkv6 {
 namespace {
@@ -509,9 +509,7 @@ template <typename T> hipError_t launch_bwd(const Wkv5Args& a, hipStream_t st)
 hipError_t launch_wkv5_fwd(const Wkv5Args& a, bool io_f32, hipStream_t st)
 {
     const dim3 grid(a.B * a.H), block(NT);
-    if (io_f32) hipLaunchKernelGGL((wkv5_fwd_kernel<float>), grid, block, LDS_FWD, st, a);
-    else hipLaunchKernelGGL((wkv5_fwd_kernel<bf16_t>), grid, block, LDS_FWD, st, a);
-    return hipGetLastError();
+    return io_f32 ? launch<wkv5_fwd_kernel<float>>(grid, block, LDS_FWD, st, a) : launch<wkv5_fwd_kernel<bf16_t>>(grid, block, LDS_FWD, st, a);
 }
 
 hipError_t launch_wkv5_bwd(const Wkv5Args& a, bool io_f32, hipStream_t st)
@@ -520,3 +518,50 @@ hipError_t launch_wkv5_bwd(const Wkv5Args& a, bool io_f32, hipStream_t st)
 }
 
 }  // namespace wkv6
+
+using namespace wkv6;
+
+// ---- the entry points (include/wkv6_amd.h).  Exact token-serial kernels only; no workspace
+extern "C" {
+
+int wkv5_forward_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v, const void* w, const void* u,
+                    void* y, unsigned flags, void* stream)
+{
+    if (int rc = check_shape(B, T, C, H)) return rc;
+    if (!r || !k || !v || !w || !u || !y) return WKV6_ENULL;
+    if (flags & ~(unsigned)(WKV6_W_RAW | WKV6_IO_F32 | WKV6_PARTIALS_F32 | WKV6_ALGO_SCAN)) return WKV6_EUNSUPPORTED;
+    Wkv5Args a = {};
+    a.B = B; a.T = T; a.C = C; a.H = H;
+    a.r = r; a.k = k; a.v = v; a.w = w; a.u = u; a.y = y;
+    a.wkind = (flags & WKV6_W_RAW) ? 1 : 0;
+    return to_rc(launch_wkv5_fwd(a, flags & WKV6_IO_F32, (hipStream_t)stream));
+}
+int wkv5_backward_ex(int B, int T, int C, int H, const void* r, const void* k, const void* v, const void* w, const float* ew,
+                     const void* u, const void* gy, void* gr, void* gk, void* gv, void* gw, void* gu, unsigned flags,
+                     void* stream)
+{
+    if (int rc = check_shape(B, T, C, H)) return rc;
+    if (!r || !k || !v || !w || !u || !gy || !gr || !gk || !gv) return WKV6_ENULL;
+    if (!(flags & WKV6_W_RAW) && !ew && gw) return WKV6_ENULL;      // gw = ew (.) d (.) dL/dd needs ew beside the decay
+    if (flags & ~(unsigned)(WKV6_W_RAW | WKV6_IO_F32 | WKV6_PARTIALS_F32 | WKV6_ALGO_SCAN)) return WKV6_EUNSUPPORTED;
+    Wkv5Args a = {};
+    a.B = B; a.T = T; a.C = C; a.H = H;
+    a.r = r; a.k = k; a.v = v; a.w = w; a.ew = ew; a.u = u;
+    a.wkind = (flags & WKV6_W_RAW) ? 1 : 0;
+    a.gy = gy; a.gr = gr; a.gk = gk; a.gv = gv; a.gw = gw; a.gu = gu;
+    a.part_f32 = (flags & WKV6_PARTIALS_F32) ? 1 : 0;
+    return to_rc(launch_wkv5_bwd(a, flags & WKV6_IO_F32, (hipStream_t)stream));
+}
+int wkv5_cuda_forward(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* eew, const void* u,
+                      void* y, void* stream)
+{
+    return wkv5_forward_ex(B, T, C, H, r, k, v, eew, u, y, 0, stream);
+}
+int wkv5_cuda_backward(int B, int T, int C, int H, const void* r, const void* k, const void* v, const float* eew, const float* ew,
+                       const void* u, const void* gy, void* gr, void* gk, void* gv, void* gw, void* gu, void* stream)
+{
+    if (!ew) return WKV6_ENULL;
+    return wkv5_backward_ex(B, T, C, H, r, k, v, eew, ew, u, gy, gr, gk, gv, gw, gu, 0, stream);
+}
+
+}  // extern "C"

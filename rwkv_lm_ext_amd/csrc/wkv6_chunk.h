@@ -1,6 +1,6 @@
 // Shared definitions of the chunked MFMA kernels (wkv6_chunk.hip, wkv6_chunk_bwd.hip).
 #pragma once
-#include "wkv6_scan.h"
+#include "wkv6_host.h"                 // want_split, bi_slots, clock_claim
 
 // Diagnostic build (-DWKV6_STAMP, tools/ablate.sh): waves accumulate s_memtime cycles per phase into the buffer set through
 // wkv6_set_debug_buffer() -- and, in the backward, the cycles inside each tag group's polls; no stamp executes in the normal build.

@@ -17,8 +17,7 @@
 // literal zero, and only the lanes of the group's rows keep (select by lane) what the pass computed.  Nothing is masked by a multiply:
 // a NaN in adapter a's matrices stays in the discarded columns of a's pass.
 #include <climits>
-#include "wkv6_scan.h"                 // launch<>
-#include "../../include/wkv6_amd.h"
+#include "wkv6_host.h"                 // launch<>, to_rc
 
 namespace wkv6 {
 namespace {
@@ -268,7 +267,7 @@ int wkv6_lora_packed_bf16(long total_T, int n_seq, int K, int N, int R, int n_ad
     a.x = (const bf16_t*)x; a.A = (const bf16_t*)A_pool; a.B = (const bf16_t*)B_pool; a.scale = scale;
     a.y = (bf16_t*)y; a.xa = (bf16_t*)workspace;
     const hipError_t e = launch_lora_packed(a, (hipStream_t)stream);
-    return e == hipSuccess ? WKV6_OK : (int)e;
+    return to_rc(e);
 }
 
 }  // extern "C"

@@ -18,8 +18,7 @@
 //
 // Layout: rows of C bf16 channels; a thread owns 4 consecutive channels (8-byte accesses, a 64-channel head = 16 lanes =
 // one DPP row, so the GroupNorm statistics are DPP row reductions); one workgroup of C/4 threads per row.
-#include "wkv6_common.h"
-#include "../../include/wkv6_amd.h"
+#include "wkv6_host.h"                 // to_rc
 
 namespace wkv6 {
 namespace {
@@ -560,7 +559,7 @@ template <typename K> int launch_flat(K kernel, const FlatArgs& a, hipStream_t s
     const long blocks = (a.n8 + 255) / 256;
     hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, a);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WKV6_OK : (int)e;
+    return to_rc(e);
 }
 
 int check_rows(long rows, int C)
@@ -594,7 +593,7 @@ int dispatch_lerp(const LerpArgs& a, bool bwd, hipStream_t st)
     else if (a.NS == 2 && !a.m) launch_lerp<2, false>(a, bwd, st);
     else return WKV6_EUNSUPPORTED;
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WKV6_OK : (int)e;
+    return to_rc(e);
 }
 
 int dispatch_slot_lerp(const SlotLerpArgs& a, hipStream_t st)
@@ -606,7 +605,7 @@ int dispatch_slot_lerp(const SlotLerpArgs& a, hipStream_t st)
     else if (a.NS == 2 && !a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<2, false>), grid, block, 0, st, a);
     else return WKV6_EUNSUPPORTED;
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WKV6_OK : (int)e;
+    return to_rc(e);
 }
 
 bool overlap(const void* p, size_t pn, const void* q, size_t qn)
@@ -729,7 +728,7 @@ int wkv6_shift_keep(long total_T, int n_seq, int max_seqlen, int C, const int* c
     a.cu_snap = cu_snap; a.snap_slot = snap_slot;
     hipLaunchKernelGGL(shift_keep_kernel, dim3((unsigned)grid), dim3(C / 4), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WKV6_OK : (int)e;
+    return to_rc(e);
 }
 
 // rev_n == null: the plain packed shift
@@ -810,7 +809,7 @@ int wkv6_gn_gate_forward(long rows, int C, int H, const void* y, const void* g, 
     a.out = (bf16_t*)out; a.stats = stats;
     hipLaunchKernelGGL(gn_gate_fwd_kernel, dim3((unsigned)rows), dim3(C / 4), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WKV6_OK : (int)e;
+    return to_rc(e);
 }
 
 int wkv6_gn_gate_backward(long rows, int C, int H, const void* y, const void* g, const void* gamma, const void* beta,
@@ -827,7 +826,7 @@ int wkv6_gn_gate_backward(long rows, int C, int H, const void* y, const void* g,
     a.dgamma_part = dgamma_part; a.dbeta_part = dbeta_part; a.nparts = nparts;
     hipLaunchKernelGGL(gn_gate_bwd_kernel, dim3(nparts), dim3(C / 4), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WKV6_OK : (int)e;
+    return to_rc(e);
 }
 
 }  // extern "C"

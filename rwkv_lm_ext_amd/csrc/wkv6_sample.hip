@@ -18,6 +18,7 @@
 // 2^46 stay below 2^63.  The quantisation is 2^-46 of the largest weight per term.
 #include <cmath>
 #include "wkv6_sample.h"
+#include "wkv6_host.h"                 // to_rc
 
 // the same expression must give the same bits wherever it is inlined (weights are formed once for W and once more for the draw)
 #pragma clang fp contract(off)
@@ -454,3 +455,44 @@ hipError_t launch_sample_slots(const SampleArgs& a, int io, hipStream_t st)
 }
 
 }  // namespace wkv6
+
+using namespace wkv6;
+
+extern "C" {
+
+// ---- the entry points (include/wkv6_amd.h); the order of the refusals is part of the contract
+static int sample_slots(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot, const int* slot_out,
+                        const float* params, const float* u, int* tokens, float* logprob, int io, void* stream)
+{
+    if (n_seq < 1 || V < 1 || n_slots < 1 || ld < V || ld % 8) return WKV6_EINVAL;
+    if (!slot && n_slots < n_seq) return WKV6_EINVAL;
+    if (((uintptr_t)logits | (uintptr_t)occ_pool) & 15) return WKV6_EINVAL;
+    if (((uintptr_t)slot | (uintptr_t)slot_out | (uintptr_t)params | (uintptr_t)u | (uintptr_t)tokens | (uintptr_t)logprob) & 3) return WKV6_EINVAL;
+    const uintptr_t lo = (uintptr_t)logits, oc = (uintptr_t)occ_pool;
+    const size_t lo_bytes = (size_t)n_seq * ld * (io == IO_F32 ? 4 : 2), oc_bytes = (size_t)n_slots * ld * 4;
+    if (logits && occ_pool && lo < oc + oc_bytes && oc < lo + lo_bytes) return WKV6_EINVAL;
+    if (V > SAMPLE_MAX_V) return WKV6_EUNSUPPORTED;
+    if (!logits || !occ_pool || !params || !u || !tokens) return WKV6_ENULL;
+    SampleArgs a = {};
+    a.n_seq = n_seq; a.V = V; a.ld = ld; a.n_slots = n_slots;
+    a.logits = logits; a.occ = occ_pool; a.slot = slot; a.slot_out = slot_out; a.params = params; a.u = u;
+    a.tokens = tokens; a.logprob = logprob;
+    return to_rc(launch_sample_slots(a, io, (hipStream_t)stream));
+}
+int rwkv6_sample_slots_bf16(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot, const int* slot_out,
+                            const float* params, const float* u, int* tokens, float* logprob, void* stream)
+{
+    return sample_slots(n_seq, V, ld, logits, occ_pool, n_slots, slot, slot_out, params, u, tokens, logprob, IO_BF16, stream);
+}
+int rwkv6_sample_slots_fp16(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot, const int* slot_out,
+                            const float* params, const float* u, int* tokens, float* logprob, void* stream)
+{
+    return sample_slots(n_seq, V, ld, logits, occ_pool, n_slots, slot, slot_out, params, u, tokens, logprob, IO_F16, stream);
+}
+int rwkv6_sample_slots_fp32(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot, const int* slot_out,
+                            const float* params, const float* u, int* tokens, float* logprob, void* stream)
+{
+    return sample_slots(n_seq, V, ld, logits, occ_pool, n_slots, slot, slot_out, params, u, tokens, logprob, IO_F32, stream);
+}
+
+}  // extern "C"

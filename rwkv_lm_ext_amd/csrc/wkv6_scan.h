@@ -97,7 +97,7 @@ struct ScanArgs {
     float gn_eps;
     void* gn_out;                     // [B,T,C]  GroupNorm_H(y) * gate  (y itself is stored too unless y == null)
     float* gn_stats;                  // [B*T, H, 2] mean, rstd of every (token, head) for the backward, or null
-    const float* g_in;                // backward as a two-level scan over T (wkv6_api.hip: chunk_backward): fp32 [B,H,N(j),N(i)] adjoint state
+    const float* g_in;                // backward as a two-level scan over T (wkv6_tsplit.hip: chunk_backward): fp32 [B,H,N(j),N(i)] adjoint state
                                       // entering this row (= segment) from the future, or null (zero)
     const float* rc_in;               // ... and fp32 [B,C]: the gw suffix sum at the segment's end, sum_{s >= end} (a_s - b_s) =
                                       // Phi[i] = sum_j G[i][j] S[i][j] at the boundary, or null (zero)
@@ -268,7 +268,6 @@ hipError_t launch_chunk_bwd(const ScanArgs& a, hipStream_t st);
 // the launch does not apply (two workgroups per pair) -- the caller then runs the halves as two launches
 hipError_t launch_chunk_fwd_bi(const ScanArgs& a1, const ScanArgs& a2, int* slots, hipStream_t st);
 hipError_t launch_chunk_bwd_bi(const ScanArgs& a1, const ScanArgs& a2, int* slots, hipStream_t st);
-int bi_slots(int BH);                        // workgroup slots such a launch uses (0: does not apply)
 hipError_t launch_chunk_bwd12k(const ScanArgs& a, hipStream_t st);    // reverse pass over 64-token row-order checkpoints, a.split as given (wkv6_chunk_bwd12k.hip)
 size_t chunk_ckpt_floats(int B, int T, int H);
 // packed variable-length rows (ScanArgs: tok_off, ck_off, ck_stride), one workgroup per (sequence, head); bf16 I/O; a.rev_n ([B], indexed
@@ -298,10 +297,6 @@ hipError_t launch_chunk_fwd_snap(const ScanArgs& a, hipStream_t st);
 // ... over the item table of a split call (SegArgs): the state pass of the items that have a successor, or the forward per item
 hipError_t launch_chunk_fwd_seg(const ScanArgs& a, const SegArgs& sg, bool state_only, hipStream_t st);
 hipError_t launch_chunk_state_pass(const ScanArgs& a, hipStream_t st);   // state recurrence only (s_out, ckpt, dsum)
-// In-run clock probe (wkv6_set_clock_ring, wkv6_api.hip): where launch number n of kind (0: chunked forward, 1: chunked backward) stamps,
-// or null; takes the launch's place in the ring (host side, one atomic increment per launch)
-unsigned long long* clock_claim(int kind, int* slots);
-int cu_count();
-int want_split(int BH);                      // two workgroups per (batch, head)?  (launch-shape policy: wkv6_api.hip)
+// (what the launchers ask of the host layer -- cu_count, want_split, bi_slots, clock_claim -- is declared in wkv6_host.h)
 
 }  // namespace wkv6

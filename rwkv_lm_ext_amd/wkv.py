@@ -505,7 +505,7 @@ class RWKV_6_VARLEN(torch.autograd.Function):
             if seg_len != 0 and r.dtype != torch.bfloat16:
                 raise RuntimeError(f"seg_len is a bf16 option, got {r.dtype}")
             # The workspace is a torch tensor, so that a graph capture owns it: without one the library takes stream-ordered scratch from a
-            # memory pool of its own (csrc/wkv6_api.hip: StreamScratch), which a capture turns into allocation and free nodes inside the
+            # memory pool of its own (csrc/wkv6_state.hip: StreamScratch), which a capture turns into allocation and free nodes inside the
             # graph -- what include/wkv6_amd.h tells callers that replay graphs not to rely on, and infctx.step_packed is replayed.  (Where
             # the wrapper is going to refuse the arguments anyway it gets none and says what is wrong.)
             ws = None

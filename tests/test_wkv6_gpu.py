@@ -311,7 +311,7 @@ def test_two_workgroups_per_head_is_the_same_arithmetic(ops):
 @pytest.mark.parametrize("segments", [2, 4, 8])
 def test_two_level_scan_forward_for_few_long_sequences(ops, oracle, segments):
     """Forward-only calls on few long sequences are cut into segments that run as extra workgroups (state pass per segment, a
-    chaining kernel, then the ordinary forward from each segment's entry state; wkv6_api.hip: chunk_forward).  dispatch(tsplit=) forces
+    chaining kernel, then the ordinary forward from each segment's entry state; wkv6_tsplit.hip: chunk_forward).  dispatch(tsplit=) forces
     the segment count: y and the final state against the oracle (bf16 contract) and against the one-pass kernel (1 ulp)."""
     bf = torch.bfloat16
     B, T, H = 1, 1024, 2
@@ -357,7 +357,7 @@ def test_two_level_scan_forward_for_few_long_sequences(ops, oracle, segments):
 
 @pytest.mark.parametrize("segments", [2, 4, 8])
 def test_two_level_scan_backward_for_few_long_sequences(ops, oracle, segments):
-    """The backward of few long sequences as a two-level scan over T (wkv6_api.hip: chunk_backward): every segment runs as its own
+    """The backward of few long sequences as a two-level scan over T (wkv6_tsplit.hip: chunk_backward): every segment runs as its own
     workgroup from the adjoint state entering it from the future (reversed state-only pass with k := r, v := gy, chained last to
     first) and from the gw suffix sum beyond its end (Phi = sum_j G S at the boundary); gu sums over the segments, gs is the adjoint
     state at the sequence start.  dispatch(tsplit=) forces the segment count: every gradient against the oracle (bf16 contract, fp32

@@ -5,11 +5,14 @@ set -e
 OUT=$1; shift
 mkdir -p "$OUT"
 SRC=rwkv_lm_ext_amd/csrc
+# the sources and the base flags are the build's own (rwkv_lm_ext_amd/_build.py), without its warning switches
+BASE=$(python -c 'from rwkv_lm_ext_amd import _build as b; print(*[f for f in b.HIPCC_FLAGS if not f.startswith("-W")])')
+SRCS=$(python -c 'from rwkv_lm_ext_amd import _build as b; print(*[s[:-4] for s in b.SOURCES])')
 for spec in "$@"; do
     name=${spec%%:*}; flags=${spec#*:}
     d="$OUT/$name"; mkdir -p "$d"
-    for f in wkv6_scan wkv6_chunk wkv6_chunk_bwd12k wkv6_mix wkv6_api; do
-        hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-strict-aliasing $flags -c $SRC/$f.hip -o "$d/$f.o" &
+    for f in $SRCS; do
+        hipcc $BASE $flags -c $SRC/$f.hip -o "$d/$f.o" &
     done
     wait
     hipcc --offload-arch=gfx950 -shared -fPIC -o "$d/lib.so" "$d"/*.o
