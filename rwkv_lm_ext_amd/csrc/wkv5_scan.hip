@@ -13,63 +13,13 @@ constexpr int CPT = TB * ROW / NT;     // channels staged per thread (2)
 constexpr int TPT = ROW / CPT;         // threads per token (32)
 static_assert(CPT == 2 && TPT == 32, "staging geometry");
 
-// ---- 2-wide channel I/O in the operator's I/O type, 1-wide parameter loads --------------------------
-template <typename T> struct io2;
-template <> struct io2<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float (&o)[2])
-    {
-        const uint32_t raw = *reinterpret_cast<const uint32_t*>(p);
-        o[0] = bf_lo(raw); o[1] = bf_hi(raw);
-    }
-    static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[2])
-    {
-        *reinterpret_cast<uint32_t*>(p) = pack_bf2(v[0], v[1]);
-    }
-    static __device__ __forceinline__ float load1(const bf16_t* p) { return bf_lo((uint32_t)*p); }
-};
-template <> struct io2<float> {
-    static __device__ __forceinline__ void load(const float* p, float (&o)[2])
-    {
-        const float2 raw = *reinterpret_cast<const float2*>(p);
-        o[0] = raw.x; o[1] = raw.y;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[2])
-    {
-        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-    }
-    static __device__ __forceinline__ float load1(const float* p) { return *p; }
-};
-__device__ __forceinline__ void lds_store2(float* p, const float (&v)[2]) { *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]); }
-__device__ __forceinline__ void lds_load2(const float* p, float (&v)[2])
-{
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x; v[1] = t.y;
-}
-__device__ __forceinline__ void lds_load4(const float* p, float (&v)[4])
-{
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-// sum over the 32 consecutive lanes that stage one token
-__device__ __forceinline__ float token_sum(float x)
-{
-    x = row_sum16(x);
-    return x + __shfl_xor(x, 16);
-}
-// one partial in the [B,C] gradient's element type
-template <typename T> __device__ __forceinline__ void store_partial(void* p, long o, float s, int part_f32)
-{
-    if (sizeof(T) == 4 || part_f32) reinterpret_cast<float*>(p)[o] = s;
-    else reinterpret_cast<bf16_t*>(p)[o] = (bf16_t)(pack_bf2(s, 0.f) & 0xffffu);
-}
-
 // decay d and ew = -exp(w) of channel hc: once per lane, in front of the token loops.  Formed in fp64 and rounded once: a
 // relative error e of d becomes t e on a contribution t tokens back, and slow channels (w = -6: d = 0.9975) remember hundreds
 // of tokens, so the fast exp's few ulps would show in fp32 I/O; at once per lane the fp64 routine costs nothing.
 template <typename T> __device__ __forceinline__ void load_decay(const Wkv5Args& a, int hc, float& d, float& ew)
 {
     if (a.wkind == 1) {
-        const double e = exp((double)io2<T>::load1(reinterpret_cast<const T*>(a.w) + hc));
+        const double e = exp((double)ion<T, CPT>::load1(reinterpret_cast<const T*>(a.w) + hc));
         ew = -(float)e;
         d = (float)exp(-e);
     } else {
@@ -104,7 +54,7 @@ __global__ __launch_bounds__(NT) void wkv5_fwd_kernel(const Wkv5Args a)
     // staging role
     const int spp = tid / TPT, sc0 = (tid % TPT) * CPT;
     float uu[CPT];
-    io2<T>::load(reinterpret_cast<const T*>(a.u) + h * HEAD + sc0, uu);
+    ion<T, CPT>::load(reinterpret_cast<const T*>(a.u) + h * HEAD + sc0, uu);
 
     // compute role
     const int jb = lane >> 4, ib = lane & 15;
@@ -125,9 +75,9 @@ __global__ __launch_bounds__(NT) void wkv5_fwd_kernel(const Wkv5Args a)
 #pragma unroll
         for (int c = 0; c < CPT; ++c) { pr[c] = 0.f; pk[c] = 0.f; pv[c] = 0.f; }
         if (p < ntok) {
-            io2<T>::load(gr_ + idx, pr);
-            io2<T>::load(gk_ + idx, pk);
-            io2<T>::load(gv_ + idx, pv);
+            ion<T, CPT>::load(gr_ + idx, pr);
+            ion<T, CPT>::load(gk_ + idx, pk);
+            ion<T, CPT>::load(gv_ + idx, pv);
         }
     };
     auto write_lds = [&](int buf) {
@@ -135,10 +85,10 @@ __global__ __launch_bounds__(NT) void wkv5_fwd_kernel(const Wkv5Args a)
         float part = 0.f;
 #pragma unroll
         for (int c = 0; c < CPT; ++c) part = fmaf(pr[c] * uu[c], pk[c], part);
-        lds_store2(ib_, pr);
-        lds_store2(ib_ + TB * ROW, pk);
-        lds_store2(ib_ + 2 * TB * ROW, pv);
-        part = token_sum(part);
+        lds_store<CPT>(ib_, pr);
+        lds_store<CPT>(ib_ + TB * ROW, pk);
+        lds_store<CPT>(ib_ + 2 * TB * ROW, pv);
+        part = token_sum<TPT>(part);
         if ((tid % TPT) == 0) coef[buf * TB + spp] = part;
     };
 
@@ -158,9 +108,9 @@ __global__ __launch_bounds__(NT) void wkv5_fwd_kernel(const Wkv5Args a)
 
             for (int pp = 0; pp < nb; ++pp) {
                 float r4[4], k4[4], vv[JR], yacc[JR];
-                lds_load4(rs + pp * ROW + i0, r4);
-                lds_load4(ks + pp * ROW + i0, k4);
-                lds_load2(vs + pp * ROW + j0, vv);
+                lds_load<4>(rs + pp * ROW + i0, r4);
+                lds_load<4>(ks + pp * ROW + i0, k4);
+                lds_load<2>(vs + pp * ROW + j0, vv);
 #pragma unroll
                 for (int jj = 0; jj < JR; ++jj) yacc[jj] = 0.f;
 #pragma unroll
@@ -184,8 +134,8 @@ __global__ __launch_bounds__(NT) void wkv5_fwd_kernel(const Wkv5Args a)
             const int p = q * TB + spp;
             if (p < ntok) {
                 float o[CPT];
-                lds_load2(ys + buf * TB * ROW + spp * ROW + sc0, o);
-                io2<T>::store(gy_ + base + (long)p * a.C + sc0, o);
+                lds_load<2>(ys + buf * TB * ROW + spp * ROW + sc0, o);
+                ion<T, CPT>::store(gy_ + base + (long)p * a.C + sc0, o);
             }
         }
     }
@@ -216,7 +166,7 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_a_kernel(const Wkv5Args a)
 
     const int spp = tid / TPT, sc0 = (tid % TPT) * CPT;
     float uu[CPT];
-    io2<T>::load(reinterpret_cast<const T*>(a.u) + h * HEAD + sc0, uu);
+    ion<T, CPT>::load(reinterpret_cast<const T*>(a.u) + h * HEAD + sc0, uu);
 
     const int irow = lane >> 4, jl = lane & 15;
     const int i0 = wv * IPW + irow * IR, j0 = jl * 4;
@@ -243,10 +193,10 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_a_kernel(const Wkv5Args a)
 #pragma unroll
         for (int c = 0; c < CPT; ++c) { pr[c] = 0.f; pk[c] = 0.f; pv[c] = 0.f; pgy[c] = 0.f; }
         if (p < ntok) {
-            io2<T>::load(gr_ + idx, pr);
-            io2<T>::load(gk_ + idx, pk);
-            io2<T>::load(gv_ + idx, pv);
-            io2<T>::load(ggy + idx, pgy);
+            ion<T, CPT>::load(gr_ + idx, pr);
+            ion<T, CPT>::load(gk_ + idx, pk);
+            ion<T, CPT>::load(gv_ + idx, pv);
+            ion<T, CPT>::load(ggy + idx, pgy);
         }
     };
     auto write_lds = [&](int buf) {
@@ -254,11 +204,11 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_a_kernel(const Wkv5Args a)
         float part = 0.f;
 #pragma unroll
         for (int c = 0; c < CPT; ++c) part = fmaf(pv[c], pgy[c], part);
-        lds_store2(ib_, pr);
-        lds_store2(ib_ + TB * ROW, pk);
-        lds_store2(ib_ + 2 * TB * ROW, pv);
-        lds_store2(ib_ + 3 * TB * ROW, pgy);
-        nvg = token_sum(part);
+        lds_store<CPT>(ib_, pr);
+        lds_store<CPT>(ib_ + TB * ROW, pk);
+        lds_store<CPT>(ib_ + 2 * TB * ROW, pv);
+        lds_store<CPT>(ib_ + 3 * TB * ROW, pgy);
+        nvg = token_sum<TPT>(part);
 #pragma unroll
         for (int c = 0; c < CPT; ++c) {
             nk[c] = pk[c];
@@ -286,10 +236,10 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_a_kernel(const Wkv5Args a)
 
             for (int pp = 0; pp < nb; ++pp) {
                 float rr[IR], kk[IR], v4[4], g4[4], dq[IR];
-                lds_load2(rs + pp * ROW + i0, rr);
-                lds_load2(ks + pp * ROW + i0, kk);
-                lds_load4(vs + pp * ROW + j0, v4);
-                lds_load4(gs + pp * ROW + j0, g4);
+                lds_load<2>(rs + pp * ROW + i0, rr);
+                lds_load<2>(ks + pp * ROW + i0, kk);
+                lds_load<4>(vs + pp * ROW + j0, v4);
+                lds_load<4>(gs + pp * ROW + j0, g4);
 #pragma unroll
                 for (int ii = 0; ii < IR; ++ii) {
                     float dD = 0.f;
@@ -313,16 +263,16 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_a_kernel(const Wkv5Args a)
             const int p = q * TB + spp;
             if (p < ntok) {
                 float dq[CPT], o[CPT];
-                lds_load2(dqs + buf * TB * ROW + spp * ROW + sc0, dq);
+                lds_load<2>(dqs + buf * TB * ROW + spp * ROW + sc0, dq);
 #pragma unroll
                 for (int c = 0; c < CPT; ++c) o[c] = fmaf(uu[c] * ck[c], cvg, dq[c]);
-                io2<T>::store(ogr + base + (long)p * a.C + sc0, o);
+                ion<T, CPT>::store(ogr + base + (long)p * a.C + sc0, o);
             }
         }
     }
     // per-batch partials: gu from the staging threads' accumulators (summed over the TB token slots), gd from the 16 lanes of each key row
     __syncthreads();
-    lds_store2(dqs + spp * ROW + sc0, gu_acc);
+    lds_store<CPT>(dqs + spp * ROW + sc0, gu_acc);
 #pragma unroll
     for (int ii = 0; ii < IR; ++ii) {
         const float s = row_sum16(gd[ii]);
@@ -335,12 +285,12 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_a_kernel(const Wkv5Args a)
             float s = 0.f;
 #pragma unroll
             for (int pp = 0; pp < TB; ++pp) s += dqs[pp * ROW + tid];
-            store_partial<T>(a.gu, o, s, a.part_f32);
+            store_partial(a.gu, sizeof(T) == 4 || a.part_f32, o, s);
         }
         if (a.gw) {
             float d, ew;
             load_decay<T>(a, h * HEAD + tid, d, ew);
-            store_partial<T>(a.gw, o, ew * d * dqs[TB * ROW + tid], a.part_f32);
+            store_partial(a.gw, sizeof(T) == 4 || a.part_f32, o, ew * d * dqs[TB * ROW + tid]);
         }
     }
 }
@@ -371,7 +321,7 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_g_kernel(const Wkv5Args a)
 
     const int spp = tid / TPT, sc0 = (tid % TPT) * CPT;
     float uu[CPT];
-    io2<T>::load(reinterpret_cast<const T*>(a.u) + h * HEAD + sc0, uu);
+    ion<T, CPT>::load(reinterpret_cast<const T*>(a.u) + h * HEAD + sc0, uu);
 
     const int irow = lane >> 4, jl = lane & 15;
     const int i0 = wv * IPW + irow * IR, j0 = jl * 4;
@@ -396,10 +346,10 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_g_kernel(const Wkv5Args a)
 #pragma unroll
         for (int c = 0; c < CPT; ++c) { pr[c] = 0.f; pk[c] = 0.f; pv[c] = 0.f; pgy[c] = 0.f; }
         if (p < ntok) {
-            io2<T>::load(gr_ + idx, pr);
-            io2<T>::load(gk_ + idx, pk);
-            io2<T>::load(gv_ + idx, pv);
-            io2<T>::load(ggy + idx, pgy);
+            ion<T, CPT>::load(gr_ + idx, pr);
+            ion<T, CPT>::load(gk_ + idx, pk);
+            ion<T, CPT>::load(gv_ + idx, pv);
+            ion<T, CPT>::load(ggy + idx, pgy);
         }
     };
     auto write_lds = [&](int buf) {
@@ -410,12 +360,12 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_g_kernel(const Wkv5Args a)
             p1 = fmaf(pr[c] * uu[c], pk[c], p1);
             p2 = fmaf(pv[c], pgy[c], p2);
         }
-        lds_store2(ib_, pr);
-        lds_store2(ib_ + TB * ROW, pk);
-        lds_store2(ib_ + 2 * TB * ROW, pv);
-        lds_store2(ib_ + 3 * TB * ROW, pgy);
-        ncoef = token_sum(p1);
-        nvg = token_sum(p2);
+        lds_store<CPT>(ib_, pr);
+        lds_store<CPT>(ib_ + TB * ROW, pk);
+        lds_store<CPT>(ib_ + 2 * TB * ROW, pv);
+        lds_store<CPT>(ib_ + 3 * TB * ROW, pgy);
+        ncoef = token_sum<TPT>(p1);
+        nvg = token_sum<TPT>(p2);
 #pragma unroll
         for (int c = 0; c < CPT; ++c) { nr[c] = pr[c]; ngy[c] = pgy[c]; }
     };
@@ -440,10 +390,10 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_g_kernel(const Wkv5Args a)
             const int nb = min(TB, ntok - q * TB);
             for (int pp = nb - 1; pp >= 0; --pp) {
                 float rr[IR], kk[IR], v4[4], g4[4], gkp[IR], gvp[4];
-                lds_load2(rs + pp * ROW + i0, rr);
-                lds_load2(ks + pp * ROW + i0, kk);
-                lds_load4(vs + pp * ROW + j0, v4);
-                lds_load4(gs + pp * ROW + j0, g4);
+                lds_load<2>(rs + pp * ROW + i0, rr);
+                lds_load<2>(ks + pp * ROW + i0, kk);
+                lds_load<4>(vs + pp * ROW + j0, v4);
+                lds_load<4>(gs + pp * ROW + j0, g4);
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) gvp[jj] = 0.f;
 #pragma unroll
@@ -468,13 +418,13 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_g_kernel(const Wkv5Args a)
             const int p = q * TB + spp;
             if (p < ntok) {
                 float dk[CPT], gvsum[CPT], ogk_[CPT], ogv_[CPT];
-                lds_load2(dks + buf * TB * ROW + spp * ROW + sc0, dk);
+                lds_load<2>(dks + buf * TB * ROW + spp * ROW + sc0, dk);
 #pragma unroll
                 for (int c = 0; c < CPT; ++c) gvsum[c] = 0.f;
 #pragma unroll
                 for (int w_ = 0; w_ < NW; ++w_) {      // fixed order over the waves' partial sums
                     float t2[CPT];
-                    lds_load2(gvs + (buf * NW + w_) * TB * ROW + spp * ROW + sc0, t2);
+                    lds_load<2>(gvs + (buf * NW + w_) * TB * ROW + spp * ROW + sc0, t2);
 #pragma unroll
                     for (int c = 0; c < CPT; ++c) gvsum[c] += t2[c];
                 }
@@ -484,8 +434,8 @@ __global__ __launch_bounds__(NT) void wkv5_bwd_g_kernel(const Wkv5Args a)
                     ogv_[c] = fmaf(ccoef, cgy[c], gvsum[c]);
                 }
                 const long idx = base + (long)p * a.C + sc0;
-                io2<T>::store(ogk + idx, ogk_);
-                io2<T>::store(ogv + idx, ogv_);
+                ion<T, CPT>::store(ogk + idx, ogk_);
+                ion<T, CPT>::store(ogv + idx, ogv_);
             }
         }
     }

@@ -97,6 +97,89 @@ template <> struct io4<float> {
     }
 };
 
+// ---- CPT-wide channel I/O of the exact-scan kernels (CPT = 2 or 4), load1: one parameter element ------
+template <typename T, int CPT> struct ion;
+template <typename T> struct ion<T, 4> : io4<T> {};
+template <> struct ion<bf16_t, 2> {
+    static __device__ __forceinline__ void load(const bf16_t* p, float (&o)[2])
+    {
+        const uint32_t raw = *reinterpret_cast<const uint32_t*>(p);
+        o[0] = bf_lo(raw); o[1] = bf_hi(raw);
+    }
+    static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[2])
+    {
+        *reinterpret_cast<uint32_t*>(p) = pack_bf2(v[0], v[1]);
+    }
+    static __device__ __forceinline__ float load1(const bf16_t* p) { return bf_lo((uint32_t)*p); }
+};
+template <> struct ion<f16_t, 2> {
+    typedef f16_t h2 __attribute__((ext_vector_type(2)));
+    static __device__ __forceinline__ void load(const f16_t* p, float (&o)[2])
+    {
+        const h2 raw = *reinterpret_cast<const h2*>(p);
+        o[0] = (float)raw[0]; o[1] = (float)raw[1];
+    }
+    static __device__ __forceinline__ void store(f16_t* p, const float (&v)[2])
+    {
+        const h2 raw = {(f16_t)v[0], (f16_t)v[1]};
+        *reinterpret_cast<h2*>(p) = raw;
+    }
+};
+template <> struct ion<float, 2> {
+    static __device__ __forceinline__ void load(const float* p, float (&o)[2])
+    {
+        const float2 raw = *reinterpret_cast<const float2*>(p);
+        o[0] = raw.x; o[1] = raw.y;
+    }
+    static __device__ __forceinline__ void store(float* p, const float (&v)[2])
+    {
+        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+    }
+    static __device__ __forceinline__ float load1(const float* p) { return *p; }
+};
+// the same widths as plain fp32 vectors (LDS images; fp32 global scratch)
+template <int CPT> __device__ __forceinline__ void lds_store(float* p, const float (&v)[CPT])
+{
+    if constexpr (CPT == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+}
+template <int CPT> __device__ __forceinline__ void lds_load(const float* p, float (&v)[CPT])
+{
+    if constexpr (CPT == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        const float2 t = *reinterpret_cast<const float2*>(p);
+        v[0] = t.x; v[1] = t.y;
+    }
+}
+// element o of a partial result (s_out, gs, gu, gw): fp32, or rounded to bf16
+__device__ __forceinline__ void store_partial(void* out, int f32, long o, float x)
+{
+    if (f32) reinterpret_cast<float*>(out)[o] = x;
+    else reinterpret_cast<bf16_t*>(out)[o] = (bf16_t)(pack_bf2(x, 0.f) & 0xffffu);
+}
+
+// ---- packed batches: the sequence that holds row r = the last s < n_seq with key(cu[s]) <= r (-1: none), by bisection in cu_seqlens --
+// workgroup-uniform scalar loads of a few cached words, no per-token flag array: 0 bytes per token beyond a dense kernel's traffic.
+// Row r opens its sequence when cu[s] == r (empty sequences in front of it share that boundary: the last index wins, which is the
+// sequence that holds the row).  key: what a boundary counts as (the plain form: itself; shift_keep_kernel clamps it).
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+template <typename Key> __device__ __forceinline__ int seq_of_row(const int* __restrict__ cu, int n_seq, long r, Key key)
+{
+    int lo = 0, hi = n_seq;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long)key(cu[mid]) <= r) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo - 1;
+}
+__device__ __forceinline__ int seq_of_row(const int* __restrict__ cu, int n_seq, long r)
+{
+    return seq_of_row(cu, n_seq, r, [](int v) { return v; });
+}
+
 // ---- cross-lane helpers ---------------------------------------------------------------------------
 template <int CTRL> __device__ __forceinline__ float dpp_mov(float x)
 {
@@ -115,6 +198,13 @@ __device__ __forceinline__ float row_sum16(float x)
     x += dpp_mov<DPP_XOR2>(x);
     x += dpp_mov<DPP_ROR4>(x);
     x += dpp_mov<DPP_ROR8>(x);
+    return x;
+}
+// sum over the TPT consecutive lanes that stage one token in the exact-scan kernels (TPT = 16 or 32)
+template <int TPT> __device__ __forceinline__ float token_sum(float x)
+{
+    x = row_sum16(x);
+    if constexpr (TPT == 32) x += __shfl_xor(x, 16);
     return x;
 }
 // Transposing row reductions: NV values per lane are summed over the 16 lanes of the row; on

@@ -55,22 +55,9 @@ inline bool lora_sizes_ok(const LoraArgs& a)
            (a.R == 8 || a.R == 16 || a.R == 32 || a.R == 64);
 }
 
-// the last s < n_seq with cu[s] <= r, -1: none (seq_of_row of wkv6_mix.hip)
-__device__ __forceinline__ int seq_of_row(const int* __restrict__ cu, int n_seq, long r)
-{
-    int lo = 0, hi = n_seq;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((long)cu[mid] <= r) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo - 1;
-}
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // Adapter of packed row `row`, -1: the row is not served (outside [0,total_T), in no sequence, or its sequence's adapter lies outside the
-// pool).  Row t belongs to sequence s = seq_of_row(t) when a_s <= t < b_s with the bounds clamped into [0,total_T]; the adapter number is
-// judged here, before any address is formed from it.
+// pool).  Row t belongs to sequence s = seq_of_row(t) (wkv6_common.h) when a_s <= t < b_s with the bounds clamped into [0,total_T]; the
+// adapter number is judged here, before any address is formed from it.
 __device__ __forceinline__ int row_adapter(const LoraArgs& a, long row)
 {
     if (row >= a.total_T) return -1;

@@ -18,7 +18,8 @@
 //
 // Layout: rows of C bf16 channels; a thread owns 4 consecutive channels (8-byte accesses, a 64-channel head = 16 lanes =
 // one DPP row, so the GroupNorm statistics are DPP row reductions); one workgroup of C/4 threads per row.
-#include "wkv6_host.h"                 // to_rc
+#include <type_traits>
+#include "wkv6_host.h"                 // launch<>, to_rc
 
 namespace wkv6 {
 namespace {
@@ -49,20 +50,7 @@ struct SlotLerpArgs : LerpArgs {
     int n_slots;
 };
 
-// Packed batches: the sequence that holds row r = the last s with cu[s] <= r (-1: none), by bisection in cu_seqlens -- workgroup-uniform
-// scalar loads of a few cached words, no per-token flag array: 0 bytes per token beyond the dense kernel's traffic.  Row r opens its
-// sequence when cu[s] == r (empty sequences in front of it share that boundary: the last index wins, which is the sequence that holds the row).
-__device__ __forceinline__ int seq_of_row(const int* __restrict__ cu, int n_seq, long r)
-{
-    int lo = 0, hi = n_seq;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if ((long)cu[mid] <= r) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo - 1;
-}
-
+// (packed batches: the sequence that holds a row is seq_of_row of wkv6_common.h)
 __device__ __forceinline__ void ld4(const bf16_t* p, float (&o)[4]) { io4<bf16_t>::load(p, o); }
 
 // Token shift over a partially reversed stream, in the ORIGINAL token order: the bidirectional encoder
@@ -80,6 +68,23 @@ __device__ __forceinline__ int next_tok(int t, int n, int T)
     if (n <= 0 || t >= n) return t + 1 < T ? t + 1 : -1;
     if (t >= 1) return t - 1;
     return n < T ? n : -1;                               // token 0 closes the reversed span
+}
+
+// The one lerp of the forward kernels: the NS blends of x, the row's channels at element `at` of a plane, with xp, the token in front of
+// it; planes `plane` elements apart.  All a forward kernel decides is where xp comes from.  (Here and in the backward helpers the row's
+// offset joins the base pointer before the plane's: one vector address per tensor and a scalar step per plane, as the kernels had it.)
+template <int NS, bool HAS_M>
+__device__ __forceinline__ void lerp_store(const LerpArgs& a, long plane, long at, int c, const float (&x)[4], const float (&xp)[4])
+{
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float maa[4], m[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
+        ld4(a.maa + c + (long)s * a.C, maa);
+        if constexpr (HAS_M) ld4(a.m + at + s * plane, m);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = fmaf(xp[q] - x[q], maa[q] + m[q], x[q]);
+        io4<bf16_t>::store(a.out + at + s * plane, o);
+    }
 }
 
 template <int NS, bool HAS_M, bool VARLEN = false>
@@ -101,16 +106,7 @@ __global__ void ddlerp_fwd_kernel(const LerpArgs a)
         if (tp >= 0) ld4(a.x + ((long)b * a.T + tp) * a.C + c, xp);
         else if (a.shifted0) ld4(a.shifted0 + (long)b * a.C + c, xp);
     }
-    const long plane = (long)a.B * a.T * a.C;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        float maa[4], m[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
-        ld4(a.maa + (long)s * a.C + c, maa);
-        if constexpr (HAS_M) ld4(a.m + s * plane + row * a.C + c, m);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = fmaf(xp[q] - x[q], maa[q] + m[q], x[q]);
-        io4<bf16_t>::store(a.out + s * plane + row * a.C + c, o);
-    }
+    lerp_store<NS, HAS_M>(a, (long)a.B * a.T * a.C, row * a.C + c, c, x, xp);
 }
 
 // The VARLEN forward with the token in front of a sequence taken from a slot pool (wkv6_ddlerp_slots_forward): the same loads of x, the same
@@ -130,16 +126,7 @@ __global__ void ddlerp_fwd_slots_kernel(const SlotLerpArgs a)
         const int sl = a.slot ? a.slot[sq] : sq;
         if (sl >= 0 && sl < a.n_slots) ld4(a.shifted0 + (long)sl * a.C + c, xp);
     }
-    const long plane = (long)a.T * a.C;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        float maa[4], m[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
-        ld4(a.maa + (long)s * a.C + c, maa);
-        if constexpr (HAS_M) ld4(a.m + s * plane + row * a.C + c, m);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = fmaf(xp[q] - x[q], maa[q] + m[q], x[q]);
-        io4<bf16_t>::store(a.out + s * plane + row * a.C + c, o);
-    }
+    lerp_store<NS, HAS_M>(a, (long)a.T * a.C, row * a.C + c, c, x, xp);
 }
 
 // Backward: dx_t = sum_s dout_{s,t} (1 - c_{s,t}) + sum_s dout_{s,t+1} c_{s,t+1}  (c = maa + m; the second term is the adjoint
@@ -147,22 +134,79 @@ __global__ void ddlerp_fwd_slots_kernel(const SlotLerpArgs a)
 // rows [p per, (p + 1) per), per = ceil(rows / nparts), backwards; reversed-span streams: workgroup p handles rows p, p + nparts, ...
 // (VARLEN: the plain walk, with "first token of a sequence" and "nothing behind this token" taken from cu_seqlens: one bisection per
 // workgroup for the sequence of its last row and one for the row behind it, then the boundaries are walked downwards with the rows)
-template <int NS, bool HAS_M, bool VARLEN = false>
-__global__ void ddlerp_bwd_kernel(const LerpArgs a)
+
+// what every backward kernel opens and closes with: maa in registers and a zero dmaa sum; the workgroup's partial row of dmaa_part
+template <int NS> __device__ __forceinline__ void bwd_open(const LerpArgs& a, int c, float (&maa)[NS][4], float (&acc)[NS][4])
 {
-    const int c = 4 * threadIdx.x;
-    const long plane = (long)a.B * a.T * a.C, rows = (long)a.B * a.T;
-    float maa[NS][4], acc[NS][4];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         ld4(a.maa + (long)s * a.C + c, maa[s]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[s][q] = 0.f;
     }
+}
+template <int NS> __device__ __forceinline__ void bwd_close(const LerpArgs& a, int c, const float (&acc)[NS][4])
+{
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        *reinterpret_cast<float4*>(a.dmaa_part + ((long)blockIdx.x * NS + s) * a.C + c) =
+            make_float4(acc[s][0], acc[s][1], acc[s][2], acc[s][3]);
+}
+// The hand-over: what row rn, the one behind row t in the stream, gives row t -- the part of its blends that came from x_t,
+// sum_s dout[s][rn] (maa_s + m_s[rn]) -- added to g plane by plane, s = 0 first.  Every path sums it in this order, on top of zeros, and
+// adds row t's own terms afterwards: the plain walk, the dense reversed branch and the packed kernels agree bit for bit.
+template <int NS, bool HAS_M>
+__device__ __forceinline__ void hand_over(const LerpArgs& a, int c, long rn, const float (&maa)[NS][4], float (&g)[4])
+{
+    const long plane = (long)a.B * a.T * a.C, at = rn * a.C + c;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float dn[4], mn[4] = {0.f, 0.f, 0.f, 0.f};
+        ld4(a.dout + at + s * plane, dn);
+        if constexpr (HAS_M) ld4(a.m + at + s * plane, mn);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) g[q] = fmaf(dn[q], maa[s][q] + mn[q], g[q]);
+    }
+}
+// Backward of a row whose stream neighbours are not the adjacent rows: xp_src = the [C] row of the token in front (null: zero), rown = the
+// row one stream position later (-1: none), fetched by a hand-over of its own (54 bytes per token-channel at NS = 5, where the plain
+// walk carries it: 34).  All a kernel decides is the two neighbours.
+template <int NS, bool HAS_M>
+__device__ __forceinline__ void bwd_far_row(const LerpArgs& a, int c, long row, const bf16_t* xp_src, long rown,
+                                            const float (&maa)[NS][4], float (&acc)[NS][4])
+{
+    const long plane = (long)a.B * a.T * a.C, at = row * a.C + c;
+    float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
+    ld4(a.x + at, x);
+    if (xp_src) ld4(xp_src + c, xp);
+    if (rown >= 0) hand_over<NS, HAS_M>(a, c, rown, maa, g);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float d[4], m[4] = {0.f, 0.f, 0.f, 0.f};
+        ld4(a.dout + at + s * plane, d);
+        if constexpr (HAS_M) ld4(a.m + at + s * plane, m);
+        float dm[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            g[q] = fmaf(d[q], 1.f - (maa[s][q] + m[q]), g[q]);
+            dm[q] = d[q] * (xp[q] - x[q]);
+            acc[s][q] += dm[q];
+        }
+        if constexpr (HAS_M) io4<bf16_t>::store(a.dm + at + s * plane, dm);
+    }
+    io4<bf16_t>::store(a.dx + at, g);
+}
+
+template <int NS, bool HAS_M, bool VARLEN = false>
+__global__ void ddlerp_bwd_kernel(const LerpArgs a)
+{
+    const int c = 4 * threadIdx.x;
+    const long plane = (long)a.B * a.T * a.C, rows = (long)a.B * a.T;
+    float maa[NS][4], acc[NS][4];
+    bwd_open<NS>(a, c, maa, acc);
     if (VARLEN || !a.rev_n) {
-        // Plain stream: a workgroup walks a contiguous run of rows backwards, so what token t+1 hands to token t -- the part of
-        // its blends that came from x_t:  sum_s dout[s][t+1] (maa_s + m_s[t+1])  -- is four floats carried in registers
-        // instead of a second read of dout and m (54 -> 34 bytes per token-channel at NS = 5).
+        // Plain stream: a workgroup walks a contiguous run of rows backwards, so what token t+1 hands to token t is four floats
+        // carried in registers instead of a second read of dout and m (54 -> 34 bytes per token-channel at NS = 5).
         const long per = (rows + gridDim.x - 1) / gridDim.x, r0 = (long)blockIdx.x * per, r1 = min(rows, r0 + per);
         float carry[4] = {0.f, 0.f, 0.f, 0.f};
         [[maybe_unused]] int sq = -1;                             // VARLEN: sequence of the row at hand, its first row,
@@ -178,16 +222,8 @@ __global__ void ddlerp_bwd_kernel(const LerpArgs a)
                 }
             }
         }
-        if (r1 > r0 && r1 < rows && (VARLEN ? !next_opens : r1 % a.T != 0)) {          // the run ends inside a sequence: fetch the next row's hand-over once
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                float dn[4], mn[4] = {0.f, 0.f, 0.f, 0.f};
-                ld4(a.dout + s * plane + r1 * a.C + c, dn);
-                if constexpr (HAS_M) ld4(a.m + s * plane + r1 * a.C + c, mn);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) carry[q] = fmaf(dn[q], maa[s][q] + mn[q], carry[q]);
-            }
-        }
+        if (r1 > r0 && r1 < rows && (VARLEN ? !next_opens : r1 % a.T != 0))            // the run ends inside a sequence: fetch the next row's hand-over once
+            hand_over<NS, HAS_M>(a, c, r1, maa, carry);
         for (long row = r1 - 1; row >= r0; --row) {
             const int t = (int)(row % a.T), b = (int)(row / a.T);
             float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f}, g[4], own[4] = {0.f, 0.f, 0.f, 0.f};
@@ -229,43 +265,12 @@ __global__ void ddlerp_bwd_kernel(const LerpArgs a)
     } else
     for (long row = blockIdx.x; row < rows; row += gridDim.x) {       // reversed-span streams: the neighbours are not adjacent rows
         const int t = (int)(row % a.T), b = (int)(row / a.T);
-        float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
-        ld4(a.x + row * a.C + c, x);
         const int nrev = min(max(a.rev_n[b], 0), a.T);
         const int tp = prev_tok(t, nrev), tn = next_tok(t, nrev, a.T);
-        if (tp >= 0) ld4(a.x + ((long)b * a.T + tp) * a.C + c, xp);
-        else if (a.shifted0) ld4(a.shifted0 + (long)b * a.C + c, xp);
-        if (tn >= 0) {                                        // (summed in the order of the plain path: the two agree bit for bit)
-            const long rown = (long)b * a.T + tn;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                float dn[4], mn[4] = {0.f, 0.f, 0.f, 0.f};
-                ld4(a.dout + s * plane + rown * a.C + c, dn);
-                if constexpr (HAS_M) ld4(a.m + s * plane + rown * a.C + c, mn);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) g[q] = fmaf(dn[q], maa[s][q] + mn[q], g[q]);
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            float d[4], m[4] = {0.f, 0.f, 0.f, 0.f};
-            ld4(a.dout + s * plane + row * a.C + c, d);
-            if constexpr (HAS_M) ld4(a.m + s * plane + row * a.C + c, m);
-            float dm[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                g[q] = fmaf(d[q], 1.f - (maa[s][q] + m[q]), g[q]);
-                dm[q] = d[q] * (xp[q] - x[q]);
-                acc[s][q] += dm[q];
-            }
-            if constexpr (HAS_M) io4<bf16_t>::store(a.dm + s * plane + row * a.C + c, dm);
-        }
-        io4<bf16_t>::store(a.dx + row * a.C + c, g);
+        bwd_far_row<NS, HAS_M>(a, c, row, tp >= 0 ? a.x + ((long)b * a.T + tp) * a.C : a.shifted0 ? a.shifted0 + (long)b * a.C : nullptr,
+                               tn >= 0 ? (long)b * a.T + tn : -1, maa, acc);
     }
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-        *reinterpret_cast<float4*>(a.dmaa_part + ((long)blockIdx.x * NS + s) * a.C + c) =
-            make_float4(acc[s][0], acc[s][1], acc[s][2], acc[s][3]);
+    bwd_close<NS>(a, c, acc);
 }
 
 // Packed batch under a reversal map (a.cu and a.rev_n, [n_seq]): the stream of sequence s is "its first rev_n[s] tokens reversed, the rest in
@@ -291,6 +296,12 @@ __device__ __forceinline__ SeqSpan seq_span(const LerpArgs& a, long row)
     p.nrev = (int)min((long)max(a.rev_n[p.sq], 0), end - p.start);
     return p;
 }
+// the token in front of a token of the span, tp = its prev_tok within the span: row start + tp, or (-1) the sequence's carried token
+__device__ __forceinline__ const bf16_t* span_xp_src(const LerpArgs& a, const SeqSpan& sp, int tp)
+{
+    if (tp >= 0) return a.x + (sp.start + tp) * a.C;
+    return a.shifted0 && sp.sq >= 0 ? a.shifted0 + (long)sp.sq * a.C : nullptr;
+}
 
 template <int NS, bool HAS_M>
 __global__ void ddlerp_fwd_varlen_rev_kernel(const LerpArgs a)
@@ -303,69 +314,23 @@ __global__ void ddlerp_fwd_varlen_rev_kernel(const LerpArgs a)
     const int tp = prev_tok((int)(row - sp.start), sp.nrev);
     if (tp >= 0) ld4(a.x + (sp.start + tp) * a.C + c, xp);
     else if (a.shifted0 && sp.sq >= 0) ld4(a.shifted0 + (long)sp.sq * a.C + c, xp);
-    const long plane = (long)a.B * a.T * a.C;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        float maa[4], m[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
-        ld4(a.maa + (long)s * a.C + c, maa);
-        if constexpr (HAS_M) ld4(a.m + s * plane + row * a.C + c, m);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = fmaf(xp[q] - x[q], maa[q] + m[q], x[q]);
-        io4<bf16_t>::store(a.out + s * plane + row * a.C + c, o);
-    }
+    lerp_store<NS, HAS_M>(a, (long)a.B * a.T * a.C, row * a.C + c, c, x, xp);
 }
 
 template <int NS, bool HAS_M>
 __global__ void ddlerp_bwd_varlen_rev_kernel(const LerpArgs a)
 {
     const int c = 4 * threadIdx.x;
-    const long plane = (long)a.B * a.T * a.C, rows = (long)a.B * a.T;
+    const long rows = (long)a.B * a.T;
     float maa[NS][4], acc[NS][4];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        ld4(a.maa + (long)s * a.C + c, maa[s]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[s][q] = 0.f;
-    }
+    bwd_open<NS>(a, c, maa, acc);
     for (long row = blockIdx.x; row < rows; row += gridDim.x) {
-        float x[4], xp[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
-        ld4(a.x + row * a.C + c, x);
         const SeqSpan sp = seq_span(a, row);
         const int t = (int)(row - sp.start);
-        const int tp = prev_tok(t, sp.nrev), tn = next_tok(t, sp.nrev, sp.slen);
-        if (tp >= 0) ld4(a.x + (sp.start + tp) * a.C + c, xp);
-        else if (a.shifted0 && sp.sq >= 0) ld4(a.shifted0 + (long)sp.sq * a.C + c, xp);
-        if (tn >= 0) {                                        // (summed in the order of the dense kernel: the two agree bit for bit)
-            const long rown = sp.start + tn;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                float dn[4], mn[4] = {0.f, 0.f, 0.f, 0.f};
-                ld4(a.dout + s * plane + rown * a.C + c, dn);
-                if constexpr (HAS_M) ld4(a.m + s * plane + rown * a.C + c, mn);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) g[q] = fmaf(dn[q], maa[s][q] + mn[q], g[q]);
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            float d[4], m[4] = {0.f, 0.f, 0.f, 0.f};
-            ld4(a.dout + s * plane + row * a.C + c, d);
-            if constexpr (HAS_M) ld4(a.m + s * plane + row * a.C + c, m);
-            float dm[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                g[q] = fmaf(d[q], 1.f - (maa[s][q] + m[q]), g[q]);
-                dm[q] = d[q] * (xp[q] - x[q]);
-                acc[s][q] += dm[q];
-            }
-            if constexpr (HAS_M) io4<bf16_t>::store(a.dm + s * plane + row * a.C + c, dm);
-        }
-        io4<bf16_t>::store(a.dx + row * a.C + c, g);
+        const int tn = next_tok(t, sp.nrev, sp.slen);
+        bwd_far_row<NS, HAS_M>(a, c, row, span_xp_src(a, sp, prev_tok(t, sp.nrev)), tn >= 0 ? sp.start + tn : -1, maa, acc);
     }
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-        *reinterpret_cast<float4*>(a.dmaa_part + ((long)blockIdx.x * NS + s) * a.C + c) =
-            make_float4(acc[s][0], acc[s][1], acc[s][2], acc[s][3]);
+    bwd_close<NS>(a, c, acc);
 }
 
 struct GnArgs {
@@ -516,8 +481,6 @@ struct KeepArgs {
     const int* snap_slot;     // [n_snap]
 };
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 __global__ void shift_keep_kernel(const KeepArgs a)
 {
     const int i = blockIdx.x;
@@ -525,13 +488,7 @@ __global__ void shift_keep_kernel(const KeepArgs a)
     const int e = i - a.n_seq;                           // snapshot entry (!last): 0 <= e < n_snap by the grid
     int s = i;
     if (!last) {                                         // the last s < n_seq with cu_snap[s] <= e
-        int lo = 0, hi = a.n_seq;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (clampi(a.cu_snap[mid], 0, a.n_snap) <= e) lo = mid + 1;
-            else hi = mid;
-        }
-        s = lo - 1;
+        s = seq_of_row(a.cu_snap, a.n_seq, e, [&](int v) { return clampi(v, 0, a.n_snap); });
         if (s < 0) return;
     }
     const int a0 = clampi(a.cu[s], 0, a.total_T), b0 = clampi(a.cu[s + 1], 0, a.total_T);
@@ -554,12 +511,10 @@ __global__ void shift_keep_kernel(const KeepArgs a)
     *(v2u*)(a.pool + (long)dst * a.C + c) = *(const v2u*)(a.x + (long)row * a.C + c);
 }
 
-template <typename K> int launch_flat(K kernel, const FlatArgs& a, hipStream_t st)
+template <auto Kernel> int launch_flat(const FlatArgs& a, hipStream_t st)
 {
     const long blocks = (a.n8 + 255) / 256;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, a);
-    const hipError_t e = hipGetLastError();
-    return to_rc(e);
+    return to_rc(launch<Kernel>(dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, a));
 }
 
 int check_rows(long rows, int C)
@@ -569,49 +524,70 @@ int check_rows(long rows, int C)
     return WKV6_OK;
 }
 
-template <int NS, bool HAS_M> void launch_lerp(const LerpArgs& a, bool bwd, hipStream_t st)
-{
-    if (a.cu && a.rev_n) {
-        if (bwd) hipLaunchKernelGGL((ddlerp_bwd_varlen_rev_kernel<NS, HAS_M>), dim3(a.nparts), dim3(a.C / 4), 0, st, a);
-        else hipLaunchKernelGGL((ddlerp_fwd_varlen_rev_kernel<NS, HAS_M>), dim3((unsigned)((long)a.B * a.T)), dim3(a.C / 4), 0, st, a);
-        return;
-    }
-    if (a.cu) {
-        if (bwd) hipLaunchKernelGGL((ddlerp_bwd_kernel<NS, HAS_M, true>), dim3(a.nparts), dim3(a.C / 4), 0, st, a);
-        else hipLaunchKernelGGL((ddlerp_fwd_kernel<NS, HAS_M, true>), dim3((unsigned)((long)a.B * a.T)), dim3(a.C / 4), 0, st, a);
-        return;
-    }
-    if (bwd) hipLaunchKernelGGL((ddlerp_bwd_kernel<NS, HAS_M>), dim3(a.nparts), dim3(a.C / 4), 0, st, a);
-    else hipLaunchKernelGGL((ddlerp_fwd_kernel<NS, HAS_M>), dim3((unsigned)((long)a.B * a.T)), dim3(a.C / 4), 0, st, a);
-}
-
-int dispatch_lerp(const LerpArgs& a, bool bwd, hipStream_t st)
-{
-    if (a.NS == 1 && !a.m) launch_lerp<1, false>(a, bwd, st);
-    else if (a.NS == 5 && a.m) launch_lerp<5, true>(a, bwd, st);
-    else if (a.NS == 1 && a.m) launch_lerp<1, true>(a, bwd, st);
-    else if (a.NS == 2 && !a.m) launch_lerp<2, false>(a, bwd, st);
-    else return WKV6_EUNSUPPORTED;
-    const hipError_t e = hipGetLastError();
-    return to_rc(e);
-}
-
-int dispatch_slot_lerp(const SlotLerpArgs& a, hipStream_t st)
-{
-    const dim3 grid((unsigned)a.T), block(a.C / 4);
-    if (a.NS == 1 && !a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<1, false>), grid, block, 0, st, a);
-    else if (a.NS == 5 && a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<5, true>), grid, block, 0, st, a);
-    else if (a.NS == 1 && a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<1, true>), grid, block, 0, st, a);
-    else if (a.NS == 2 && !a.m) hipLaunchKernelGGL((ddlerp_fwd_slots_kernel<2, false>), grid, block, 0, st, a);
-    else return WKV6_EUNSUPPORTED;
-    const hipError_t e = hipGetLastError();
-    return to_rc(e);
-}
-
 bool overlap(const void* p, size_t pn, const void* q, size_t qn)
 {
     const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
     return a < b + qn && b < a + pn;
+}
+
+// The (NS, m) pairs the lerp kernels are built for, in one place: f(NS, HAS_M), both as integral constants, launches; any other pair is
+// refused.
+template <typename F> int dispatch_lerp(int NS, bool has_m, F f)
+{
+    if (NS == 1 && !has_m) return to_rc(f(std::integral_constant<int, 1>(), std::false_type()));
+    if (NS == 5 && has_m) return to_rc(f(std::integral_constant<int, 5>(), std::true_type()));
+    if (NS == 1 && has_m) return to_rc(f(std::integral_constant<int, 1>(), std::true_type()));
+    if (NS == 2 && !has_m) return to_rc(f(std::integral_constant<int, 2>(), std::false_type()));
+    return WKV6_EUNSUPPORTED;
+}
+
+// forward: one workgroup per row; backward: nparts workgroups.  The kernel by the arrays that are there: cu -> packed, rev_n -> reversal map
+template <int NS, bool HAS_M> hipError_t launch_lerp(const LerpArgs& a, bool bwd, hipStream_t st)
+{
+    const dim3 grid(bwd ? (unsigned)a.nparts : (unsigned)((long)a.B * a.T)), block(a.C / 4);
+    if (a.cu && a.rev_n)
+        return bwd ? launch<ddlerp_bwd_varlen_rev_kernel<NS, HAS_M>>(grid, block, 0, st, a)
+                   : launch<ddlerp_fwd_varlen_rev_kernel<NS, HAS_M>>(grid, block, 0, st, a);
+    if (a.cu) return bwd ? launch<ddlerp_bwd_kernel<NS, HAS_M, true>>(grid, block, 0, st, a) : launch<ddlerp_fwd_kernel<NS, HAS_M, true>>(grid, block, 0, st, a);
+    return bwd ? launch<ddlerp_bwd_kernel<NS, HAS_M>>(grid, block, 0, st, a) : launch<ddlerp_fwd_kernel<NS, HAS_M>>(grid, block, 0, st, a);
+}
+
+// ---- what the eight wkv6_ddlerp_* entry points share: an entry point types its tensors into the argument block (lerp_tensors, and
+// set_grads for a backward), adds the arrays of its form, and ddlerp checks sizes, then nulls, then dispatches
+enum LerpForm { DENSE, PACKED, SLOTS };
+
+SlotLerpArgs lerp_tensors(int C, int NS, const void* x, const void* shifted0, const void* m, const void* maa, const int* rev_n)
+{
+    SlotLerpArgs a = {};
+    a.C = C; a.NS = NS;
+    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    a.rev_n = rev_n;
+    return a;
+}
+void set_grads(LerpArgs& a, const void* dout, void* dx, void* dm, float* dmaa_part, int nparts)
+{
+    a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
+}
+// B x T rows as the caller gave them (PACKED, SLOTS: 1 x total_T).  The order of the refusals is part of the interface.
+int ddlerp(LerpForm form, bool bwd, long B, long T, SlotLerpArgs a, void* stream)
+{
+    const bool packed = form != DENSE;
+    if (B < 1 || T < 1 || (packed && a.n_seq < 1) || (form == SLOTS && a.n_slots < 1) || (bwd && a.nparts < 1)) return WKV6_EINVAL;
+    if (int rc = check_rows(B * T, a.C)) return rc;
+    if (packed && T > 0x7fffffffL) return WKV6_EUNSUPPORTED;                  // cu_seqlens is int32
+    if (form == SLOTS && !a.slot && a.n_slots < a.n_seq) return WKV6_EINVAL;  // slot = sequence index: the pool must hold n_seq slots
+    if ((packed && !a.cu) || !a.x || !a.maa || (form == SLOTS && !a.shifted0)) return WKV6_ENULL;
+    if (bwd ? !a.dout || !a.dx || !a.dmaa_part || (a.m && !a.dm) : !a.out) return WKV6_ENULL;
+    if (form == SLOTS) {
+        if (((uintptr_t)a.x | (uintptr_t)a.out | (uintptr_t)a.shifted0) & 7) return WKV6_EINVAL;
+        if (overlap(a.out, (size_t)a.NS * T * a.C * 2, a.shifted0, (size_t)a.n_slots * a.C * 2)) return WKV6_EINVAL;
+    }
+    a.B = (int)B; a.T = (int)T;
+    const hipStream_t st = (hipStream_t)stream;
+    return dispatch_lerp(a.NS, a.m != nullptr, [&](auto ns, auto has_m) {
+        if (form == SLOTS) return launch<ddlerp_fwd_slots_kernel<ns(), has_m()>>(dim3((unsigned)a.T), dim3(a.C / 4), 0, st, a);
+        return launch_lerp<ns(), has_m()>(a, bwd, st);
+    });
 }
 
 }  // namespace
@@ -621,25 +597,18 @@ using namespace wkv6;
 
 extern "C" {
 
-int wkv6_ddlerp_rev_forward(int B, int T, int C, int NS, const void* x, const void* shifted0, const void* m, const void* maa,
-                            const int* rev_n, void* out, void* stream)
-{
-    if (B < 1 || T < 1) return WKV6_EINVAL;
-    if (int rc = check_rows((long)B * T, C)) return rc;
-    if (!x || !maa || !out) return WKV6_ENULL;
-    LerpArgs a = {};
-    a.B = B; a.T = T; a.C = C; a.NS = NS;
-    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
-    a.rev_n = rev_n;
-    a.out = (bf16_t*)out;
-    return dispatch_lerp(a, false, (hipStream_t)stream);
-}
 int wkv6_ddlerp_forward(int B, int T, int C, int NS, const void* x, const void* shifted0, const void* m, const void* maa,
                         void* out, void* stream)
 {
     return wkv6_ddlerp_rev_forward(B, T, C, NS, x, shifted0, m, maa, nullptr, out, stream);
 }
-
+int wkv6_ddlerp_rev_forward(int B, int T, int C, int NS, const void* x, const void* shifted0, const void* m, const void* maa,
+                            const int* rev_n, void* out, void* stream)
+{
+    SlotLerpArgs a = lerp_tensors(C, NS, x, shifted0, m, maa, rev_n);
+    a.out = (bf16_t*)out;
+    return ddlerp(DENSE, false, B, T, a, stream);
+}
 int wkv6_ddlerp_backward(int B, int T, int C, int NS, const void* x, const void* shifted0, const void* m, const void* maa,
                          const void* dout, void* dx, void* dm, float* dmaa_part, int nparts, void* stream)
 {
@@ -648,63 +617,49 @@ int wkv6_ddlerp_backward(int B, int T, int C, int NS, const void* x, const void*
 int wkv6_ddlerp_rev_backward(int B, int T, int C, int NS, const void* x, const void* shifted0, const void* m, const void* maa,
                              const int* rev_n, const void* dout, void* dx, void* dm, float* dmaa_part, int nparts, void* stream)
 {
-    if (B < 1 || T < 1 || nparts < 1) return WKV6_EINVAL;
-    if (int rc = check_rows((long)B * T, C)) return rc;
-    if (!x || !maa || !dout || !dx || !dmaa_part || (m && !dm)) return WKV6_ENULL;
-    LerpArgs a = {};
-    a.B = B; a.T = T; a.C = C; a.NS = NS;
-    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
-    a.rev_n = rev_n;
-    a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
-    return dispatch_lerp(a, true, (hipStream_t)stream);
+    SlotLerpArgs a = lerp_tensors(C, NS, x, shifted0, m, maa, rev_n);
+    set_grads(a, dout, dx, dm, dmaa_part, nparts);
+    return ddlerp(DENSE, true, B, T, a, stream);
 }
 
+// (the packed calls: rev_n == null is the plain packed shift)
 int wkv6_ddlerp_varlen_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
                                const void* m, const void* maa, void* out, void* stream)
 {
-    if (total_T < 1 || n_seq < 1) return WKV6_EINVAL;
-    if (int rc = check_rows(total_T, C)) return rc;
-    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;          // cu_seqlens is int32
-    if (!cu_seqlens || !x || !maa || !out) return WKV6_ENULL;
-    LerpArgs a = {};
-    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
-    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    return wkv6_ddlerp_varlen_rev_forward(total_T, n_seq, C, NS, cu_seqlens, x, shifted0, m, maa, nullptr, out, stream);
+}
+int wkv6_ddlerp_varlen_rev_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                                   const void* m, const void* maa, const int* rev_n, void* out, void* stream)
+{
+    SlotLerpArgs a = lerp_tensors(C, NS, x, shifted0, m, maa, rev_n);
     a.cu = cu_seqlens; a.n_seq = n_seq;
     a.out = (bf16_t*)out;
-    return dispatch_lerp(a, false, (hipStream_t)stream);
+    return ddlerp(PACKED, false, 1, total_T, a, stream);
 }
 int wkv6_ddlerp_varlen_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
                                 const void* m, const void* maa, const void* dout, void* dx, void* dm, float* dmaa_part, int nparts,
                                 void* stream)
 {
-    if (total_T < 1 || n_seq < 1 || nparts < 1) return WKV6_EINVAL;
-    if (int rc = check_rows(total_T, C)) return rc;
-    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;
-    if (!cu_seqlens || !x || !maa || !dout || !dx || !dmaa_part || (m && !dm)) return WKV6_ENULL;
-    LerpArgs a = {};
-    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
-    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    return wkv6_ddlerp_varlen_rev_backward(total_T, n_seq, C, NS, cu_seqlens, x, shifted0, m, maa, nullptr, dout, dx, dm, dmaa_part, nparts,
+                                           stream);
+}
+int wkv6_ddlerp_varlen_rev_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
+                                    const void* m, const void* maa, const int* rev_n, const void* dout, void* dx, void* dm,
+                                    float* dmaa_part, int nparts, void* stream)
+{
+    SlotLerpArgs a = lerp_tensors(C, NS, x, shifted0, m, maa, rev_n);
     a.cu = cu_seqlens; a.n_seq = n_seq;
-    a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
-    return dispatch_lerp(a, true, (hipStream_t)stream);
+    set_grads(a, dout, dx, dm, dmaa_part, nparts);
+    return ddlerp(PACKED, true, 1, total_T, a, stream);
 }
 
 int wkv6_ddlerp_slots_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shift_pool,
                               int n_slots, const int* slot, const void* m, const void* maa, void* out, void* stream)
 {
-    if (total_T < 1 || n_seq < 1 || n_slots < 1) return WKV6_EINVAL;
-    if (int rc = check_rows(total_T, C)) return rc;
-    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;          // cu_seqlens is int32
-    if (!slot && n_slots < n_seq) return WKV6_EINVAL;             // slot = sequence index: the pool must hold n_seq slots
-    if (!cu_seqlens || !x || !maa || !out || !shift_pool) return WKV6_ENULL;
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)shift_pool) & 7) return WKV6_EINVAL;
-    if (overlap(out, (size_t)NS * total_T * C * 2, shift_pool, (size_t)n_slots * C * 2)) return WKV6_EINVAL;
-    SlotLerpArgs a = {};
-    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
-    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shift_pool; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
+    SlotLerpArgs a = lerp_tensors(C, NS, x, shift_pool, m, maa, nullptr);
     a.cu = cu_seqlens; a.n_seq = n_seq; a.slot = slot; a.n_slots = n_slots;
     a.out = (bf16_t*)out;
-    return dispatch_slot_lerp(a, (hipStream_t)stream);
+    return ddlerp(SLOTS, false, 1, total_T, a, stream);
 }
 
 int wkv6_shift_keep(long total_T, int n_seq, int max_seqlen, int C, const int* cu_seqlens, const void* x, void* shift_pool, int n_slots,
@@ -726,42 +681,7 @@ int wkv6_shift_keep(long total_T, int n_seq, int max_seqlen, int C, const int* c
     a.snap_every = snaps ? snap_every : 0; a.n_snap = snaps ? n_snap : 0;
     a.cu = cu_seqlens; a.x = (const bf16_t*)x; a.pool = (bf16_t*)shift_pool; a.slot_out = slot_out;
     a.cu_snap = cu_snap; a.snap_slot = snap_slot;
-    hipLaunchKernelGGL(shift_keep_kernel, dim3((unsigned)grid), dim3(C / 4), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return to_rc(e);
-}
-
-// rev_n == null: the plain packed shift
-int wkv6_ddlerp_varlen_rev_forward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
-                                   const void* m, const void* maa, const int* rev_n, void* out, void* stream)
-{
-    if (!rev_n) return wkv6_ddlerp_varlen_forward(total_T, n_seq, C, NS, cu_seqlens, x, shifted0, m, maa, out, stream);
-    if (total_T < 1 || n_seq < 1) return WKV6_EINVAL;
-    if (int rc = check_rows(total_T, C)) return rc;
-    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;
-    if (!cu_seqlens || !x || !maa || !out) return WKV6_ENULL;
-    LerpArgs a = {};
-    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
-    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
-    a.cu = cu_seqlens; a.n_seq = n_seq; a.rev_n = rev_n;
-    a.out = (bf16_t*)out;
-    return dispatch_lerp(a, false, (hipStream_t)stream);
-}
-int wkv6_ddlerp_varlen_rev_backward(long total_T, int n_seq, int C, int NS, const int* cu_seqlens, const void* x, const void* shifted0,
-                                    const void* m, const void* maa, const int* rev_n, const void* dout, void* dx, void* dm,
-                                    float* dmaa_part, int nparts, void* stream)
-{
-    if (!rev_n) return wkv6_ddlerp_varlen_backward(total_T, n_seq, C, NS, cu_seqlens, x, shifted0, m, maa, dout, dx, dm, dmaa_part, nparts, stream);
-    if (total_T < 1 || n_seq < 1 || nparts < 1) return WKV6_EINVAL;
-    if (int rc = check_rows(total_T, C)) return rc;
-    if (total_T > 0x7fffffffL) return WKV6_EUNSUPPORTED;
-    if (!cu_seqlens || !x || !maa || !dout || !dx || !dmaa_part || (m && !dm)) return WKV6_ENULL;
-    LerpArgs a = {};
-    a.B = 1; a.T = (int)total_T; a.C = C; a.NS = NS;
-    a.x = (const bf16_t*)x; a.shifted0 = (const bf16_t*)shifted0; a.m = (const bf16_t*)m; a.maa = (const bf16_t*)maa;
-    a.cu = cu_seqlens; a.n_seq = n_seq; a.rev_n = rev_n;
-    a.dout = (const bf16_t*)dout; a.dx = (bf16_t*)dx; a.dm = (bf16_t*)dm; a.dmaa_part = dmaa_part; a.nparts = nparts;
-    return dispatch_lerp(a, true, (hipStream_t)stream);
+    return to_rc(launch<shift_keep_kernel>(dim3((unsigned)grid), dim3(C / 4), 0, (hipStream_t)stream, a));
 }
 
 int wkv6_sqrelu_forward(long n, const void* x, void* out, void* stream)
@@ -770,7 +690,7 @@ int wkv6_sqrelu_forward(long n, const void* x, void* out, void* stream)
     if (!x || !out) return WKV6_ENULL;
     FlatArgs a = {};
     a.n8 = n / 8; a.a = (const bf16_t*)x; a.out = (bf16_t*)out;
-    return launch_flat(sqrelu_kernel<false>, a, (hipStream_t)stream);
+    return launch_flat<sqrelu_kernel<false>>(a, (hipStream_t)stream);
 }
 int wkv6_sqrelu_backward(long n, const void* x, const void* dout, void* dx, void* stream)
 {
@@ -778,7 +698,7 @@ int wkv6_sqrelu_backward(long n, const void* x, const void* dout, void* dx, void
     if (!x || !dout || !dx) return WKV6_ENULL;
     FlatArgs a = {};
     a.n8 = n / 8; a.a = (const bf16_t*)x; a.dout = (const bf16_t*)dout; a.da = (bf16_t*)dx;
-    return launch_flat(sqrelu_kernel<true>, a, (hipStream_t)stream);
+    return launch_flat<sqrelu_kernel<true>>(a, (hipStream_t)stream);
 }
 int wkv6_sigmul_forward(long n, const void* r, const void* kv, void* out, void* stream)
 {
@@ -786,7 +706,7 @@ int wkv6_sigmul_forward(long n, const void* r, const void* kv, void* out, void* 
     if (!r || !kv || !out) return WKV6_ENULL;
     FlatArgs a = {};
     a.n8 = n / 8; a.a = (const bf16_t*)r; a.b = (const bf16_t*)kv; a.out = (bf16_t*)out;
-    return launch_flat(sigmul_kernel<false>, a, (hipStream_t)stream);
+    return launch_flat<sigmul_kernel<false>>(a, (hipStream_t)stream);
 }
 int wkv6_sigmul_backward(long n, const void* r, const void* kv, const void* dout, void* dr, void* dkv, void* stream)
 {
@@ -794,7 +714,7 @@ int wkv6_sigmul_backward(long n, const void* r, const void* kv, const void* dout
     if (!r || !kv || !dout || !dr || !dkv) return WKV6_ENULL;
     FlatArgs a = {};
     a.n8 = n / 8; a.a = (const bf16_t*)r; a.b = (const bf16_t*)kv; a.dout = (const bf16_t*)dout; a.da = (bf16_t*)dr; a.db = (bf16_t*)dkv;
-    return launch_flat(sigmul_kernel<true>, a, (hipStream_t)stream);
+    return launch_flat<sigmul_kernel<true>>(a, (hipStream_t)stream);
 }
 
 int wkv6_gn_gate_forward(long rows, int C, int H, const void* y, const void* g, const void* gamma, const void* beta,
@@ -807,9 +727,7 @@ int wkv6_gn_gate_forward(long rows, int C, int H, const void* y, const void* g, 
     a.rows = rows; a.C = C; a.H = H; a.eps = eps;
     a.y = (const bf16_t*)y; a.g = (const bf16_t*)g; a.gamma = (const bf16_t*)gamma; a.beta = (const bf16_t*)beta;
     a.out = (bf16_t*)out; a.stats = stats;
-    hipLaunchKernelGGL(gn_gate_fwd_kernel, dim3((unsigned)rows), dim3(C / 4), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return to_rc(e);
+    return to_rc(launch<gn_gate_fwd_kernel>(dim3((unsigned)rows), dim3(C / 4), 0, (hipStream_t)stream, a));
 }
 
 int wkv6_gn_gate_backward(long rows, int C, int H, const void* y, const void* g, const void* gamma, const void* beta,
@@ -824,9 +742,7 @@ int wkv6_gn_gate_backward(long rows, int C, int H, const void* y, const void* g,
     a.y = (const bf16_t*)y; a.g = (const bf16_t*)g; a.gamma = (const bf16_t*)gamma; a.beta = (const bf16_t*)beta;
     a.stats = const_cast<float*>(stats); a.dout = (const bf16_t*)dout; a.dy = (bf16_t*)dy; a.dg = (bf16_t*)dg;
     a.dgamma_part = dgamma_part; a.dbeta_part = dbeta_part; a.nparts = nparts;
-    hipLaunchKernelGGL(gn_gate_bwd_kernel, dim3(nparts), dim3(C / 4), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    return to_rc(e);
+    return to_rc(launch<gn_gate_bwd_kernel>(dim3(nparts), dim3(C / 4), 0, (hipStream_t)stream, a));
 }
 
 }  // extern "C"

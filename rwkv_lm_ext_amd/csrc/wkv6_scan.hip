@@ -7,66 +7,6 @@ namespace {
 constexpr int TB = 16;                 // tokens staged per LDS batch
 constexpr int ROW = HEAD;              // floats per staged token row
 
-// ---- CPT-wide channel I/O (CPT = 2 or 4) ----------------------------------------------------------
-template <typename T, int CPT> struct ion;
-template <typename T> struct ion<T, 4> : io4<T> {};
-template <> struct ion<bf16_t, 2> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float (&o)[2])
-    {
-        const uint32_t raw = *reinterpret_cast<const uint32_t*>(p);
-        o[0] = bf_lo(raw); o[1] = bf_hi(raw);
-    }
-    static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[2])
-    {
-        *reinterpret_cast<uint32_t*>(p) = pack_bf2(v[0], v[1]);
-    }
-};
-template <> struct ion<f16_t, 2> {
-    typedef f16_t h2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ void load(const f16_t* p, float (&o)[2])
-    {
-        const h2 raw = *reinterpret_cast<const h2*>(p);
-        o[0] = (float)raw[0]; o[1] = (float)raw[1];
-    }
-    static __device__ __forceinline__ void store(f16_t* p, const float (&v)[2])
-    {
-        const h2 raw = {(f16_t)v[0], (f16_t)v[1]};
-        *reinterpret_cast<h2*>(p) = raw;
-    }
-};
-template <> struct ion<float, 2> {
-    static __device__ __forceinline__ void load(const float* p, float (&o)[2])
-    {
-        const float2 raw = *reinterpret_cast<const float2*>(p);
-        o[0] = raw.x; o[1] = raw.y;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[2])
-    {
-        *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-    }
-};
-template <int CPT> __device__ __forceinline__ void lds_store(float* p, const float (&v)[CPT])
-{
-    if constexpr (CPT == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-}
-template <int CPT> __device__ __forceinline__ void lds_load(const float* p, float (&v)[CPT])
-{
-    if constexpr (CPT == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        const float2 t = *reinterpret_cast<const float2*>(p);
-        v[0] = t.x; v[1] = t.y;
-    }
-}
-// sum over the TPT consecutive lanes that stage one token (TPT = 16 or 32)
-template <int TPT> __device__ __forceinline__ float token_sum(float x)
-{
-    x = row_sum16(x);
-    if constexpr (TPT == 32) x += __shfl_xor(x, 16);
-    return x;
-}
 template <int NV> __device__ __forceinline__ float pick(const float (&v)[NV], int s)
 {
     float o = v[0];

@@ -5,13 +5,6 @@ using namespace wkv6;
 
 namespace {            // (the kernels keep their names outside namespace wkv6: profile filters tell them from the operator kernels by it)
 
-// element o of a partial result (s_out, gs, gu): fp32, or rounded to bf16
-__device__ __forceinline__ void store_partial(void* out, int f32, long o, float x)
-{
-    if (f32) reinterpret_cast<float*>(out)[o] = x;
-    else reinterpret_cast<bf16_t*>(out)[o] = (bf16_t)(pack_bf2(x, 0.f) & 0xffffu);
-}
-
 // ---- forward: the sequence is cut into S segments that run as S times as many workgroups:
 //   1. state pass per segment from a zero state: A_seg = the segment's own contribution to the state, and the per-channel sum
 //      of its log-decays (ScanArgs::dsum);

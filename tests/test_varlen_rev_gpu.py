@@ -478,6 +478,40 @@ def test_token_shift_equals_the_dense_reversed_shift_on_each_sequence(vec, ns, h
         assert not bool(sl.grad[[i for i, n in enumerate(lens) if n == 0]].any())
 
 
+@pytest.mark.parametrize("nparts", [1, 5])
+@pytest.mark.parametrize("rev", [0, 1, 3, 4, 5])
+def test_token_shift_ns1_with_m_on_the_smallest_packed_batch(rev, nparts):
+    """NS = 1 with m, the pair the test above leaves out, through the C ABI at the smallest shapes at which the neighbour rule can go
+    wrong: C = 64, sequences of 0, 1 and 4 tokens between a row in front of cu[0] and one behind cu[n_seq], every sequence with
+    rev_n = rev (0, 1, len - 1, len, len + 1 of the longest), one workgroup and more workgroups than half the rows.  A row in front of
+    cu[0] is a plain stream of its own with a zero token in front; the row behind cu[n_seq] continues the last sequence in place.  out,
+    dx and dm equal the dense reversed call on each of those streams bit for bit; the partial rows sum to the fp64 terms."""
+    from rwkv_lm_ext_amd import _lib
+    from test_mix_kernels_gpu import check_partials, ddlerp_ref, lerp_bwd_abi, lerp_fwd_abi, no_nan, poisoned, ptr, rnd, stream
+    lib = _lib.load()
+    cu, T, Cx, n_seq = dev_i32([1, 1, 2, 6]), 7, 64, 3
+    x, maa, m = rnd(T, Cx, seed=60), rnd(1, Cx, scale=0.5, seed=61), rnd(1, T, Cx, scale=0.3, seed=62)
+    s0, dout, rev_n = rnd(n_seq, Cx, seed=63), rnd(1, T, Cx, seed=64), dev_i32([rev] * n_seq)
+    out, dx, dm, part = poisoned(1, T, Cx), poisoned(T, Cx), poisoned(1, T, Cx), poisoned(nparts, 1, Cx, dtype=torch.float32)
+    assert lib.wkv6_ddlerp_varlen_rev_forward(T, n_seq, Cx, 1, ptr(cu), ptr(x), ptr(s0), ptr(m), ptr(maa), ptr(rev_n), ptr(out),
+                                              stream()) == 0
+    assert lib.wkv6_ddlerp_varlen_rev_backward(T, n_seq, Cx, 1, ptr(cu), ptr(x), ptr(s0), ptr(m), ptr(maa), ptr(rev_n), ptr(dout), ptr(dx),
+                                               ptr(dm), ptr(part), nparts, stream()) == 0
+    torch.cuda.synchronize()
+    no_nan(f"rev {rev} nparts {nparts}", out, dx, dm, part)
+    terms = []
+    # (first row, rows, token in front, reversed span) of every stream of the batch
+    for t0, n, front, nrev in [(0, 1, None, 0), (1, 1, s0[1:2], min(rev, 1)), (2, 5, s0[2:3], min(rev, 4))]:
+        sl_ = slice(t0, t0 + n)
+        xd, md, dd, rd = x[sl_].view(1, n, Cx), m[:, sl_].reshape(1, 1, n, Cx), dout[:, sl_].reshape(1, 1, n, Cx), dev_i32([nrev])
+        assert same(out[:, sl_], lerp_fwd_abi(lib, xd, maa, md, front, rd).view(1, n, Cx)), (t0, "out")
+        dxd, dmd, _ = lerp_bwd_abi(lib, xd, maa, md, front, rd, dd, 1)
+        assert same(dx[sl_], dxd.view(n, Cx)), (t0, "dx")
+        assert same(dm[:, sl_], dmd.view(1, n, Cx)), (t0, "dm")
+        terms.append(ddlerp_ref(xd, maa, md, front, rd, dd)[2].view(n, 1, Cx))
+    check_partials(part, torch.cat(terms), f"rev {rev} nparts {nparts} dmaa", range(T, nparts))
+
+
 # ---- autograd nodes ------------------------------------------------------------------------------------------------------------------
 def test_autograd_nodes_give_the_raw_calls_and_survive_a_second_backward(ops):
     from rwkv_lm_ext_amd.wkv import WKV_6_VARLEN_PAIR, WKV_6_VARLEN_REV, _sum_bf16
