@@ -93,7 +93,8 @@ def test_parity_bf16_every_surface(oracle, shim, B, T, H, decay_set):
 
 
 @pytest.mark.parametrize("decay_set", ["ramp", "stress"])
-@pytest.mark.parametrize("B,T,H", [(2, 1, 2), (1, 2, 1), (2, 17, 2), (3, 160, 2), (2, 1000, 2), (5, 64, 32)])
+@pytest.mark.parametrize("B,T,H", [(2, 1, 2), (1, 2, 1), (2, 17, 2), (3, 160, 2), (2, 1000, 2), (5, 64, 32),
+                                   (2, 16, 1), (1, 32, 1), (1, 33, 1)])      # one full staging batch, an even and an odd number of batches
 def test_fp32_flavour_vs_oracle(oracle, B, T, H, decay_set):
     from rwkv_lm_ext_amd import wkv6_op
     p = w5.problem(B, T, H, seed=7 + T, decay_set=decay_set)

@@ -235,6 +235,27 @@ def test_random_vs_oracle(ops, oracle, shape, io):
     assert max_norm_err(host(gu), og["gu_b"]) <= (F32_TOL if io == torch.float32 else PART_TOL)
 
 
+@pytest.mark.parametrize("T", [15, 16, 17, 31, 32, 33, 49])
+def test_exact_kernels_at_staging_batch_boundaries(ops, oracle, T):
+    """The exact kernels in fp32 I/O around the 16-token staging batch: one batch short of full, full and one over, an even and an odd
+    number of batches (the descending sweep then starts in either LDS buffer), with a per-sample initial state carried to s_out and gs."""
+    B, H = 2, 1
+    r, k, v, w, u, gy = rand_inputs(400 + T, B, T, H, "stress")
+    g = torch.Generator().manual_seed(T + 2)
+    s0 = (torch.randn(B, H, 64, 64, generator=g) * 0.5).to(torch.bfloat16).float().numpy()
+    f32 = torch.float32
+    d = [dev(x, f32) for x in (r, k, v, w, u, gy)]
+    s, s_out = dev(s0, f32), torch.empty(B, H, 64, 64, device="cuda")
+    yo, so = oracle.forward(r, k, v, w, u, s0, return_state=True)
+    check(ops.forward_ex(*d[:5], H, s0=s, s_out=s_out, algo="scan"), yo, f32, "y")
+    check(s_out, so, f32, "s_out")
+    og = oracle.backward(r, k, v, w, u, gy, s0)
+    gr, gk, gv, gw, gu, gs = ops.backward_ex(*d, H, s0=s, want_gs=True, algo="scan")
+    for n, t in (("gr", gr), ("gk", gk), ("gv", gv), ("gw", gw), ("gs", gs)):
+        check(t, og["gs_b" if n == "gs" else n], f32, n)
+    assert max_norm_err(host(gu), og["gu_b"]) <= F32_TOL
+
+
 def test_autograd_surface(ops, oracle):
     """WKV_6.apply / RUN_CUDA_RWKV6 / WKV_6STATE / infctx / WKV_6_BI: gradient tuple order and values."""
     from rwkv_lm_ext_amd.wkv import (RUN_CUDA_RWKV6, RUN_CUDA_RWKV6_BI, RUN_CUDA_RWKV6_INFCTX,
