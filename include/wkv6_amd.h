@@ -520,6 +520,36 @@ int rwkv6_sample_slots_fp16(int n_seq, int V, int ld, const void* logits, float*
                             const int* slot_out, const float* params, const float* u, int* tokens, float* logprob, void* stream);
 int rwkv6_sample_slots_fp32(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot,
                             const int* slot_out, const float* params, const float* u, int* tokens, float* logprob, void* stream);
+/* ---- sentence pooling on a packed batch (bf16, forward and backward; csrc/wkv6_pool.hip): RwkvForSequenceEmbedding.pooling
+ * (src/model_ext.py:1708-1738) without the padded [B,T,C] tensor.
+ *   x bf16 [total_T,C], C a multiple of 8;  cu_seqlens int32 [n_seq + 1] and actual_len int32 [n_seq] (or NULL) on the device, never read
+ *   by the host;  out bf16 [n_seq,C];  backward: gout bf16 [n_seq,C], gx bf16 [total_T,C].
+ * Sequence s, every cu_seqlens entry clamped into [0, total_T] first (cu = the clamped values):
+ *     len_s = clamp(cu[s+1] - cu[s], 0, total_T - cu[s]);   a_s = clamp(actual_len[s], 0, len_s - 1), with actual_len NULL a_s = len_s - 1
+ * (a_s is the row's position of the first emb_id token, as the reference's argmax gives it), x_t = x[cu[s] + t].  fp32 arithmetic, one
+ * rounding to bf16 at the end:
+ *     WKV6_POOL_WEIGHTEDMEAN   out[s] = ( sum_{t = 0 .. a_s} (t + 1) x_t ) / a_s / a_s        (the emb_id token included, as the reference)
+ *     WKV6_POOL_AVG            out[s] = ( sum_{t < a_s} x_t ) / a_s
+ *     WKV6_POOL_LASTTOKEN      out[s] = x[cu[s] + a_s]                                        (a copy: bit-exact)
+ * a_s == 0 gives a NaN row for the two means (0 / 0, as the dense function does); an empty sequence (len_s == 0) gives a +0 row.  Rows of
+ * x outside every sequence, and rows of a sequence past a_s (for WKV6_POOL_AVG: from a_s on), are never read: a NaN there reaches nothing
+ * (the dense function multiplies it by a zero weight).
+ * backward: gx[cu[s] + t] = bf16(weight_t gout[s]) with the forward's weights -- (t + 1) / a_s / a_s for t <= a_s, 1 / a_s for t < a_s,
+ * the copy of gout[s] at t == a_s; the weighted mean's row of a sequence with a_s == 0 gets NaN.  EVERY row of gx is written (the caller
+ * passes uninitialised memory): rows outside every sequence, rows of a sequence that the forward did not sum and every row of an empty
+ * sequence get +0.  A row finds its sequence by the varlen rule (the last s with cu_seqlens[s] <= row).
+ * Every index is clamped or compared before an address is formed from it: garbage in either int array touches no memory outside the
+ * arguments.  One launch each, stream-ordered, capturable, no workspace, no atomics: the order of a sequence's token sum depends on the
+ * token's index in the sequence alone (four interleaved partial sums, added in a fixed order), so the same call gives the same bits every
+ * time and a sequence's row has the same bits alone or in a batch, wherever it lies in x.
+ * Refused before any launch, in this order: (1) WKV6_EINVAL -- total_T or n_seq < 1, C < 8 or no multiple of 8, an unknown kind;
+ * (2) WKV6_EUNSUPPORTED -- total_T > INT_MAX, n_seq * ceil(C / 512) > INT_MAX; (3) WKV6_ENULL -- a NULL cu_seqlens, x / gout or out / gx
+ * (actual_len may be NULL); (4) WKV6_EINVAL -- x / gout or out / gx not 16-byte aligned, cu_seqlens or actual_len not 4-byte aligned. */
+enum { WKV6_POOL_WEIGHTEDMEAN = 0, WKV6_POOL_LASTTOKEN = 1, WKV6_POOL_AVG = 2 };
+int wkv6_pool_packed_forward(long total_T, int n_seq, int C, int kind, const int* cu_seqlens, const int* actual_len,
+                             const void* x, void* out, void* stream);
+int wkv6_pool_packed_backward(long total_T, int n_seq, int C, int kind, const int* cu_seqlens, const int* actual_len,
+                              const void* gout, void* gx, void* stream);
 /* gn_gate (src/model.py:462-468): out = GroupNorm_H(y; gamma, beta, eps) * g on rows of C = 64 H channels (nn.GroupNorm(H, C)
  * applied to [rows, C]); stats fp32 [rows,H,2] (mean, rstd) is written for the backward (may be NULL in inference).
  * backward: dy, dg [rows,C]; dgamma_part, dbeta_part fp32 [nparts,C] partial sums. */

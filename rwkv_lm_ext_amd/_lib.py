@@ -75,6 +75,8 @@ SIGNATURES = {
     "rwkv6_sample_slots_bf16": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
     "rwkv6_sample_slots_fp16": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
     "rwkv6_sample_slots_fp32": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
+    "wkv6_pool_packed_forward": (_I, [_L] + [_I] * 3 + [_VP] * 5),
+    "wkv6_pool_packed_backward": (_I, [_L] + [_I] * 3 + [_VP] * 5),
     "wkv6_ddlerp_forward": (_I, [_I] * 4 + [_VP] * 6),
     "wkv6_ddlerp_backward": (_I, [_I] * 4 + [_VP] * 8 + [_I, _VP]),
     "wkv6_ddlerp_rev_forward": (_I, [_I] * 4 + [_VP] * 7),
@@ -104,6 +106,7 @@ SIGNATURES_WKV5 = {
 # flags of include/wkv6_amd.h
 W_EW_F32, W_RAW, IO_F32, S0_PER_BATCH, ALGO_SCAN, CKPT_VALID, BI_KEEP_CKPT, PARTIALS_F32 = 0, 1, 2, 4, 16, 32, 64, 128
 REV_R, REV_K, REV_V, REV_W, REV_Y, REV_ALL = 1, 2, 4, 8, 16, 31      # wkv6_*_rev_ex: tensors held in reversed order
+POOL_KINDS = {"weightedmean": 0, "lasttoken": 1, "avg": 2}           # WKV6_POOL_* of wkv6_pool_packed_*
 
 EUNSUPPORTED = -4
 ERRORS = {-1: "WKV6_EINVAL (shape: need C == H*64 and B,T,C,H >= 1)", -2: "WKV6_ENULL (null pointer)",

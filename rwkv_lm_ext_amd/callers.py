@@ -10,6 +10,7 @@ Parameter names equal the reference's state_dict keys, so a reference checkpoint
   Tmix_x060.forward_bi_b   composition B: WKV(r,k,v,w,u) + unrev(WKV(r, rev k, rev v, w, u)), src/model_bi.py:325-350  SURVEY a16
   BiBlock / RwkvEncoder    src/model_encoder_run.py:222-348 (encoder with sentence embedding at the first emb_id)  SURVEY a15
   pooling / info_nce_loss  src/model_ext.py:1708-1738, 1882-1911                                       SURVEY a17
+  pooling_packed           the same pooling on a packed batch (HIP kernels of mix_op.pool_packed, or an eager restatement)
 
 The WKV call itself is `wkv(B, T, C, H, r, k, v, w, u) -> y` (default: rwkv_lm_ext_amd.wkv.RUN_CUDA_RWKV6, the HIP
 kernels; bf16 on the GPU); on a packed variable-length batch (forward(x, cu_seqlens=...)) it is the second hook
@@ -468,6 +469,58 @@ def pooling(x, actual_len, pooling_type="weightedmean"):
         mask = (torch.arange(T, device=x.device).unsqueeze(0) < actual_len.unsqueeze(1)).to(x.dtype)
         return (torch.sum(x * mask.unsqueeze(-1), dim=1) / actual_len.unsqueeze(1).float()).bfloat16()
     raise ValueError(pooling_type)
+
+
+def _pool_kernel(x, cu_seqlens, actual_len, kernels):
+    """Whether mix_op.pool_packed serves this call (kernels as in infctx._sample_kernel: None where it applies, False never, True it
+    must -- then mix_op says what is wrong)."""
+    if kernels is False:
+        return False
+    if kernels:
+        return True
+    def ints(t):
+        return isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and t.device == x.device
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[-1] % 8 == 0 and x.data_ptr() % 16 == 0
+            and ints(cu_seqlens) and (actual_len is None or ints(actual_len)))
+
+
+def pooling_packed(x, cu_seqlens, actual_len=None, pooling_type="weightedmean", kernels=None):
+    """`pooling` on a packed batch x [1,total_T,C] (or [total_T,C]) -> [n_seq,C]: sequence s holds rows cu_seqlens[s] .. cu_seqlens[s+1]-1
+    and is pooled at a_s = clamp(actual_len[s], 0, len_s - 1) (actual_len None: its last token), its position of the first emb_id token.
+    The operation is stated in include/wkv6_amd.h (wkv6_pool_packed_forward): fp32 sums rounded once -- to bf16 for the two means, as the
+    dense function returns them; "lasttoken" is a copy in the type of x --, a NaN row where a_s == 0, a zero row for an empty sequence,
+    and rows outside every sequence or past a_s are never read (the dense function multiplies them by zero: NaN * 0).
+    kernels: None = the HIP kernels (mix_op.pool_packed) where they apply -- contiguous bf16 x on the GPU, contiguous int32 arrays on its
+    device --, else the eager restatement below (CPU, fp32, fp16; differentiable by autograd; on the GPU its index_add sums in no fixed
+    order); False = always eager; True = the kernels or their error.  Neither path reads the int arrays on the host."""
+    if pooling_type not in ("weightedmean", "lasttoken", "avg"):
+        raise ValueError(pooling_type)
+    if _pool_kernel(x, cu_seqlens, actual_len, kernels):
+        from . import mix_op
+        return mix_op.pool_packed(x, cu_seqlens, actual_len, pooling_type)
+    C = x.shape[-1]
+    x2 = x.reshape(-1, C)
+    T, n_seq = x2.shape[0], cu_seqlens.numel() - 1
+    cu = cu_seqlens.long().clamp(0, T)
+    start = cu[:-1]
+    length = (cu[1:] - start).clamp_min(0)
+    a = length - 1 if actual_len is None else torch.minimum(actual_len.long().clamp_min(0), length - 1)
+    if pooling_type == "lasttoken":
+        row = x2[(start + a).clamp(0, T - 1)]
+        return torch.where((length > 0).unsqueeze(1), row, torch.zeros_like(row))
+    pos = torch.arange(T, device=x.device)
+    seq = torch.searchsorted(cu_seqlens.long()[:-1].contiguous(), pos, right=True) - 1        # the last s with cu_seqlens[s] <= row
+    at = seq.clamp_min(0)
+    t = pos - start[at]
+    n = a + 1 if pooling_type == "weightedmean" else a                                        # tokens 0 .. n - 1 are summed
+    summed = (seq >= 0) & (t >= 0) & (t < length[at]) & (t < n[at])
+    weight = (t + 1).float() if pooling_type == "weightedmean" else torch.ones(T, device=x.device)
+    terms = torch.where(summed.unsqueeze(1), x2.float() * weight.unsqueeze(1), torch.zeros((), device=x.device))
+    total = torch.zeros(n_seq, C, device=x.device).index_add(0, at, terms)
+    fa = a.clamp_min(1).float().unsqueeze(1)
+    out = total / fa / fa if pooling_type == "weightedmean" else total / fa
+    out = out * torch.where(a == 0, float("nan"), 1.0).to(out).unsqueeze(1)                  # 0 / 0; the gradient of such a row is NaN too
+    return torch.where((length > 0).unsqueeze(1), out, torch.zeros((), device=x.device)).bfloat16()
 
 
 def cos_sim(a, b):

@@ -336,6 +336,56 @@ def sample_slots(logits, occ_pool, slots, params, u, out_slots=None, want_logpro
     return (tokens, logprob) if want_logprob else tokens
 
 
+# ---- sentence pooling on a packed batch (include/wkv6_amd.h: wkv6_pool_packed_*); bf16, GPU, with a backward.  Shapes and types are judged
+# first, the device last (there is no CPU path here: callers.pooling_packed has the eager one).
+class _PoolPacked(torch.autograd.Function):
+    """out [n_seq,C] of x [total_T,C] (checked by pool_packed); gx is written whole by the backward kernel, the +0 rows included."""
+
+    @staticmethod
+    def forward(ctx, x, cu_seqlens, actual_len, kind):
+        C = x.shape[-1]
+        total, n_seq = x.numel() // C, cu_seqlens.numel() - 1
+        out = torch.empty((n_seq, C), device=x.device, dtype=x.dtype)
+        _call("wkv6_pool_packed_forward", "pool packed forward", x.device, total, n_seq, C, kind, *_ptrs(cu_seqlens, actual_len, x, out))
+        ctx.save_for_backward(cu_seqlens, actual_len)
+        ctx.kind, ctx.shape = kind, x.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        cu_seqlens, actual_len = ctx.saved_tensors
+        gout = _require(gout, "gout")
+        C = ctx.shape[-1]
+        gx = torch.empty(ctx.shape, device=gout.device, dtype=gout.dtype)
+        _call("wkv6_pool_packed_backward", "pool packed backward", gout.device, gx.numel() // C, cu_seqlens.numel() - 1, C, ctx.kind,
+              *_ptrs(cu_seqlens, actual_len, gout, gx))
+        return gx, None, None, None
+
+
+def pool_packed(x, cu_seqlens, actual_len=None, kind="weightedmean"):
+    """One vector per sequence of the packed bf16 batch x [1,total_T,C] (or [total_T,C], C a multiple of 8) -> bf16 [n_seq,C]: kind
+    "weightedmean", "lasttoken" or "avg" of RwkvForSequenceEmbedding.pooling at a_s = clamp(actual_len[s], 0, len_s - 1) (actual_len int32
+    [n_seq]: the position of the sequence's first emb_id token; None: its last token); the operation, its clamping rule and the rows the
+    backward writes as +0 are stated in include/wkv6_amd.h.  Nothing is read on the host."""
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16 and x.dim() in (2, 3)):
+        raise RuntimeError("x must be a bf16 tensor [1, total_T, C] (or [total_T, C])")
+    if x.dim() == 3 and x.shape[0] != 1:
+        raise RuntimeError("a packed batch is [1, total_T, C] (or [total_T, C])")
+    C = x.shape[-1]
+    if C < 8 or C % 8 or x.numel() < C:
+        raise RuntimeError(f"pool_packed: C must be a multiple of 8 and total_T >= 1, got x {list(x.shape)}")
+    if kind not in _lib.POOL_KINDS:
+        raise RuntimeError(f"pool_packed: kind must be one of {sorted(_lib.POOL_KINDS)}, got {kind!r}")
+    n_seq = _ints(cu_seqlens, _AT_LEAST_2, None, _CU_SEQLENS).numel() - 1
+    if actual_len is not None:
+        _check_ints(actual_len, (n_seq,), "actual_len")
+    if not x.is_cuda:
+        raise RuntimeError("x must be on the GPU (pool_packed has no CPU path: callers.pooling_packed has the eager one)")
+    if cu_seqlens.device != x.device or (actual_len is not None and actual_len.device != x.device):
+        raise RuntimeError("cu_seqlens and actual_len must be on the device of x")
+    return _PoolPacked.apply(x.contiguous(), cu_seqlens, actual_len, _lib.POOL_KINDS[kind])
+
+
 def gn_gate_forward(y, g, gamma, beta, H, eps):
     """(out, stats): out = GroupNorm_H(y) * g on [rows, C]; stats fp32 [rows, H, 2] = mean, rstd (for gn_gate_backward)."""
     y, g, gamma, beta = _require(y, "y"), _require(g, "g"), _require(gamma, "gamma"), _require(beta, "beta")

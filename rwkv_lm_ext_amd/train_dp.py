@@ -109,19 +109,23 @@ def inject_lora(model: nn.Module, targets: Sequence[str] = ("ffn.key", "ffn.valu
 class Block(nn.Module):
     """Causal RWKV-6 block (src/model.py:904-933 without dropout / tiny-att): x + att(ln1 x), x + ffn(ln2 x)."""
 
-    def __init__(self, n_embd, dim_att, dim_ffn, layer_id, wkv=None):
+    def __init__(self, n_embd, dim_att, dim_ffn, layer_id, wkv=None, wkv_varlen=None):
         super().__init__()
         self.layer_id = layer_id
         self.ln1 = nn.LayerNorm(n_embd)
         self.ln2 = nn.LayerNorm(n_embd)
         if layer_id == 0:
             self.ln0 = nn.LayerNorm(n_embd)
-        self.att = callers.Tmix_x060(n_embd, dim_att, wkv=wkv)
+        self.att = callers.Tmix_x060(n_embd, dim_att, wkv=wkv, wkv_varlen=wkv_varlen)
         self.ffn = callers.CMix_x060(n_embd, dim_ffn)
 
-    def forward(self, x):
+    def forward(self, x, cu_seqlens=None, max_seqlen=None):
+        """cu_seqlens (int32 [n_seq + 1] on the device of x) / max_seqlen: x is a packed batch [1,total_T,C] (callers.Tmix_x060.forward)."""
         if self.layer_id == 0:
             x = self.ln0(x)
+        if cu_seqlens is not None:
+            x = x + self.att(self.ln1(x), cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+            return x + self.ffn(self.ln2(x), cu_seqlens=cu_seqlens)
         x = x + self.att(self.ln1(x))
         return x + self.ffn(self.ln2(x))
 
@@ -131,33 +135,50 @@ class SequenceEmbedder(nn.Module):
     first `emb_id` token -> optional tanh(dense(.))."""
 
     def __init__(self, vocab_size, n_embd, n_layer, dim_att=None, dim_ffn=None, emb_id=1, pad_id=0,
-                 pooling_type="weightedmean", add_mlp=False, output_dim=0, grad_cp=False, wkv=None):
+                 pooling_type="weightedmean", add_mlp=False, output_dim=0, grad_cp=False, wkv=None, wkv_varlen=None):
         super().__init__()
         self.emb_id, self.pad_id, self.pooling_type, self.grad_cp = emb_id, pad_id, pooling_type, grad_cp
         self.emb = nn.Embedding(vocab_size, n_embd)
-        self.blocks = nn.ModuleList([Block(n_embd, dim_att or n_embd, dim_ffn or int(n_embd * 3.5) // 32 * 32, i, wkv=wkv)
-                                     for i in range(n_layer)])
+        self.blocks = nn.ModuleList([Block(n_embd, dim_att or n_embd, dim_ffn or int(n_embd * 3.5) // 32 * 32, i, wkv=wkv,
+                                           wkv_varlen=wkv_varlen) for i in range(n_layer)])
         self.ln_out = nn.LayerNorm(n_embd)
         self.dense = nn.Linear(n_embd, output_dim or n_embd) if add_mlp else None
 
-    def forward(self, idx):
+    def forward(self, idx, cu_seqlens=None, max_seqlen=None, actual_len=None):
+        """cu_seqlens (int32 [n_seq + 1] on the device of idx): idx is a packed batch [1,total_T] as pack_rows makes it -- the rows back to
+        back, each cut behind its first emb_id token -- with max_seqlen the longest row and actual_len (int32 [n_seq]) the emb_id token's
+        position in every row (None: the row's last token); one vector per sequence comes back, as from the padded rows.  Nothing of the
+        packed route reads the device."""
         x = self.emb(idx)
+        packed = {} if cu_seqlens is None else {"cu_seqlens": cu_seqlens, "max_seqlen": max_seqlen}
+        if packed:
+            assert idx.size(0) == 1, "a packed batch is [1,total_T]"
         for block in self.blocks:
             if self.grad_cp and self.training and torch.is_grad_enabled():   # args.grad_cp, src/model_ext.py:1756-1758
                 from torch.utils.checkpoint import checkpoint
-                x = checkpoint(block, x, use_reentrant=False)
+                x = checkpoint(block, x, use_reentrant=False, **packed)
             else:
-                x = block(x)
+                x = block(x, **packed)
         x = self.ln_out(x)
-        actual_len = torch.eq(idx, self.emb_id).int().argmax(-1)
-        x = callers.pooling(x, actual_len, self.pooling_type)
+        if packed:
+            x = callers.pooling_packed(x, cu_seqlens, actual_len, self.pooling_type)
+        else:
+            actual_len = torch.eq(idx, self.emb_id).int().argmax(-1)
+            x = callers.pooling(x, actual_len, self.pooling_type)
         if self.dense is not None:
             x = torch.tanh(self.dense(x.to(self.dense.weight.dtype)))   # pooling returns bf16 (src/model_ext.py:1721)
         return x
 
 
-def training_loss(model: nn.Module, query, positive, negative=None):
-    """RwkvForSequenceEmbedding.training_step with is_in_batch_negative (src/model_ext.py:1882-1911)."""
+def training_loss(model: nn.Module, query, positive=None, negative=None):
+    """RwkvForSequenceEmbedding.training_step with is_in_batch_negative (src/model_ext.py:1882-1911).  `query` may be a packed batch (a
+    dict of batches(packed=True): the query, positive and negative rows of the step in one packed idx); positive and negative are then
+    not used."""
+    if isinstance(query, dict):
+        p = query
+        emb = model(p["idx"], cu_seqlens=p["cu_seqlens"], max_seqlen=p["max_seqlen"], actual_len=p["actual_len"]).float()
+        bs = p["bs"]
+        return callers.info_nce_loss(emb[:bs], emb[bs:2 * bs], emb[2 * bs:] if emb.size(0) > 2 * bs else None)
     parts = [query, positive] + ([negative] if negative is not None else [])
     emb = model(torch.cat(parts, dim=0)).float()
     bs = query.size(0)
@@ -198,20 +219,49 @@ def synth_example(index: int, seq_len: int, vocab_size: int, emb_id: int = 1, pa
     return out
 
 
-def batches(sampler: BucketBatchSampler, seq_len: int, vocab_size: int) -> Iterable[dict]:
+def pack_rows(idx, emb_id: int = 1, total_multiple: int = 1, pad_id: int = 0):
+    """The padded rows idx [B, T] (a host tensor, where the loader's batches live) as one packed batch: (idx [1, total_T], cu_seqlens int32
+    [B + 1], max_seqlen int, actual_len int32 [B]).  Row b keeps its tokens 0 .. a_b inclusive, a_b = the position of its first emb_id
+    (argmax semantics: a row without emb_id keeps one token, a_b = 0, and pools to what the dense path gives it); actual_len = a.
+    total_multiple > 1 rounds total_T up to a multiple of it with pad_id rows behind the last sequence that belong to none
+    (cu_seqlens[-1] < total_T): the packed operators never read such rows and write their outputs and gradients as +0
+    (include/wkv6_amd.h, "rows outside every sequence"), and a run sees at most T B / total_multiple distinct GEMM shapes."""
+    assert idx.dim() == 2 and total_multiple >= 1
+    a = torch.eq(idx, emb_id).int().argmax(-1)
+    keep = torch.arange(idx.size(1)).unsqueeze(0) <= a.unsqueeze(1)
+    lens = a + 1
+    cu = F.pad(lens.cumsum(0), (1, 0)).to(torch.int32)
+    flat = idx[keep]
+    total = -(-flat.numel() // total_multiple) * total_multiple
+    flat = F.pad(flat, (0, total - flat.numel()), value=pad_id)
+    return flat.unsqueeze(0), cu, int(lens.max()), a.to(torch.int32)
+
+
+def batches(sampler: BucketBatchSampler, seq_len: int, vocab_size: int, packed: bool = False, total_multiple: int = 1) -> Iterable[dict]:
+    """packed: one packed batch per step instead of three padded ones -- the query, then the positive, then the negative rows through
+    pack_rows, with "bs" (rows per part) recorded; training_loss and train_steps take it as it is."""
     for idxs in sampler:
         rows = [synth_example(i, seq_len, vocab_size) for i in idxs]
+        if packed:
+            idx, cu, max_seqlen, actual_len = pack_rows(torch.stack([r[j] for j in range(3) for r in rows]), total_multiple=total_multiple)
+            yield {"idx": idx, "cu_seqlens": cu, "max_seqlen": max_seqlen, "actual_len": actual_len, "bs": len(rows)}
+            continue
         yield {"query": torch.stack([r[0] for r in rows]), "positive": torch.stack([r[1] for r in rows]),
                "negative": torch.stack([r[2] for r in rows])}
+
+
+def to_device(batch: dict, device) -> dict:
+    """The tensors of a batch of batches() on `device`; the ints of a packed batch (max_seqlen, bs) stay host ints."""
+    return {k: v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
 
 
 def train_steps(model, opt, batch_iter, device, steps: int):
     """`steps` optimizer steps; returns the losses.  `model` is the DDP-wrapped SequenceEmbedder."""
     losses = []
     for _, batch in zip(range(steps), batch_iter):
-        batch = {k: v.to(device, non_blocking=True) for k, v in batch.items()}
+        batch = to_device(batch, device)
         opt.zero_grad(set_to_none=True)
-        loss = training_loss(model, batch["query"], batch["positive"], batch.get("negative"))
+        loss = training_loss(model, batch) if "idx" in batch else training_loss(model, batch["query"], batch["positive"], batch.get("negative"))
         loss.backward()              # DDP all-reduces the LoRA gradients here
         opt.step()
         losses.append(loss.detach())
