@@ -550,6 +550,53 @@ int wkv6_pool_packed_forward(long total_T, int n_seq, int C, int kind, const int
                              const void* x, void* out, void* stream);
 int wkv6_pool_packed_backward(long total_T, int n_seq, int C, int kind, const int* cu_seqlens, const int* actual_len,
                               const void* gout, void* gx, void* stream);
+/* ---- LM-head cross-entropy with L2Wrap on rows of logits (forward and backward; csrc/wkv6_ce.hip): what every language-model training step
+ * of the reference does behind head(ln_out(x)) -- F.cross_entropy(logits.view(-1, V), targets.view(-1)), then L2Wrap.apply(loss, logits)
+ * (src/model.py:937-974, 1244-1283) -- as one pass for the statistics and one for the gradient, no [n_rows, V] tensor besides the logits.
+ *   logits [n_rows,ld] in the entry point's type, only columns < V count (ld >= V, ld % 8 == 0, V >= 1 with no upper limit: a padded head);
+ *   targets int64 [n_rows] on the device, as torch holds them; -100 means the row is ignored;
+ *   loss_row, lse, zmax fp32 [n_rows], imax int32 [n_rows];  ce_scale, l2_scale fp32 [n_rows] on the device;  glogits [n_rows,ld_g] in the
+ *   type of the logits (ld_g >= V, ld_g % 8 == 0).
+ * All arithmetic is fp32, rows are independent of each other.  Forward, row r with z = its V logits:
+ *     zmax[r] = max_n z[n];   imax[r] = the lowest n that attains it (torch.max leaves ties open; this rule closes them);
+ *     lse[r] = zmax + log(sum_n exp(z[n] - zmax));   loss_row[r] = lse[r] - z[target], +0 for an ignored row.
+ * Backward, row r and column n < V, rounded once to the type of the logits:
+ *     g[r,n] = ce_scale[r] * (exp(z[n] - lse[r]) - [n == target]) + l2_scale[r] * zmax[r] * [n == imax[r]]
+ * An ignored row has no cross-entropy term, whatever ce_scale says.  A row that is ignored with l2_scale[r] == 0 is written as +0 without
+ * its logits being read: a NaN there reaches nothing, by the rule of "rows outside every sequence" above (the fused forward does not read
+ * such a row either and reports lse = zmax = +0, imax = 0 for it).  EVERY column < V of every row of g is written (the caller passes
+ * uninitialised memory); columns >= V are never used and never written (the 16-byte load of a row's last chunk covers them, masked by
+ * lane, never multiplied by zero).  glogits may be the logits buffer itself (in place, ld_g == ld): that is a defined use.
+ * A target other than -100 outside [0, V): loss_row and the whole gradient row are NaN, no address is formed from the target, the row's
+ * lse, zmax, imax are what its logits give, and its neighbours are unaffected.
+ * Non-finite logits follow fp32 arithmetic: a -inf logit has p = 0.  A row with a NaN, a +inf or no finite logit has lse = NaN, hence a
+ * NaN loss (+0 when it is ignored) and a NaN gradient row (unless it is ignored with l2_scale == 0), for that row alone; the zmax and
+ * imax of a row with a NaN are taken over its other logits.
+ * One launch, one workgroup per row, stream-ordered, capturable, no workspace, no atomics: the order of a row's sum depends on V and the
+ * thread layout alone, so the same call gives the same bits every time and a row has the same bits alone or in a batch.
+ * wkv6_ce_rows_forward_*: glogits == NULL is statistics only (ce_scale, l2_scale, ld_g are then not looked at); a non-NULL glogits writes
+ * the gradient in the same launch -- the fused mode of a chunked head, which knows its scales before it has any loss --, bit-identical
+ * to the forward followed by wkv6_ce_rows_backward_* on what it stored.
+ * Refused before any launch, in this order: (1) WKV6_EINVAL -- n_rows or V < 1, ld < V or ld % 8, with a gradient ld_g < V or ld_g % 8;
+ * (2) WKV6_EUNSUPPORTED -- n_rows > INT_MAX; (3) WKV6_ENULL -- a NULL logits, targets, lse, zmax, imax or (forward) loss_row, with a
+ * gradient a NULL ce_scale or l2_scale, in the backward a NULL glogits; (4) WKV6_EINVAL -- logits or glogits not 16-byte aligned, targets
+ * not 8-byte aligned, any other array that the call looks at not 4-byte aligned, glogits overlapping logits in any way but the in-place
+ * one. */
+int wkv6_ce_rows_forward_bf16(long n_rows, int V, long ld, const void* logits, const long long* targets, float* loss_row, float* lse,
+                              float* zmax, int* imax, const float* ce_scale, const float* l2_scale, void* glogits, long ld_g, void* stream);
+int wkv6_ce_rows_forward_fp16(long n_rows, int V, long ld, const void* logits, const long long* targets, float* loss_row, float* lse,
+                              float* zmax, int* imax, const float* ce_scale, const float* l2_scale, void* glogits, long ld_g, void* stream);
+int wkv6_ce_rows_forward_fp32(long n_rows, int V, long ld, const void* logits, const long long* targets, float* loss_row, float* lse,
+                              float* zmax, int* imax, const float* ce_scale, const float* l2_scale, void* glogits, long ld_g, void* stream);
+int wkv6_ce_rows_backward_bf16(long n_rows, int V, long ld, const void* logits, const long long* targets, const float* lse,
+                               const float* zmax, const int* imax, const float* ce_scale, const float* l2_scale, void* glogits, long ld_g,
+                               void* stream);
+int wkv6_ce_rows_backward_fp16(long n_rows, int V, long ld, const void* logits, const long long* targets, const float* lse,
+                               const float* zmax, const int* imax, const float* ce_scale, const float* l2_scale, void* glogits, long ld_g,
+                               void* stream);
+int wkv6_ce_rows_backward_fp32(long n_rows, int V, long ld, const void* logits, const long long* targets, const float* lse,
+                               const float* zmax, const int* imax, const float* ce_scale, const float* l2_scale, void* glogits, long ld_g,
+                               void* stream);
 /* gn_gate (src/model.py:462-468): out = GroupNorm_H(y; gamma, beta, eps) * g on rows of C = 64 H channels (nn.GroupNorm(H, C)
  * applied to [rows, C]); stats fp32 [rows,H,2] (mean, rstd) is written for the backward (may be NULL in inference).
  * backward: dy, dg [rows,C]; dgamma_part, dbeta_part fp32 [nparts,C] partial sums. */

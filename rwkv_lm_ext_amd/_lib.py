@@ -77,6 +77,12 @@ SIGNATURES = {
     "rwkv6_sample_slots_fp32": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
     "wkv6_pool_packed_forward": (_I, [_L] + [_I] * 3 + [_VP] * 5),
     "wkv6_pool_packed_backward": (_I, [_L] + [_I] * 3 + [_VP] * 5),
+    "wkv6_ce_rows_forward_bf16": (_I, [_L, _I, _L] + [_VP] * 9 + [_L, _VP]),
+    "wkv6_ce_rows_forward_fp16": (_I, [_L, _I, _L] + [_VP] * 9 + [_L, _VP]),
+    "wkv6_ce_rows_forward_fp32": (_I, [_L, _I, _L] + [_VP] * 9 + [_L, _VP]),
+    "wkv6_ce_rows_backward_bf16": (_I, [_L, _I, _L] + [_VP] * 8 + [_L, _VP]),
+    "wkv6_ce_rows_backward_fp16": (_I, [_L, _I, _L] + [_VP] * 8 + [_L, _VP]),
+    "wkv6_ce_rows_backward_fp32": (_I, [_L, _I, _L] + [_VP] * 8 + [_L, _VP]),
     "wkv6_ddlerp_forward": (_I, [_I] * 4 + [_VP] * 6),
     "wkv6_ddlerp_backward": (_I, [_I] * 4 + [_VP] * 8 + [_I, _VP]),
     "wkv6_ddlerp_rev_forward": (_I, [_I] * 4 + [_VP] * 7),

@@ -11,6 +11,8 @@ Parameter names equal the reference's state_dict keys, so a reference checkpoint
   BiBlock / RwkvEncoder    src/model_encoder_run.py:222-348 (encoder with sentence embedding at the first emb_id)  SURVEY a15
   pooling / info_nce_loss  src/model_ext.py:1708-1738, 1882-1911                                       SURVEY a17
   pooling_packed           the same pooling on a packed batch (HIP kernels of mix_op.pool_packed, or an eager restatement)
+  lm_loss / head_loss      src/model.py:937-974, 1244-1283 (F.cross_entropy + L2Wrap behind the LM head; HIP kernels of mix_op.ce_rows,
+                           or an eager restatement); head_loss walks the head in row chunks and never holds [rows, V]
 
 The WKV call itself is `wkv(B, T, C, H, r, k, v, w, u) -> y` (default: rwkv_lm_ext_amd.wkv.RUN_CUDA_RWKV6, the HIP
 kernels; bf16 on the GPU); on a packed variable-length batch (forward(x, cu_seqlens=...)) it is the second hook
@@ -541,6 +543,190 @@ def info_nce_loss(query, positive, negative=None, scale=20.0):
         scores = torch.cat([scores, pairwise_cos_sim(query, negative).unsqueeze(1) * scale], dim=1)
     labels = torch.arange(scores.shape[0], dtype=torch.long, device=scores.device)
     return F.cross_entropy(scores, labels)
+
+
+# ---- the LM head's loss: F.cross_entropy + L2Wrap (src/model.py:937-974, 1244-1283) ------------------------------------------------
+# What kernels=None means for lm_loss where the kernels apply (profiles/ce_rows_time.txt, measured at V = 65536 only): the two launches
+# behind autograd beat torch's own cross-entropy + L2Wrap 3.3x at 4096 rows and 3.65x at 49152 rows, and lose 1.4x at 256 rows, where
+# both are bound by the host's launches and this path makes more of them.  None takes the kernels from the smallest size at which they
+# were measured faster, counted in logits.  Where the crossover lies between 256 and 4096 rows, and where it lies for another V -- the
+# host's cost goes with the calls, not with the elements -- is not measured.  (head_loss runs the fused launch per chunk, which was
+# faster than torch at every size measured: 4.0x at 256 rows.)
+CE_KERNELS_FROM = 4096 * 65536
+
+
+class _L2Wrap(torch.autograd.Function):
+    """The reference's L2Wrap (src/model.py:937-974): the loss passes through; in the backward every row of the logits gets factor * max
+    at its argmax, NOT multiplied by the incoming gradient.  factor: a float or a 0-d tensor; rows (a [rows] tensor or None) weights it."""
+
+    @staticmethod
+    def forward(ctx, loss, y, factor, rows):
+        ctx.save_for_backward(y, rows)
+        ctx.factor = factor
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        y, rows = ctx.saved_tensors
+        maxx, ids = torch.max(y, -1, keepdim=True)
+        gy = torch.zeros_like(y)
+        term = maxx * ctx.factor
+        if rows is not None:
+            term = term * rows.to(term.dtype).view(term.shape)
+        gy.scatter_(-1, ids, term.to(y.dtype))
+        return grad_output, gy, None, None
+
+
+def _l2_factor(l2wrap, rows, token_amount):
+    """l2wrap / (B * T), or l2wrap / token_amount (the infctx form; a device tensor stays one); None: the term is off."""
+    if not l2wrap or (not isinstance(token_amount, torch.Tensor) and token_amount == 0):
+        return None
+    return l2wrap / (rows if token_amount is None else token_amount)
+
+
+_CE_TYPES = (torch.bfloat16, torch.float16, torch.float32)
+
+
+def _ce_kernel(z, targets, kernels):
+    """Whether mix_op.ce_rows serves logits rows z [rows, V] (kernels as in _pool_kernel): under None, where mix_op would accept them --
+    its dtype, layout, alignment and device tests -- and the size is one at which the kernels were measured faster."""
+    if kernels is False:
+        return False
+    if kernels:
+        return True
+    if not (z.is_cuda and z.dtype in _CE_TYPES and z.shape[0] * z.shape[1] >= CE_KERNELS_FROM and z.stride(1) == 1):
+        return False
+    from . import mix_op
+    return (mix_op._ce_ld(z) is not None and z.data_ptr() % 16 == 0 and targets.dtype == torch.int64 and targets.device == z.device
+            and targets.is_contiguous())
+
+
+def _row_scales(targets, mask, factor, l2_rows):
+    """(ce_scale, l2_scale) fp32 [rows] of the final loss, from device data alone: the weight of every row's loss in
+    mean-over-non-ignored (or sum(loss * mask) / sum(mask)), and the L2 factor of every row."""
+    if mask is None:
+        valid = (targets != -100).float()
+        ce = valid / valid.sum()
+    else:
+        m = mask.reshape(-1).float()
+        ce = m / m.sum()
+    if factor is None:
+        l2 = torch.zeros_like(ce)
+    else:
+        l2 = torch.ones_like(ce) * factor
+        if l2_rows is not None:
+            l2 = l2 * l2_rows.reshape(-1).float()
+    return ce.contiguous(), l2.contiguous()
+
+
+def lm_loss(logits, targets, mask=None, l2wrap=1e-4, token_amount=None, kernels=None, l2_rows=None):
+    """The loss of the reference's training_step on logits [B,T,V] (or packed [total_T,V]) and int64 targets of the leading shape
+    (-100: the row is ignored): the mean of F.cross_entropy over the non-ignored rows, or with mask sum(loss * mask) / sum(mask) (my_qa_mask),
+    then L2Wrap: in the backward every row of the logits -- ignored ones included, as in the reference -- gets l2wrap / (B * T) * max at
+    its argmax, l2wrap / token_amount with token_amount (the infctx form; an int or a 0-d device tensor), not multiplied by the incoming
+    gradient.  l2wrap = 0 turns it off; l2_rows ([rows] of 0 / 1, or None) names the rows that take it.  Every count stays on the device.
+    kernels: None = the HIP kernels (mix_op.ce_rows: one pass for the statistics, one for the gradient, fp32 loss) where they apply and
+    were measured faster -- GPU, rows a multiple of 8 elements apart, at least CE_KERNELS_FROM logits --, else the eager three lines below (CPU; double backward; the loss in the type of the
+    logits); False = always eager; True = the kernels or their error."""
+    V = logits.shape[-1]
+    z, t = logits.reshape(-1, V), targets.reshape(-1)
+    factor = _l2_factor(l2wrap, z.shape[0], token_amount)
+    if _ce_kernel(z, t, kernels):
+        from . import mix_op
+        ce, l2 = _row_scales(t, mask, factor, l2_rows)
+        return (mix_op.ce_rows(z, t, None if factor is None else l2) * ce).sum()
+    if mask is None:
+        loss = F.cross_entropy(z, t)
+    else:
+        m = mask.reshape(-1)
+        loss = torch.sum(F.cross_entropy(z, t, reduction="none") * m) / torch.sum(m)
+    return loss if factor is None else _L2Wrap.apply(loss, logits, factor, l2_rows)
+
+
+def _ce_rows_grad_eager(z, t, ce, l2):
+    """mix_op.ce_rows_grad_ restated: (loss_row fp32, the gradient in the type of z) of a chunk z [n,V]."""
+    zf = z.float()
+    lse = torch.logsumexp(zf, -1)
+    valid = t != -100
+    at = t.clamp_min(0).unsqueeze(1)
+    loss = torch.where(valid, lse - zf.gather(1, at)[:, 0], torch.zeros_like(lse))
+    g = torch.exp(zf - lse.unsqueeze(1))
+    g.scatter_add_(1, at, -torch.ones_like(lse).unsqueeze(1))
+    g = g * (ce * valid).unsqueeze(1)
+    zmax, imax = zf.max(-1)
+    g.scatter_add_(1, imax.unsqueeze(1), (l2 * zmax).unsqueeze(1))
+    return loss, g.to(z.dtype)
+
+
+def _gw_gemm(g, x, out):
+    """out = g^T x [V,C]: the head's weight gradient of one chunk (a function of its own so that a test can count its calls)."""
+    return torch.mm(g.t(), x, out=out)
+
+
+class _HeadLoss(torch.autograd.Function):
+    """sum_r ce_scale[r] * loss_row[r] of the logits x W^T, walked in chunks of chunk_rows rows of x through one reused logits buffer:
+    GEMM, the fused cross-entropy kernel in place (the buffer then holds the chunk's logits gradient, final scales and all), gx = g W
+    where x takes a gradient, and gW += g^T x where W does: each chunk's product is one GEMM in the type of x (for bf16: fp32 sums inside
+    the GEMM, rounded to bf16 once, into one reused [V,C] buffer) and the chunks are added up in fp32.  The backward scales the stored
+    gradients by the incoming one."""
+
+    @staticmethod
+    def forward(ctx, x, weight, targets, ce, l2, chunk_rows, use_kernels):
+        rows, V = x.shape[0], weight.shape[0]
+        ld = (V + 7) // 8 * 8
+        buf = torch.empty((min(chunk_rows, rows), ld), device=x.device, dtype=x.dtype)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gW = torch.zeros(weight.shape, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        gW_chunk = None if gW is None else torch.empty_like(weight)             # one chunk's product, in the type of the GEMM
+        loss_rows = torch.empty(rows, device=x.device, dtype=torch.float32)
+        if use_kernels:
+            from . import mix_op
+        for a in range(0, rows, chunk_rows):
+            b = min(a + chunk_rows, rows)
+            z = buf[:b - a, :V]
+            torch.mm(x[a:b], weight.t(), out=z)
+            if use_kernels:
+                loss_rows[a:b] = mix_op.ce_rows_grad_(z, targets[a:b], ce[a:b], l2[a:b])
+            else:
+                loss_rows[a:b], g = _ce_rows_grad_eager(z, targets[a:b], ce[a:b], l2[a:b])
+                z.copy_(g)
+            if gx is not None:
+                torch.mm(z, weight, out=gx[a:b])
+            if gW is not None:
+                gW += _gw_gemm(z, x[a:b], gW_chunk)
+        ctx.save_for_backward(gx, gW)
+        ctx.wdtype = weight.dtype
+        return (loss_rows * ce).sum()
+
+    @staticmethod
+    def backward(ctx, gloss):
+        gx, gW = ctx.saved_tensors
+        return (None if gx is None else gx * gloss.to(gx.dtype), None if gW is None else (gW * gloss).to(ctx.wdtype), None, None, None,
+                None, None)
+
+
+def head_loss(x, weight, targets, mask=None, l2wrap=1e-4, token_amount=None, chunk_rows=4096, kernels=None, l2_rows=None):
+    """lm_loss(x @ weight.T, targets, ...) without ever holding the [rows, V] logits: x [.., C] is the hidden state behind ln_out, weight
+    [V, C] the bias-free head.  One autograd function walks x in chunks of chunk_rows rows; per chunk a logits GEMM into one reused buffer,
+    the fused cross-entropy kernel in place with the FINAL scales (they come from targets and mask alone, on the device), gx = g W, and
+    -- only if weight.requires_grad; a frozen head under LoRA skips that GEMM -- gW += g^T x, each chunk's product rounded to the type of
+    x by its GEMM and the chunks summed in fp32.  Peak extra memory: chunk_rows * ld elements of logits (ld = V rounded up to 8) plus gx
+    (plus, for a trainable head, an fp32 gW and one [V, C] chunk product).
+    The backward multiplies the stored gx (and gW) by the incoming scalar gradient.  That also scales the L2 term, which L2Wrap -- and
+    lm_loss -- leave unscaled: the two agree where the incoming gradient is 1, as at the loss.backward() of a training step, and differ
+    under loss scaling or gradient accumulation by division.  No double backward.
+    kernels: None = mix_op.ce_rows_grad_ on the GPU, an eager restatement of it per chunk elsewhere; False = always eager; True = the
+    kernel or its error."""
+    C = x.shape[-1]
+    x2, t = x.reshape(-1, C), targets.reshape(-1)
+    if weight.dim() != 2 or weight.shape[1] != C or weight.dtype != x.dtype:
+        raise RuntimeError(f"head_loss: weight must be [V, C = {C}] in the type of x")
+    if t.shape[0] != x2.shape[0] or chunk_rows < 1:
+        raise RuntimeError("head_loss: targets must have one entry per row of x, chunk_rows must be >= 1")
+    ce, l2 = _row_scales(t, mask, _l2_factor(l2wrap, x2.shape[0], token_amount), l2_rows)
+    # None: the fused kernel where mix_op.ce_rows_grad_ accepts the chunk (the buffer's layout is this function's own)
+    use = bool(kernels) if kernels is not None else (x.is_cuda and x.dtype in _CE_TYPES and t.dtype == torch.int64 and t.device == x.device)
+    return _HeadLoss.apply(x2, weight, t, ce, l2, int(chunk_rows), use)
 
 
 # ---- RWKV-5 time-mix (src/model.py:292-374) ------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 // 2^46 stay below 2^63.  The quantisation is 2^-46 of the largest weight per term.
 #include <cmath>
 #include "wkv6_sample.h"
+#include "wkv6_rows.h"                 // load8, load1
 #include "wkv6_host.h"                 // to_rc
 
 // the same expression must give the same bits wherever it is inlined (weights are formed once for W and once more for the draw)
@@ -27,35 +28,11 @@ namespace wkv6 {
 namespace {
 
 typedef unsigned long long u64;
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 constexpr int THREADS = 1024, WAVES = THREADS / 64;
 constexpr int PARTS = SAMPLE_MAX_V / 8 / 64;                  // 128: the chunks of 8 tokens come in blocks of 64 (one wave, one round)
 constexpr float FIX = 70368744177664.f;                      // 2^46
 constexpr float NEG_INF = -__builtin_inff();
-
-// ---- 8 consecutive elements of a row as fp32
-template <typename T> __device__ __forceinline__ void load8(const T* p, float (&x)[8]);
-template <> __device__ __forceinline__ void load8<float>(const float* p, float (&x)[8])
-{
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-}
-template <> __device__ __forceinline__ void load8<bf16_t>(const bf16_t* p, float (&x)[8])
-{
-    const v4u raw = *reinterpret_cast<const v4u*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { x[2 * i] = bf_lo(raw[i]); x[2 * i + 1] = bf_hi(raw[i]); }
-}
-template <> __device__ __forceinline__ void load8<f16_t>(const f16_t* p, float (&x)[8])
-{
-    typedef f16_t h8 __attribute__((ext_vector_type(8)));
-    const h8 raw = *reinterpret_cast<const h8*>(p);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x[i] = (float)raw[i];
-}
-template <typename T> __device__ __forceinline__ float load1(const T* p) { return (float)*p; }
-template <> __device__ __forceinline__ float load1<bf16_t>(const bf16_t* p) { return __uint_as_float((unsigned)*p << 16); }
 
 // ---- the monotone key of a (non-NaN) float: a > b  <=>  key(a) > key(b)
 __device__ __forceinline__ unsigned key_of(float z)

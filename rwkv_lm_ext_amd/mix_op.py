@@ -1,7 +1,8 @@
 """Fused elementwise neighbours of the WKV6 operator in the RWKV-6 blocks, served by librwkv6_amd.so
 (csrc/wkv6_mix.hip): the token-shift / data-dependent-lerp chain in front of the time-mix projections (src/model.py:435-448,
 SURVEY.md row n4), the per-head GroupNorm + gate behind the operator (src/model.py:462-468, row n1), and the elementwise glue of
-the channel-mix FFN (token shift + two lerps, squared ReLU, sigmoid gate: src/model.py:636-644).
+the channel-mix FFN (token shift + two lerps, squared ReLU, sigmoid gate: src/model.py:636-644); further down the packed serving and
+training pieces, the last of them the LM-head cross-entropy with L2Wrap (ce_rows, ce_rows_grad_: csrc/wkv6_ce.hip).
 
 bf16 GPU tensors only; like the operator itself there is no CPU path.  Each op is a torch.autograd.Function whose
 forward and backward are one HIP kernel each; parameter gradients come back as fp32 partial rows summed here."""
@@ -384,6 +385,103 @@ def pool_packed(x, cu_seqlens, actual_len=None, kind="weightedmean"):
     if cu_seqlens.device != x.device or (actual_len is not None and actual_len.device != x.device):
         raise RuntimeError("cu_seqlens and actual_len must be on the device of x")
     return _PoolPacked.apply(x.contiguous(), cu_seqlens, actual_len, _lib.POOL_KINDS[kind])
+
+
+# ---- LM-head cross-entropy with L2Wrap on rows of logits (include/wkv6_amd.h: wkv6_ce_rows_*); bf16, fp16 or fp32 on the GPU, with a
+# backward.  Shapes and types are judged first, the device last (there is no CPU path here: callers.lm_loss has the eager one).
+_CE_ENTRY = {torch.bfloat16: "bf16", torch.float16: "fp16", torch.float32: "fp32"}
+
+
+def _ce_ld(logits):
+    """The row stride the kernels take logits [n_rows, V] with (one row: V rounded up to 8), or None where the layout does not serve them:
+    rows ld elements apart, ld a multiple of 8 and >= V, every row readable up to the next multiple of 8 columns."""
+    n_rows, V = logits.shape
+    ld = logits.stride(0) if n_rows > 1 else (V + 7) // 8 * 8
+    return ld if ld >= V and ld % 8 == 0 and _rows_in_storage(logits, ld) else None
+
+
+def _check_ce(logits, targets, scales):
+    """(n_rows, V, ld) of logits [n_rows, V] (a view of the first V columns of a contiguous [n_rows, ld] tensor is taken as it is), int64
+    targets [n_rows] and the fp32 [n_rows] arrays of `scales` (name -> tensor or None)."""
+    if not (isinstance(logits, torch.Tensor) and logits.dtype in _CE_ENTRY and logits.dim() == 2 and logits.shape[0] >= 1
+            and logits.shape[1] >= 1 and logits.stride(1) == 1):
+        raise RuntimeError("logits must be a bf16, fp16 or fp32 tensor [n_rows, V] with unit stride along V")
+    n_rows, V = logits.shape
+    ld = _ce_ld(logits)
+    if ld is None:
+        raise RuntimeError(f"logits rows must lie ld elements apart in memory, ld a multiple of 8 and >= V = {V}: pass the first V columns "
+                           f"of a padded [n_rows, ld] tensor (INTEGRATION.md), got a row stride of {logits.stride(0)}")
+    if not (isinstance(targets, torch.Tensor) and targets.dtype == torch.int64 and tuple(targets.shape) == (n_rows,) and targets.is_contiguous()):
+        raise RuntimeError(f"targets must be a contiguous int64 tensor [n_rows = {n_rows}]")
+    for name, t in scales.items():
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == (n_rows,) and t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous fp32 tensor [n_rows = {n_rows}]")
+    if not logits.is_cuda:
+        raise RuntimeError("logits must be on the GPU (ce_rows has no CPU path: callers.lm_loss has the eager one)")
+    if any(t is not None and t.device != logits.device for t in (targets, *scales.values())):
+        raise RuntimeError("targets and the scales must be on the device of logits")
+    if logits.data_ptr() % 16:
+        raise RuntimeError("logits must be 16-byte aligned")
+    return n_rows, V, ld
+
+
+def _ce_stats(logits):
+    n, dev = logits.shape[0], logits.device
+    f = torch.empty((3, n), device=dev, dtype=torch.float32)
+    return f[0], f[1], f[2], torch.empty(n, device=dev, dtype=torch.int32)
+
+
+class _CeRows(torch.autograd.Function):
+    """loss_row of checked logits; the backward is one kernel with ce_scale = the incoming gradient.  As in the reference's L2Wrap the L2
+    term is not multiplied by it."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, l2_scale, dims):
+        n_rows, V, ld = dims
+        loss, lse, zmax, imax = _ce_stats(logits)
+        _call("wkv6_ce_rows_forward_" + _CE_ENTRY[logits.dtype], "ce rows forward", logits.device, n_rows, V, ld,
+              *_ptrs(logits, targets, loss, lse, zmax, imax, None, None, None), 0)
+        ctx.save_for_backward(logits, targets, lse, zmax, imax, l2_scale)
+        ctx.dims = dims
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        logits, targets, lse, zmax, imax, l2_scale = ctx.saved_tensors
+        n_rows, V, ld = ctx.dims
+        if l2_scale is None:
+            l2_scale = torch.zeros(n_rows, device=logits.device, dtype=torch.float32)
+        ce_scale = gloss.float().contiguous()
+        ld_g = (V + 7) // 8 * 8
+        g = torch.empty((n_rows, ld_g), device=logits.device, dtype=logits.dtype)
+        _call("wkv6_ce_rows_backward_" + _CE_ENTRY[logits.dtype], "ce rows backward", logits.device, n_rows, V, ld,
+              *_ptrs(logits, targets, lse, zmax, imax, ce_scale, l2_scale, g), ld_g)
+        return g[:, :V], None, None, None
+
+
+def ce_rows(logits, targets, l2_scale=None):
+    """loss_row fp32 [n_rows] = logsumexp(logits[r]) - logits[r, targets[r]] (+0 where targets[r] == -100) of logits [n_rows, V] (bf16, fp16
+    or fp32; rows ld elements apart, ld % 8 == 0) and int64 targets; the operation is stated in include/wkv6_amd.h.  Differentiable in
+    logits: the gradient is gloss_row[r] * (softmax - onehot) plus, with l2_scale (fp32 [n_rows]), the L2Wrap term l2_scale[r] * max at
+    the row's argmax, which is NOT multiplied by the incoming gradient (src/model.py:960-974).  Nothing is read on the host."""
+    dims = _check_ce(logits, targets, {"l2_scale": l2_scale})
+    return _CeRows.apply(logits, targets, l2_scale, dims)
+
+
+def ce_rows_grad_(logits, targets, ce_scale, l2_scale):
+    """The fused mode: one launch that OVERWRITES logits with the gradient ce_scale[r] * (softmax - onehot) + l2_scale[r] * max at the
+    argmax and returns loss_row fp32 [n_rows]; for a caller that knows its scales before it has any loss (callers.head_loss).  No
+    autograd: raises when a gradient is required."""
+    dims = _check_ce(logits, targets, {"ce_scale": ce_scale, "l2_scale": l2_scale})
+    if ce_scale is None or l2_scale is None:
+        raise RuntimeError("ce_rows_grad_ needs ce_scale and l2_scale (fp32 [n_rows])")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (logits, ce_scale, l2_scale)):
+        raise RuntimeError("ce_rows_grad_ overwrites logits and has no backward: call it under torch.no_grad() (ce_rows has autograd)")
+    n_rows, V, ld = dims
+    loss, lse, zmax, imax = _ce_stats(logits)
+    _call("wkv6_ce_rows_forward_" + _CE_ENTRY[logits.dtype], "ce rows fused", logits.device, n_rows, V, ld,
+          *_ptrs(logits, targets, loss, lse, zmax, imax, ce_scale, l2_scale, logits), ld)
+    return loss
 
 
 def gn_gate_forward(y, g, gamma, beta, H, eps):

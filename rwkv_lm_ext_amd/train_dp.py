@@ -130,6 +130,21 @@ class Block(nn.Module):
         return x + self.ffn(self.ln2(x))
 
 
+def _backbone(model, idx, cu_seqlens, max_seqlen):
+    """(ln_out(blocks(emb(idx))), the packed keywords) of a model with emb, blocks, ln_out and grad_cp; a packed batch is [1,total_T]."""
+    x = model.emb(idx)
+    packed = {} if cu_seqlens is None else {"cu_seqlens": cu_seqlens, "max_seqlen": max_seqlen}
+    if packed:
+        assert idx.size(0) == 1, "a packed batch is [1,total_T]"
+    for block in model.blocks:
+        if model.grad_cp and model.training and torch.is_grad_enabled():   # args.grad_cp, src/model_ext.py:1756-1758
+            from torch.utils.checkpoint import checkpoint
+            x = checkpoint(block, x, use_reentrant=False, **packed)
+        else:
+            x = block(x, **packed)
+    return model.ln_out(x), packed
+
+
 class SequenceEmbedder(nn.Module):
     """RwkvForSequenceEmbedding.forward (src/model_ext.py:1739-1769): emb -> blocks -> ln_out -> pooling at the
     first `emb_id` token -> optional tanh(dense(.))."""
@@ -149,17 +164,7 @@ class SequenceEmbedder(nn.Module):
         back, each cut behind its first emb_id token -- with max_seqlen the longest row and actual_len (int32 [n_seq]) the emb_id token's
         position in every row (None: the row's last token); one vector per sequence comes back, as from the padded rows.  Nothing of the
         packed route reads the device."""
-        x = self.emb(idx)
-        packed = {} if cu_seqlens is None else {"cu_seqlens": cu_seqlens, "max_seqlen": max_seqlen}
-        if packed:
-            assert idx.size(0) == 1, "a packed batch is [1,total_T]"
-        for block in self.blocks:
-            if self.grad_cp and self.training and torch.is_grad_enabled():   # args.grad_cp, src/model_ext.py:1756-1758
-                from torch.utils.checkpoint import checkpoint
-                x = checkpoint(block, x, use_reentrant=False, **packed)
-            else:
-                x = block(x, **packed)
-        x = self.ln_out(x)
+        x, packed = _backbone(self, idx, cu_seqlens, max_seqlen)
         if packed:
             x = callers.pooling_packed(x, cu_seqlens, actual_len, self.pooling_type)
         else:
@@ -183,6 +188,55 @@ def training_loss(model: nn.Module, query, positive=None, negative=None):
     emb = model(torch.cat(parts, dim=0)).float()
     bs = query.size(0)
     return callers.info_nce_loss(emb[:bs], emb[bs:2 * bs], emb[2 * bs:] if negative is not None else None)
+
+
+class CausalLM(nn.Module):
+    """The language model of src/model.py:1147-1154 (RWKV.forward without dropout / head_qk): emb -> blocks -> ln_out, and a bias-free
+    head that forward does NOT apply: it returns the hidden state behind ln_out, and lm_training_loss hands it to callers.head_loss
+    together with head.weight, so that the [rows, V] logits never exist (model.head(x) applies the head where somebody wants them)."""
+
+    def __init__(self, vocab_size, n_embd, n_layer, dim_att=None, dim_ffn=None, grad_cp=False, wkv=None, wkv_varlen=None):
+        super().__init__()
+        self.grad_cp = grad_cp
+        self.emb = nn.Embedding(vocab_size, n_embd)
+        self.blocks = nn.ModuleList([Block(n_embd, dim_att or n_embd, dim_ffn or int(n_embd * 3.5) // 32 * 32, i, wkv=wkv,
+                                           wkv_varlen=wkv_varlen) for i in range(n_layer)])
+        self.ln_out = nn.LayerNorm(n_embd)
+        self.head = nn.Linear(n_embd, vocab_size, bias=False)
+
+    def forward(self, idx, cu_seqlens=None, max_seqlen=None):
+        """cu_seqlens (int32 [n_seq + 1] on the device of idx) / max_seqlen: idx is a packed batch [1,total_T] as pack_lm_rows makes it."""
+        return _backbone(self, idx, cu_seqlens, max_seqlen)[0]
+
+
+def pack_lm_rows(idx, targets, lengths, total_multiple: int = 1, pad_id: int = 0):
+    """The padded rows idx, targets [B, T] (host tensors) with lengths [B] as one packed batch: (idx [1, total_T], targets [1, total_T],
+    cu_seqlens int32 [B + 1], max_seqlen int).  Row b keeps its first lengths[b] tokens.  total_multiple > 1 rounds total_T up with rows
+    behind the last sequence that belong to none: pad_id tokens with target -100, which the packed operators never read and the loss
+    ignores (lm_training_loss gives them no L2 term either)."""
+    assert idx.dim() == 2 and idx.shape == targets.shape and total_multiple >= 1
+    lens = torch.as_tensor(lengths, dtype=torch.long).clamp(0, idx.size(1))
+    keep = torch.arange(idx.size(1)).unsqueeze(0) < lens.unsqueeze(1)
+    cu = F.pad(lens.cumsum(0), (1, 0)).to(torch.int32)
+    flat_idx, flat_tgt = idx[keep], targets[keep]
+    total = max(-(-flat_idx.numel() // total_multiple) * total_multiple, 1)
+    flat_idx = F.pad(flat_idx, (0, total - flat_idx.numel()), value=pad_id)
+    flat_tgt = F.pad(flat_tgt, (0, total - flat_tgt.numel()), value=-100)
+    return flat_idx.unsqueeze(0), flat_tgt.unsqueeze(0), cu, int(lens.max())
+
+
+def lm_training_loss(model: nn.Module, idx, targets, mask=None, cu_seqlens=None, max_seqlen=None, chunk_rows: int = 4096,
+                     l2wrap: float = 1e-4, kernels=None):
+    """The reference's training_step loss (src/model.py:1244-1283) of a CausalLM through callers.head_loss.  idx, targets [B,T]: the L2
+    term covers all B * T rows, pad rows included, as the reference's does.  With cu_seqlens (idx, targets [1,total_T] of pack_lm_rows) the
+    L2 row count is cu_seqlens[-1], taken on the device, and rows outside every sequence get no L2 term: with target -100 they are then
+    never read."""
+    x = model(idx, cu_seqlens=cu_seqlens, max_seqlen=max_seqlen)
+    if cu_seqlens is None:
+        return callers.head_loss(x, model.head.weight, targets, mask, l2wrap, None, chunk_rows, kernels)
+    pos = torch.arange(x.shape[-2], device=x.device)
+    inside = (pos >= cu_seqlens[0]) & (pos < cu_seqlens[-1])
+    return callers.head_loss(x, model.head.weight, targets, mask, l2wrap, cu_seqlens[-1], chunk_rows, kernels, l2_rows=inside)
 
 
 def trainable_parameters(model: nn.Module) -> List[nn.Parameter]:
