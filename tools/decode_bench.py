@@ -4,6 +4,7 @@
 import os
 import sys
 
+import timing
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,16 +21,7 @@ for B, T in ((1, 1), (8, 1), (64, 1), (256, 1), (64, 4), (8, 16)):
     state = torch.zeros(B, H, 64, 64, device=dev)
     y = torch.empty(B, T, C, device=dev, dtype=bf)
     fn = lambda: rwkv6.forward_bf16(B, T, C, H, state, r, k, v, w, u, y)
-    for _ in range(20):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(200):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) / 200 * 1e3
+    us = timing.one_shot(fn, 200, 20) * 1e3
     gb = 2 * B * H * 64 * 64 * 4 / 1e9
     print(f"B={B:4d} T={T:3d}: {us:8.1f} us per call   state traffic {gb * 1e3:7.1f} MB -> {gb / (us * 1e-6):8.1f} GB/s", flush=True)
 
@@ -52,27 +44,13 @@ def step():
 
 step()
 torch.cuda.synchronize()
-side = torch.cuda.Stream()
-with torch.cuda.stream(side):
-    step()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        step()
+replay, _ = timing.graphed(step)
 torch.cuda.synchronize()
 y_eager = None
-for name, fn in (("eager", step), ("graph replay", graph.replay)):
+for name, fn in (("eager", step), ("graph replay", replay)):
     for st in states:
         st.zero_()
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(50):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    print(f"decode step of {L} calls, B={B}: {name:13s} {e0.elapsed_time(e1) / 50 * 1e3:8.1f} us", flush=True)
+    print(f"decode step of {L} calls, B={B}: {name:13s} {timing.one_shot(fn, 50, 5) * 1e3:8.1f} us", flush=True)
     if y_eager is None:
         y_eager = (y.clone(), states[0].clone())
     else:

@@ -17,6 +17,7 @@ import ctypes
 import os
 import sys
 
+import timing
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -71,15 +72,8 @@ def bwd(lib):
 
 
 def time_alone(lib, n):
-    for _ in range(10):
-        fwd(lib)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fwd(lib)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+    timing.warm(lambda: fwd(lib), calls=10, sync=None)
+    return timing.event_time(lambda: fwd(lib), n)
 
 
 def time_in_step(lib, blib, n):

@@ -6,6 +6,7 @@
 import os
 import sys
 
+import timing
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,16 +26,8 @@ def run(B, T, lens, label, iters=40):
     bwd = lambda: wkv6_op.bi_backward_ex(mask, r, k, v, w, u, gy, H, ws=ws)
     out = []
     for f in (fwd, bwd):
-        for _ in range(10):
-            fwd(); bwd()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            f()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
+        timing.warm(lambda: (fwd(), bwd()), calls=10)          # (both, in front of either timing: not timing.one_shot)
+        out.append(timing.event_time(f, iters))
     ntok = int(lens.sum().item())
     units = ntok * H * 2                                           # (token, head, direction)
     g64 = int(((lens + 63) // 64).sum().item()) * H * 2

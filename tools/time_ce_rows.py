@@ -14,15 +14,15 @@ head_loss at C = 2048, V = 65536, rows = 16384, trainable head, chunk_rows in {1
 (F.linear, then lm_loss(kernels=False)): time of forward + backward and torch.cuda.max_memory_allocated above what was allocated before
 the call.  The memory claim -- no [rows, V] tensor besides one chunk -- is asserted from those figures.
 
-Method: everything is allocated first, every contender is warmed, then --repeats rounds alternate the contenders, each timing --iters
-back-to-back calls with device events.
+Method: tools/timing.py (a few warm-up calls of every contender, --repeats rounds, --iters calls per timing).
 
     python tools/time_ce_rows.py [--out profiles/ce_rows_time.txt]
 """
 import argparse
 import os
-import statistics
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -33,24 +33,13 @@ def alternate(contenders, iters, repeats, warm=3):
     """{name: [ms per call, one per round]}; contenders: {name: callable}"""
     import torch
     for fn in contenders.values():
-        for _ in range(warm):
-            fn()
+        timing.warm(fn, calls=warm, sync=None)
     torch.cuda.synchronize()
-    out = {name: [] for name in contenders}
-    for _ in range(repeats):
-        for name, fn in contenders.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                fn()
-            e1.record()
-            e1.synchronize()
-            out[name].append(e0.elapsed_time(e1) / iters)
-    return out
+    return timing.alternate(contenders, lambda fn: timing.event_time(fn, iters), repeats)
 
 
 def fmt(ms):
-    med = statistics.median(ms)
+    med = timing.median(ms)
     return f"{med:9.3f} ms [{min(ms):8.3f}, {max(ms):8.3f}]  spread {100 * (max(ms) - min(ms)) / med:5.1f} %"
 
 
@@ -89,9 +78,9 @@ def row_kernels(n_rows, iters, repeats, say):
     must = 3 * n_rows * V * 2
     say(f"n_rows = {n_rows}, V = {V}, bf16 (logits {n_rows * V * 2 / 2 ** 30:.2f} GiB)")
     for name, ms in times.items():
-        rate = "" if name == "torch" else f"  {must / statistics.median(ms) * 1e-9:7.3f} TB/s of the {must / 2 ** 30:.2f} GiB that must move"
+        rate = "" if name == "torch" else f"  {must / timing.median(ms) * 1e-9:7.3f} TB/s of the {must / 2 ** 30:.2f} GiB that must move"
         say(f"  {name:8s} {fmt(ms)}  peak +{peaks[name] / 2 ** 30:6.2f} GiB{rate}")
-    med = {name: statistics.median(ms) for name, ms in times.items()}
+    med = {name: timing.median(ms) for name, ms in times.items()}
     margin = max(times["torch"]) - min(times["torch"]) + max(times["kernels"]) - min(times["kernels"])
     say(f"  torch / kernels = {med['torch'] / med['kernels']:.2f}x, torch / fused = {med['torch'] / med['fused']:.2f}x; "
         f"kernels below torch by more than both spreads: {med['torch'] - med['kernels'] > margin}")
@@ -149,11 +138,8 @@ def main():
     import torch
     assert torch.cuda.is_available(), "no GPU: nothing is measured on a CPU"
     torch.set_num_threads(min(16, torch.get_num_threads()))
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
+    log = timing.Log()
+    say = log.say
 
     p = torch.cuda.get_device_properties(0)
     say(f"# tools/time_ce_rows.py on {p.name}, {p.multi_processor_count} CUs, torch {torch.__version__}, HIP {torch.version.hip}; one box, one run")
@@ -168,9 +154,7 @@ def main():
         torch.cuda.empty_cache()
     say(f"lm_loss(kernels=None) may choose the kernels at n_rows {[n for n, w in wins.items() if w]}, not at {[n for n, w in wins.items() if not w]}")
     head(16384, 2048, max(1, args.iters // 2), args.repeats, say)
-    if args.out:
-        with open(os.path.join(ROOT, args.out) if not os.path.isabs(args.out) else args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    log.write(args.out and os.path.join(ROOT, args.out))          # (a relative --out is under the repository; join keeps an absolute one)
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ Shape: BASELINE configs[2] (B=48, T=512, C=2048, mask lengths U[64,512])."""
 import os
 import sys
 
+import timing
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,21 +36,12 @@ def module(in_kernel):
     return tm
 
 
-def run(tm, comp, n=20):
+def run(tm, comp):
     def step():
         x = x0.clone().requires_grad_(True)
         out = tm.forward_bi_b(x, mask) if comp == "b" else tm.forward_bi_c(x, rev_idx, mask)
         out.backward(dout)
-    for _ in range(5):
-        step()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        step()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+    return timing.one_shot(step, 20, 5)
 
 
 for comp in ("b", "c"):
@@ -89,19 +81,7 @@ def one():
     op.backward_pair_ex(H, u, sets)
 
 
-def timeit(fn, n=30):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
+timeit = lambda fn: timing.one_shot(fn, 30, 5)
 for rnd in range(3):
     print(f"operator only, both directions fwd+bwd (B=48, T=512, full length): two launches per pass {timeit(two):.4f} ms   "
           f"one launch per pass {timeit(one):.4f} ms", flush=True)

@@ -13,20 +13,17 @@ against three baselines, eagerly and replayed from a captured graph:
            checkout of the parent commit with its own built library, imported in a process of its own; without it the same code runs
            from this tree and the output says so.
 
-Method of tools/time_packed_step.py: one child process per contender, everything allocated first, each contender warmed for --warm seconds,
-then --repeats rounds alternate the contenders (only one of them running at a time), each timing --iters back-to-back calls with device
-events; reported is the median [min, max] over the rounds.  The accuracy lines are mix_op.lora_packed on the inputs of
+Method: tools/timing.py, one child process per contender (--warm seconds of warm-up each, synchronised after every call; --repeats rounds;
+--iters calls per timing); reported is the median [min, max] over the rounds.  The accuracy lines are mix_op.lora_packed on the inputs of
 tests/test_lora_packed_gpu.py against the fp64 restatement of tests/lora_common.py.
 
     python tools/time_lora_packed.py [--parent-tree PATH] [--out profiles/lora_packed_time.txt]
 """
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
-import time
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C, H, DIM_FFN, LAYERS, N_SLOTS, RANK = 2048, 32, 7168, 24, 256, 8
@@ -38,7 +35,6 @@ CASES = {
     "(ii) 8 x 66..512 + 56 x 1, 3 adapters": dict(lens=PROMPTS + [1] * 56, n_adapters=3),
 }
 KINDS = ("multi", "plain", "masked", "groups")
-TAG = "@@ "
 
 
 def worker(tree, layers, kind):
@@ -114,26 +110,8 @@ def worker(tree, layers, kind):
         if not graph:
             return run
         if "g" not in state["graphs"]:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                run()
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    state["keep"] = run()
-            torch.cuda.current_stream().wait_stream(side)
-            state["graphs"]["g"] = g
-        return state["graphs"]["g"].replay
-
-    def timed(fn, iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / iters * 1e3
+            state["graphs"]["g"] = timing.graphed(run)                       # (the replay, and the output it writes)
+        return state["graphs"]["g"][0]
 
     def accuracy():
         sys.path.insert(0, os.path.join(tree, "tests"))
@@ -148,63 +126,14 @@ def worker(tree, layers, kind):
                 out.append([K, N, R, total_T, lc.worst_ratio(y.cpu(), *lc.reference(K, N, R, total_T))])
         return out
 
-    p = torch.cuda.get_device_properties(0)
-    print(TAG + json.dumps({"ready": True, "device": p.name, "cus": p.multi_processor_count, "torch": torch.__version__, "hip": torch.version.hip}),
-          flush=True)
+    ops = {
+        "setup": setup,
+        "warm": lambda graph, seconds: timing.warm(contender(graph), seconds=seconds, sync="each"),
+        "time": lambda graph, iters: {"us": timing.event_time(contender(graph), iters) * 1e3},
+        "accuracy": lambda: {"rows": accuracy()},
+    }
     with torch.no_grad():
-        for line in sys.stdin:
-            q = json.loads(line)
-            try:
-                if q["op"] == "quit":
-                    break
-                if q["op"] == "setup":
-                    setup(q["case"])
-                    r = {}
-                elif q["op"] == "warm":
-                    fn = contender(q["graph"])
-                    t0 = time.time()
-                    while time.time() - t0 < q["seconds"]:
-                        fn()
-                        torch.cuda.synchronize()
-                    r = {}
-                elif q["op"] == "time":
-                    r = {"us": timed(contender(q["graph"]), q["iters"])}
-                elif q["op"] == "accuracy":
-                    r = {"rows": accuracy()}
-                else:
-                    raise ValueError(q["op"])
-            except Exception as e:                      # reported, not hidden: the parent of this process prints it and stops
-                r = {"error": f"{type(e).__name__}: {e}"}
-            print(TAG + json.dumps(r), flush=True)
-
-
-class Child:
-    def __init__(self, tree, layers, kind):
-        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", kind, "--tree", tree, "--layers", str(layers)],
-                                  stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, cwd=tree)
-        self.hello = self.read()
-
-    def read(self):
-        for line in self.p.stdout:
-            if line.startswith(TAG):
-                r = json.loads(line[len(TAG):])
-                if "error" in r:
-                    raise RuntimeError(r["error"])
-                return r
-        raise RuntimeError(f"the child process ended (exit code {self.p.wait()})")
-
-    def ask(self, **q):
-        self.p.stdin.write(json.dumps(q) + "\n")
-        self.p.stdin.flush()
-        return self.read()
-
-    def close(self):
-        try:
-            self.p.stdin.write(json.dumps({"op": "quit"}) + "\n")
-            self.p.stdin.close()
-        except OSError:
-            pass
-        self.p.wait()
+        timing.serve({"ready": True, **timing.device_record()}, ops)
 
 
 def main():
@@ -220,17 +149,15 @@ def main():
     a = ap.parse_args()
     if a.worker:
         return worker(os.path.abspath(a.tree), a.layers, a.worker)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
+    log = timing.Log()
+    say = log.say
     group_tree = os.path.abspath(a.parent_tree) if a.parent_tree else ROOT
-    kids = {k: Child(group_tree if k == "groups" else ROOT, a.layers, k) for k in KINDS}
+    kids = {}
+    for k in KINDS:
+        tree = group_tree if k == "groups" else ROOT
+        kids[k] = timing.Child([os.path.abspath(__file__), "--worker", k, "--tree", tree, "--layers", str(a.layers)], cwd=tree)
     try:
-        h = kids["multi"].hello
-        say(f"device: {h['device']}, {h['cus']} CUs; torch {h['torch']}; hip {h['hip']}")
+        say(timing.device_header(kids["multi"].hello))
         say(f"infctx.step_packed, bf16, C={C}, H={H}, dim_ffn={DIM_FFN}, {a.layers} layers, {N_SLOTS} slots, LoRA r={RANK} on the six targets; "
             f"{a.iters} calls per timing, {a.repeats} alternated rounds, {a.warm:.1f} s warm-up each; us per step: median [min, max]")
         say("multi: per-sequence adapters through the HIP kernels (this tree).  plain: no adapter (this tree).  masked: the eager masked loop "
@@ -244,13 +171,10 @@ def main():
                 k.ask(op="setup", case=case)
             say(case)
             for graph in (True, False):
-                res = {k: [] for k in kids}
-                for k, kid in kids.items():
+                for kid in kids.values():
                     kid.ask(op="warm", graph=graph, seconds=a.warm)
-                for _ in range(a.repeats):
-                    for k, kid in kids.items():
-                        res[k].append(kid.ask(op="time", graph=graph, iters=a.iters)["us"])
-                m = {k: statistics.median(v) for k, v in res.items()}
+                res = timing.alternate(kids, lambda kid: kid.ask(op="time", graph=graph, iters=a.iters)["us"], a.repeats)
+                m = {k: timing.median(v) for k, v in res.items()}
                 mode = "graph" if graph else "eager"
                 for k in KINDS:
                     say(f"  {mode:5s} {k:6s} {m[k]:10.1f} [{min(res[k]):10.1f}, {max(res[k]):10.1f}]" +
@@ -263,9 +187,7 @@ def main():
     finally:
         for k in kids.values():
             k.close()
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    log.write(a.out)
 
 
 if __name__ == "__main__":

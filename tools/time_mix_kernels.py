@@ -8,6 +8,7 @@ RWKV_AMD_LIB names another build of the library (rwkv_lm_ext_amd/_lib.py): the s
 import os
 import sys
 
+import timing
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,19 +24,7 @@ i32 = lambda v: torch.as_tensor(v, dtype=torch.int32).to(dev)
 tc = B * T * C
 
 
-def timeit(fn, n=50):
-    for _ in range(10):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3     # us
-
-
+timeit = lambda fn: timing.one_shot(fn, 50, 10) * 1e3     # us
 rows = []
 cu = i32([T * s for s in range(B + 1)])
 rev_n = torch.randint(0, T + 1, (B,), device=dev, generator=g).to(torch.int32)

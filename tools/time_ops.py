@@ -5,6 +5,7 @@ import argparse
 import os
 import sys
 
+import timing
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,29 +30,19 @@ y = torch.empty_like(r)
 ckpt = wkv6_op.new_checkpoint(B, T, C, H, dev)
 
 
-def run(fn, n):
-    for _ in range(10):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-
-
+run = lambda fn, n: timing.one_shot(fn, n, 10)
 fwd = lambda: wkv6_op.forward_ex(r, k, v, w, u, H, y=y, ckpt=None if args.no_ckpt else ckpt)
 bwd = lambda: wkv6_op.backward_ex(r, k, v, w, u, gy, H, ckpt=ckpt)
-import time as _time
-_t0 = _time.perf_counter()
-while _time.perf_counter() - _t0 < float(os.environ.get("WKV6_PREWARM_S", "0.6")):     # sustained clocks first (profiles/r06_dvfs_transient.txt)
+
+
+def burst():
     for _ in range(16):
         fwd()
         if args.only != "fwd":
             bwd()
-    torch.cuda.synchronize()
+
+
+timing.warm(burst, seconds=float(os.environ.get("WKV6_PREWARM_S", "0.6")), sync="each")     # sustained clocks first (profiles/r06_dvfs_transient.txt)
 out = {}
 if args.only == "both" and os.environ.get("WKV6_CLOCKS", "0") == "1":
     # inside fwd+bwd steps, launch by launch from the clock ring (what bench.py times): mean duration, clock and cycles per loop unit

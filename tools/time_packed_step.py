@@ -13,20 +13,18 @@ fresh (this tool never replaces a process image).  The parent has no step_packed
 cmix_forward_packed itself, with the same residual adds and LayerNorms.  Without --parent-tree the baseline is this tree with
 pool_kernels=False (the same eager code, kept as the fallback), and the output says so.
 
-Method of tools/time_rwkv6_split.py: everything is allocated first, each contender is warmed for --warm seconds, then --repeats rounds
-alternate the two sides (one child process each, only one of them running at a time), each timing --iters back-to-back calls with device
-events; reported is the median [min, max] over the rounds.  The kernel launches per sub-layer come from a torch.profiler trace taken in
-child processes of their own, after the timing ones have ended.
+Method: tools/timing.py, one child process per side (--warm seconds of warm-up each, synchronised after every call; --repeats rounds;
+--iters-block / --iters-step calls per timing); reported is the median [min, max] over the rounds.  The kernel launches per sub-layer come
+from a torch.profiler trace taken in child processes of their own, after the timing ones have ended.
 
     python tools/time_packed_step.py [--parent-tree PATH] [--out profiles/packed_step_time.txt]
 """
 import argparse
-import json
+import functools
 import os
-import statistics
-import subprocess
 import sys
-import time
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C, H, DIM_FFN, LAYERS = 2048, 32, 7168, 24
@@ -36,7 +34,6 @@ CASES = {
     "(iii) 8 x 1024, snapshot every 256": dict(lens=[1024] * 8, snap_every=256),
 }
 N_SLOTS = (256, 4096)
-TAG = "@@ "
 
 
 # ---- a child: one side (one tree) in one process, driven over stdin / stdout
@@ -101,26 +98,8 @@ def worker(tree, layers):
             return lambda: run(n_layers, pool_kernels)
         key = (n_layers, pool_kernels)
         if key not in state["graphs"]:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                run(n_layers, pool_kernels)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    state["keep", key] = run(n_layers, pool_kernels)
-            torch.cuda.current_stream().wait_stream(side)
-            state["graphs"][key] = g
-        return state["graphs"][key].replay
-
-    def timed(fn, iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / iters * 1e3
+            state["graphs"][key] = timing.graphed(lambda: run(n_layers, pool_kernels))      # (the replay, and the output it writes)
+        return state["graphs"][key][0]
 
     def count(pool_kernels):
         """device operations (kernels, copies, memsets) of one time-mix and one channel-mix sub-layer call, from a profiler trace"""
@@ -140,63 +119,18 @@ def worker(tree, layers):
             out[name] = sum(1 for e in prof.events() if e.device_type == DeviceType.CUDA)
         return out
 
-    print(TAG + json.dumps({"ready": True, "has_step": has_step, "device": torch.cuda.get_device_properties(0).name,
-                            "cus": torch.cuda.get_device_properties(0).multi_processor_count, "torch": torch.__version__,
-                            "hip": torch.version.hip}), flush=True)
+    ops = {
+        "setup": setup,
+        "warm": lambda layers, pool_kernels, graph, seconds: timing.warm(contender(layers, pool_kernels, graph), seconds=seconds, sync="each"),
+        "time": lambda layers, pool_kernels, graph, iters: {"us": timing.event_time(contender(layers, pool_kernels, graph), iters) * 1e3},
+        "count": lambda pool_kernels: {"count": count(pool_kernels)},
+    }
     with torch.no_grad():
-        for line in sys.stdin:
-            q = json.loads(line)
-            try:
-                if q["op"] == "quit":
-                    break
-                if q["op"] == "setup":
-                    setup(q["case"], q["n_slots"])
-                    r = {}
-                elif q["op"] == "warm":
-                    fn = contender(q["layers"], q["pool_kernels"], q["graph"])
-                    t0 = time.time()
-                    while time.time() - t0 < q["seconds"]:
-                        fn()
-                        torch.cuda.synchronize()
-                    r = {}
-                elif q["op"] == "time":
-                    r = {"us": timed(contender(q["layers"], q["pool_kernels"], q["graph"]), q["iters"])}
-                elif q["op"] == "count":
-                    r = {"count": count(q["pool_kernels"])}
-                else:
-                    raise ValueError(q["op"])
-            except Exception as e:                      # reported, not hidden: the parent of this process prints it and stops
-                r = {"error": f"{type(e).__name__}: {e}"}
-            print(TAG + json.dumps(r), flush=True)
+        timing.serve({"ready": True, "has_step": has_step, **timing.device_record()}, ops)
 
 
-class Child:
-    def __init__(self, tree, layers):
-        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", "--tree", tree, "--layers", str(layers)],
-                                  stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, cwd=tree)
-        self.hello = self.read()
-
-    def read(self):
-        for line in self.p.stdout:
-            if line.startswith(TAG):
-                r = json.loads(line[len(TAG):])
-                if "error" in r:
-                    raise RuntimeError(r["error"])
-                return r
-        raise RuntimeError(f"the child process ended (exit code {self.p.wait()})")
-
-    def ask(self, **q):
-        self.p.stdin.write(json.dumps(q) + "\n")
-        self.p.stdin.flush()
-        return self.read()
-
-    def close(self):
-        try:
-            self.p.stdin.write(json.dumps({"op": "quit"}) + "\n")
-            self.p.stdin.close()
-        except OSError:
-            pass
-        self.p.wait()
+def child(tree, layers):
+    return timing.Child([os.path.abspath(__file__), "--worker", "--tree", tree, "--layers", str(layers)], cwd=tree)
 
 
 def main():
@@ -213,19 +147,14 @@ def main():
     a = ap.parse_args()
     if a.worker:
         return worker(os.path.abspath(a.tree), a.layers)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
+    log = timing.Log()
+    say = log.say
     base_tree = os.path.abspath(a.parent_tree) if a.parent_tree else ROOT
     base_kernels = None if a.parent_tree else False    # the parent tree has no such argument; this tree's eager code is pool_kernels=False
     sides = {"new": (ROOT, None), "base": (base_tree, base_kernels)}
-    kids = {n: Child(tree, a.layers) for n, (tree, _) in sides.items()}
+    kids = {n: child(tree, a.layers) for n, (tree, _) in sides.items()}
     try:
-        h = kids["new"].hello
-        say(f"device: {h['device']}, {h['cus']} CUs; torch {h['torch']}; hip {h['hip']}")
+        say(timing.device_header(kids["new"].hello))
         if a.parent_tree:
             assert not kids["base"].hello["has_step"], "--parent-tree already has step_packed: not the parent commit"
             say("baseline ('base'): the parent commit's tree in a process of its own, its tmix_forward_packed / cmix_forward_packed looped with the "
@@ -245,16 +174,13 @@ def main():
                 say(f"{case}, n_slots = {n_slots}")
                 for what, layers, iters in (("block", 1, a.iters_block), (f"step x{a.layers}", a.layers, a.iters_step)):
                     for graph in (False, True):
-                        res = {n: [] for n in kids}
-                        for n, k in kids.items():
-                            k.ask(op="warm", layers=layers, pool_kernels=sides[n][1], graph=graph, seconds=a.warm)
-                        for _ in range(a.repeats):
-                            for n, k in kids.items():
-                                res[n].append(k.ask(op="time", layers=layers, pool_kernels=sides[n][1], graph=graph, iters=iters)["us"])
-                        m = {n: statistics.median(xs) for n, xs in res.items()}
+                        ask = {n: functools.partial(k.ask, layers=layers, pool_kernels=sides[n][1], graph=graph) for n, k in kids.items()}
+                        for q in ask.values():
+                            q(op="warm", seconds=a.warm)
+                        res = timing.alternate(ask, lambda q: q(op="time", iters=iters)["us"], a.repeats)
+                        m = {n: timing.median(xs) for n, xs in res.items()}
                         fmt = lambda n: f"{n} {m[n]:10.1f} [{min(res[n]):10.1f}, {max(res[n]):10.1f}]"
-                        apart = ("ranges do not overlap" if max(res["new"]) < min(res["base"]) or min(res["new"]) > max(res["base"])
-                                 else "ranges overlap")
+                        apart = "ranges do not overlap" if timing.apart(res["new"], res["base"]) else "ranges overlap"
                         mode = "graph" if graph else "eager"
                         say(f"  {what:9s} {mode:5s}  {fmt('new')}   {fmt('base')}   new / base = {m['new'] / m['base']:.3f} ({apart})")
                         summary.append(f"{case}, n_slots {n_slots}, {what}, {mode}: {m['new']:.1f} against {m['base']:.1f} us = "
@@ -269,7 +195,7 @@ def main():
     say()
     say("device operations (kernels, copies, memsets) per sub-layer call, from a torch.profiler trace in a process of its own:")
     for n, (tree, pool_kernels) in sides.items():
-        k = Child(tree, 1)
+        k = child(tree, 1)
         try:
             for case in CASES:
                 for n_slots in N_SLOTS[:1]:
@@ -281,9 +207,7 @@ def main():
                         say(f"  {n:4s} {case}: not measured ({e})")
         finally:
             k.close()
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    log.write(a.out)
 
 
 if __name__ == "__main__":

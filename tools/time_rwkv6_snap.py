@@ -10,19 +10,16 @@ serves the same request without it, bf16, H=32, C=2048:
                      pool[dst] = pool[src] followed by the packed call in place on dst
 
 The baselines go to --parent-lib (a librwkv6_amd.so built from the commit before the snap call existed), else to this tree's library.
-Method of tools/time_rwkv6_varlen.py: ctypes calls with pre-bound arguments on both sides, everything allocated first, a bits check, each
-contender warmed for --warm seconds, then --repeats rounds alternate the contenders in one process, each timing --iters back-to-back calls
-with device events; the baseline runs twice per round ("base-2") to show the spread of a contender against itself.
+Method: tools/timing.py (ctypes calls with pre-bound arguments on both sides, a bits check first, --warm seconds of warm-up each, --repeats
+rounds in one process, --iters calls per timing); the baseline runs twice per round ("base-2").
 
     python tools/time_rwkv6_snap.py [--parent-lib PATH] [--out profiles/rwkv6_snap_time.txt]
 """
 import argparse
-import ctypes
 import os
-import statistics
 import sys
-import time
 
+import timing
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,20 +41,14 @@ def main():
     a = ap.parse_args()
     H = a.H
     C = 64 * H
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
+    log = timing.Log()
+    say = log.say
 
     lib = _lib.load()
+    parent = lib
     if a.parent_lib:
-        parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
-        parent.rwkv6_forward_varlen_bf16.restype = ctypes.c_int
-        parent.rwkv6_forward_varlen_bf16.argtypes = lib.rwkv6_forward_varlen_bf16.argtypes
-        assert not hasattr(parent, "rwkv6_forward_varlen_snap_bf16"), "--parent-lib already has the snap call: not the parent commit's library"
-    else:
-        parent = lib
+        parent = timing.load_library(a.parent_lib, {"rwkv6_forward_varlen_bf16": _lib.SIGNATURES["rwkv6_forward_varlen_bf16"]},
+                                     lacks=("rwkv6_forward_varlen_snap_bf16", "the snap call"))
     stream = torch.cuda.current_stream().cuda_stream
     g = torch.Generator(device="cuda").manual_seed(0)
     p = lambda t: None if t is None else t.data_ptr()
@@ -94,45 +85,26 @@ def main():
             slot_out, every, cu_snap, snap_slot = snap
             fn = which.rwkv6_forward_varlen_snap_bf16
             args += (p(slot_out), every, p(cu_snap), p(snap_slot), 0 if snap_slot is None else snap_slot.numel())
+        return timing.bound(fn, *args)
 
-        def run():
-            rc = fn(*args)
-            assert rc == 0, rc
-        return run
-
-    prop = torch.cuda.get_device_properties(0)
-    say(f"device: {prop.name}, {prop.multi_processor_count} CUs; torch {torch.__version__}; hip {torch.version.hip}")
+    say(timing.device_header())
     where = "the parent commit's library" if a.parent_lib else "this library"
     say(f"bf16, H={H}, C={C}; baselines from {where}; {a.iters} calls per timing, {a.repeats} alternated repeats, {a.warm:.1f} s warm-up each")
     say()
 
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / a.iters * 1e3                          # us per call (or per chain of calls)
+    timed = lambda fn: timing.event_time(fn, a.iters) * 1e3                 # us per call (or per chain of calls)
 
     def race(title, new, base):
-        contenders = {"snap": new, "base": base, "base-2": base}
         for fn in (new, base):
-            t0 = time.time()
-            while time.time() - t0 < a.warm:
-                fn()
-            torch.cuda.synchronize()
-        res = {n: [] for n in contenders}
-        for _ in range(a.repeats):
-            for n, fn in contenders.items():
-                res[n].append(timed(fn))
+            timing.warm(fn, seconds=a.warm)
+        res = timing.alternate({"snap": new, "base": base, "base-2": base}, timed, a.repeats)
         for n, xs in res.items():
-            say(f"  {n:8s} us: " + " ".join(f"{x:8.1f}" for x in xs) + f"   median {statistics.median(xs):8.1f}  min {min(xs):8.1f}  max {max(xs):8.1f}")
-        m = {n: statistics.median(xs) for n, xs in res.items()}
+            say(f"  {n:8s} us: " + timing.values_and_stats(xs, 8, 1))
+        m = {n: timing.median(xs) for n, xs in res.items()}
         lo, hi = min(res["base"] + res["base-2"]), max(res["base"] + res["base-2"])
         say(f"  snap / base = {m['snap'] / m['base']:.3f} ({m['snap'] - m['base']:+.1f} us, {100 * (m['snap'] / m['base'] - 1):+.1f} %); "
             f"base against itself: {m['base-2'] / m['base']:.3f}, range [{lo:.1f}, {hi:.1f}] us; "
-            f"{'ranges do not overlap' if max(res['snap']) < lo or min(res['snap']) > hi else 'ranges overlap'}")
+            f"{'ranges do not overlap' if timing.apart(res['snap'], (lo, hi)) else 'ranges overlap'}")
         say()
         return m
 
@@ -197,9 +169,7 @@ def main():
     say(f"(b) the snapshots cost {mb['snap'] - mb['base']:+.1f} us ({100 * (mb['snap'] / mb['base'] - 1):+.1f} %) for {stores / 2**20:.0f} MiB of stores: "
         f"{stores / max(mb['snap'] - mb['base'], 1e-3) / 1e6:.2f} TB/s if the difference were the stores alone")
     say(f"(c) one call with output slots against copy + call: {mc['snap'] - mc['base']:+.1f} us ({100 * (mc['snap'] / mc['base'] - 1):+.1f} %)")
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    log.write(a.out)
 
 
 if __name__ == "__main__":

@@ -7,19 +7,16 @@
 
 The dense calls go to --parent-lib when one is given (a librwkv6_amd.so built from the commit before the packed call existed), else to this
 tree's library.  Every call is made through ctypes with pre-bound arguments, the same way on both sides, so that the host cost per call is
-the same few microseconds.  Method of tools/time_varlen.py: everything is allocated first, each contender is warmed for --warm seconds,
-then --repeats rounds alternate the contenders in one process, each timing --iters back-to-back calls with device events; the dense
-contender runs twice per round ("dense-2") to show the spread of a contender against itself.
+the same few microseconds.  Method: tools/timing.py (--warm seconds of warm-up each, --repeats rounds in one process, --iters calls per
+timing); the dense contender runs twice per round ("dense-2").
 
     python tools/time_rwkv6_varlen.py [--parent-lib PATH] [--out profiles/rwkv6_varlen_time.txt]
 """
 import argparse
-import ctypes
 import os
-import statistics
 import sys
-import time
 
+import timing
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,64 +38,31 @@ def main():
     a = ap.parse_args()
     H = a.H
     C = 64 * H
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
+    log = timing.Log()
+    say = log.say
 
     lib = _lib.load()
+    parent = lib
     if a.parent_lib:
-        parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
-        parent.rwkv6_cuda_forward_bf16.restype = ctypes.c_int
-        parent.rwkv6_cuda_forward_bf16.argtypes = lib.rwkv6_cuda_forward_bf16.argtypes
-        assert not hasattr(parent, "rwkv6_forward_varlen_bf16"), "--parent-lib already has the packed call: not the parent commit's library"
-    else:
-        parent = lib
+        parent = timing.load_library(a.parent_lib, {"rwkv6_cuda_forward_bf16": _lib.SIGNATURES["rwkv6_cuda_forward_bf16"]},
+                                     lacks=("rwkv6_forward_varlen_bf16", "the packed call"))
     stream = torch.cuda.current_stream().cuda_stream
     g = torch.Generator(device="cuda").manual_seed(0)
-    keep = []                                                                # every buffer a bound call points into
 
     def batch(lens):
-        total = sum(lens)
-        r, k, v = (torch.randn(total, C, device="cuda", generator=g).mul_(0.5).to(bf) for _ in range(3))
-        w = torch.exp(-torch.exp(torch.randn(total, C, device="cuda", generator=g) - 2.0)).contiguous()
-        y = torch.empty(total, C, device="cuda", dtype=bf)
-        cu = torch.tensor([0] + list(torch.tensor(lens).cumsum(0)), dtype=torch.int32, device="cuda")
-        pool = torch.zeros(len(lens), H, 64, 64, device="cuda")
-        ws = torch.empty(lib.rwkv6_varlen_workspace_bytes(len(lens)), dtype=torch.uint8, device="cuda")
-        keep.extend((r, k, v, w, y, cu, pool, ws))
-        return dict(r=r, k=k, v=v, w=w, y=y, cu=cu, pool=pool, ws=ws, lens=lens, total=total)
+        return timing.packed_batch(lens, H, g, lib.rwkv6_varlen_workspace_bytes(len(lens)))
 
     u = (torch.randn(H, 64, device="cuda", generator=g) * 0.3).to(bf)
     p = lambda t: t.data_ptr()
 
     def packed_call(d):
-        args = (d["total"], len(d["lens"]), max(d["lens"]), C, H, p(d["cu"]), None, len(d["lens"]), p(d["pool"]), p(d["r"]), p(d["k"]), p(d["v"]),
-                p(d["w"]), p(u), p(d["y"]), p(d["ws"]), d["ws"].numel(), 0, stream)
+        return timing.bound(lib.rwkv6_forward_varlen_bf16, d["total"], len(d["lens"]), max(d["lens"]), C, H, p(d["cu"]), None, len(d["lens"]),
+                            p(d["pool"]), p(d["r"]), p(d["k"]), p(d["v"]), p(d["w"]), p(u), p(d["y"]), p(d["ws"]), d["ws"].numel(), 0, stream)
 
-        def run():
-            rc = lib.rwkv6_forward_varlen_bf16(*args)
-            assert rc == 0, rc
-        return run
+    def dense_calls(d, rows):
+        return timing.dense_calls(parent.rwkv6_cuda_forward_bf16, d, rows, H, u, stream)
 
-    def dense_calls(d, which, rows):
-        """rows: (first token, B, T, first slot) per dense call"""
-        bound = []
-        for t0, B, T, slot in rows:
-            el = t0 * C
-            bound.append((B, T, C, H, p(d["pool"]) + slot * H * 4096 * 4, p(d["r"]) + el * 2, p(d["k"]) + el * 2, p(d["v"]) + el * 2,
-                          p(d["w"]) + el * 4, p(u), p(d["y"]) + el * 2, stream))
-        fn = which.rwkv6_cuda_forward_bf16
-
-        def run():
-            for args in bound:
-                rc = fn(*args)
-                assert rc == 0, rc
-        return run
-
-    prop = torch.cuda.get_device_properties(0)
-    say(f"device: {prop.name}, {prop.multi_processor_count} CUs; torch {torch.__version__}; hip {torch.version.hip}")
+    say(timing.device_header())
     where = "the parent commit's library" if a.parent_lib else "this library"
     say(f"bf16, H={H}, C={C}; dense calls from {where}; "
         f"{a.iters} calls per timing, {a.repeats} alternated repeats, {a.warm:.1f} s warm-up each")
@@ -114,18 +78,10 @@ def main():
         "(c) prefill 8 x 512": (prefill, [(0, 8, 512, 0)]),
     }
 
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / a.iters * 1e3                          # us per call (or per loop of dense calls)
-
+    timed = lambda fn: timing.event_time(fn, a.iters) * 1e3                 # us per call (or per loop of dense calls)
     med = {}
     for title, (d, rows) in cases.items():
-        contenders = {"packed": packed_call(d), "dense": dense_calls(d, parent, rows), "dense-2": dense_calls(d, parent, rows)}
+        contenders = {"packed": packed_call(d), "dense": dense_calls(d, rows), "dense-2": dense_calls(d, rows)}
         # same results first: y and the pool, bit for bit (from zero states)
         d["pool"].zero_()
         contenders["dense"]()
@@ -136,22 +92,16 @@ def main():
         torch.cuda.synchronize()
         say(f"{title}: packed y and states == dense, bit for bit: {bool(torch.equal(d['y'], want[0]) and torch.equal(d['pool'], want[1]))}")
         for fn in contenders.values():
-            t0 = time.time()
-            while time.time() - t0 < a.warm:
-                fn()
-            torch.cuda.synchronize()
-        res = {n: [] for n in contenders}
-        for _ in range(a.repeats):
-            for n, fn in contenders.items():
-                res[n].append(timed(fn))
+            timing.warm(fn, seconds=a.warm)
+        res = timing.alternate(contenders, timed, a.repeats)
         for n, xs in res.items():
-            say(f"  {n:8s} us: " + " ".join(f"{x:8.1f}" for x in xs) + f"   median {statistics.median(xs):8.1f}  min {min(xs):8.1f}  max {max(xs):8.1f}")
-        m = {n: statistics.median(xs) for n, xs in res.items()}
+            say(f"  {n:8s} us: " + timing.values_and_stats(xs, 8, 1))
+        m = {n: timing.median(xs) for n, xs in res.items()}
         med[title] = m
         lo, hi = min(res["dense"] + res["dense-2"]), max(res["dense"] + res["dense-2"])
         say(f"  packed / dense = {m['packed'] / m['dense']:.3f} ({m['packed'] - m['dense']:+.1f} us, {100 * (m['packed'] / m['dense'] - 1):+.1f} %); "
             f"dense against itself: {m['dense-2'] / m['dense']:.3f}, range [{lo:.1f}, {hi:.1f}] us; "
-            f"{'ranges do not overlap' if max(res['packed']) < lo or min(res['packed']) > hi else 'ranges overlap'}")
+            f"{'ranges do not overlap' if timing.apart(res['packed'], (lo, hi)) else 'ranges overlap'}")
         say()
     ta, tb, tc = (med[t] for t in cases)
     say(f"(a) one packed call is {ta['dense'] / ta['packed']:.2f}x the speed of the loop of 64 dense B = 1 calls"
@@ -160,9 +110,7 @@ def main():
         f"for that launch alone in profiles/varlen_time.txt)")
     say(f"(c) packed prefill against dense: {100 * (tc['packed'] / tc['dense'] - 1):+.1f} % (the packed training forward: +2.9 %; here the packed call "
         f"has a preparation launch and a scan launch, whose workgroups all leave at once, beside the chunked one)")
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    log.write(a.out)
 
 
 if __name__ == "__main__":

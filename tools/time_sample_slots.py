@@ -6,21 +6,20 @@ Baseline ('torch'): what a caller of the parent commit has behind the head -- a 
 pool rows, penalties, softmax over a full descending sort, cumsum, nucleus / top-k mask, inverse CDF in sorted order, scatter-update of the
 pool).  It reads nothing on the host, so that it can be captured too.
 
-Method of tools/time_lora_packed.py: one child process per n_seq, started fresh and ended by a time limit of its own (--limit seconds), at
-most 16 threads; everything is allocated first, each contender is warmed for --warm seconds, then --repeats rounds alternate the two, each
-timing --iters back-to-back calls with device events; reported is the median [min, max] over the rounds.  The last lines state the kernel's
+Method: tools/timing.py, in one child process per n_seq, started fresh and ended by a time limit of its own (--limit seconds), at most 16
+threads (--warm seconds of warm-up each, synchronised after every call; --repeats rounds of the two; --iters calls per timing); reported is
+the median [min, max] over the rounds.  The last lines state the kernel's
 time as a share of the graph-replayed decode step of 256 sequences that tools/time_packed_step.py recorded (profiles/packed_step_time.txt).
 
     python tools/time_sample_slots.py [--out profiles/sample_slots_time.txt]
 """
 import argparse
-import json
 import os
 import re
-import statistics
 import subprocess
 import sys
-import time
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 V, N_SLOTS = 65536, 256
@@ -28,7 +27,6 @@ N_SEQ = (1, 8, 256)
 SETTINGS = {"top-p 0.85": dict(temperature=1.0, top_p=0.85, top_k=0), "top-k 50": dict(temperature=1.0, top_p=1.0, top_k=50),
             "greedy": dict(temperature=0.0, top_p=1.0, top_k=0)}
 PENALTIES = dict(alpha_presence=0.3, alpha_frequency=0.3, alpha_decay=0.996)
-TAG = "@@ "
 
 
 def torch_sampler(logits, occ, slots, params, u):
@@ -60,29 +58,11 @@ def worker(n_seq, iters, repeats, warm):
     logits = (torch.randn(n_seq, V, device="cuda") * 2).bfloat16()
     slots = torch.randperm(N_SLOTS, device="cuda")[:n_seq].int()
     u = torch.rand(n_seq, device="cuda")
-    p = torch.cuda.get_device_properties(0)
-    print(TAG + json.dumps({"device": p.name, "cus": p.multi_processor_count, "torch": torch.__version__, "hip": torch.version.hip}), flush=True)
-
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / iters * 1e3
+    timing.emit(timing.device_record())
 
     def graphed(fn):
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            fn()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=side):
-                keep = fn()
-        torch.cuda.current_stream().wait_stream(side)
-        return lambda: (g.replay(), keep)[1]
+        replay, kept = timing.graphed(fn)
+        return lambda: (replay(), kept)[1]
 
     with torch.no_grad():
         for name, setting in SETTINGS.items():
@@ -95,16 +75,10 @@ def worker(n_seq, iters, repeats, warm):
             for graph in (False, True):
                 fns = {"kernel": graphed(kernel) if graph else kernel, "torch": graphed(torch_) if graph else torch_}
                 for fn in fns.values():
-                    t0 = time.time()
-                    while time.time() - t0 < warm:
-                        fn()
-                        torch.cuda.synchronize()
-                res = {k: [] for k in fns}
-                for _ in range(repeats):
-                    for k, fn in fns.items():
-                        res[k].append(timed(fn))
-                print(TAG + json.dumps({"setting": name, "graph": graph, "us": res, "same_tokens": same}), flush=True)
-    print(TAG + json.dumps({"done": True}), flush=True)
+                    timing.warm(fn, seconds=warm, sync="each")
+                res = timing.alternate(fns, lambda fn: timing.event_time(fn, iters) * 1e3, repeats)
+                timing.emit({"setting": name, "graph": graph, "us": res, "same_tokens": same})
+    timing.emit({"done": True})
 
 
 def main():
@@ -118,12 +92,8 @@ def main():
     a = ap.parse_args()
     if a.worker:
         return worker(a.worker, a.iters, a.repeats, a.warm)
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
-
+    log = timing.Log()
+    say = log.say
     env = dict(os.environ, OMP_NUM_THREADS=str(min(16, int(os.environ.get("OMP_NUM_THREADS", "16")))))
     graph_kernel_256 = {}
     for n_seq in N_SEQ:
@@ -134,13 +104,12 @@ def main():
         except subprocess.TimeoutExpired:
             say(f"n_seq = {n_seq}: the child process passed its limit of {a.limit:.0f} s and was ended; nothing after it is run")
             break
-        rows = [json.loads(line[len(TAG):]) for line in out.stdout.splitlines() if line.startswith(TAG)]
+        rows = timing.records(out.stdout)
         if out.returncode != 0 or not rows or not rows[-1].get("done"):
             say(f"n_seq = {n_seq}: the child process failed (exit code {out.returncode}); nothing after it is run")
             break
-        if not lines:
-            h = rows[0]
-            say(f"device: {h['device']}, {h['cus']} CUs; torch {h['torch']}; hip {h['hip']}")
+        if not log.lines:
+            say(timing.device_header(rows[0]))
             say(f"bf16 logits [n_seq, {V}], occurrence pool fp32 [{N_SLOTS}, {V}] with 1 % of its entries set, penalties {PENALTIES}; "
                 f"{a.iters} calls per timing, {a.repeats} alternated rounds, {a.warm:.1f} s warm-up each; us per call: median [min, max]")
             say("kernel: mix_op.sample_slots (one launch).  torch: the batched sort-based sampler of torch ops in tools/time_sample_slots.py.")
@@ -148,8 +117,8 @@ def main():
         say(f"n_seq = {n_seq}")
         for r in rows[1:-1]:
             k, t = r["us"]["kernel"], r["us"]["torch"]
-            mk, mt = statistics.median(k), statistics.median(t)
-            clear = "ranges do not overlap" if max(k) < min(t) or max(t) < min(k) else "RANGES OVERLAP"
+            mk, mt = timing.median(k), timing.median(t)
+            clear = "ranges do not overlap" if timing.apart(k, t) else "RANGES OVERLAP"
             say(f"  {r['setting']:10s} {'graph' if r['graph'] else 'eager'}  kernel {mk:9.1f} [{min(k):9.1f}, {max(k):9.1f}]   torch {mt:9.1f} "
                 f"[{min(t):9.1f}, {max(t):9.1f}]   kernel / torch = {mk / mt:.3f} ({clear}); torch's spread {max(t) - min(t):.1f}")
             if n_seq == 256 and r["graph"]:
@@ -166,9 +135,7 @@ def main():
             "included in either):")
         for name, us in graph_kernel_256.items():
             say(f"  {name:10s} kernel {us:9.1f} us = {100 * us / step:.2f} % of the step")
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    log.write(a.out)
 
 
 if __name__ == "__main__":

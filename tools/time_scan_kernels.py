@@ -1,11 +1,10 @@
 """The exact token-serial kernels (csrc/wkv6_scan.hip, csrc/wkv5_scan.hip) of this tree's library against another build of the library,
 normally the parent commit's: first every output bit for bit, then the time per call.
 
-Method of tools/time_rwkv6_varlen.py: both libraries are loaded through ctypes in one process and called with pre-bound arguments on the same
-inputs.  Equality: every output buffer is filled with NaN (a state pool: with the same initial states) before each side's call and compared as
-bits; the first difference is printed and the exit code is 1.  Speed: everything is allocated first, each contender is warmed, then
---repeats rounds alternate parent, tree and parent again ("parent-2": the spread of a contender against itself), each timing back-to-back
-calls with device events.  A row is "inside" when the tree's median is no further above the parent's than parent-2's is from the parent's.
+Both libraries are loaded through ctypes in one process and called with pre-bound arguments on the same inputs.  Equality: every output
+buffer is filled with NaN (a state pool: with the same initial states) before each side's call and compared as bits; the first difference is
+printed and the exit code is 1.  Speed: the method of tools/timing.py, --repeats rounds of parent, tree and parent again ("parent-2").  A
+row is "inside" when the tree's median is no further above the parent's than parent-2's is from the parent's.
 
     git archive <parent> | tar -x -C build_ab/parent_tree
     bash tools/build_tree_variant.sh parent build_ab/parent_tree/rwkv_lm_ext_amd/csrc ""
@@ -17,10 +16,9 @@ rwkv_lm_ext_amd/_lib.py (a rehearsal of the tool itself).
 import argparse
 import ctypes
 import os
-import statistics
 import sys
-import time
 
+import timing
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,21 +35,13 @@ class Lib:
     """One build of the library, typed from the binding's tables."""
 
     def __init__(self, path):
-        self.h = ctypes.CDLL(os.path.abspath(path))
-        for name, (res, args) in SIGS.items():
-            fn = getattr(self.h, name)
-            fn.restype, fn.argtypes = res, args
+        self.h = timing.load_library(path, SIGS)
 
     def size(self, name, *args):
         return getattr(self.h, name)(*args)
 
     def bind(self, name, *args):
-        fn = getattr(self.h, name)
-
-        def run():
-            rc = fn(*args)
-            assert rc == 0, (name, rc)
-        return run
+        return timing.bound(getattr(self.h, name), *args)
 
 
 class DryLib:
@@ -92,11 +82,8 @@ def main():
     ap.add_argument("--dry", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
+    log = timing.Log()
+    say = log.say
 
     if a.dry:
         device, stream = "cpu", 0
@@ -107,8 +94,7 @@ def main():
         device = "cuda"
         tree, parent = Lib(_lib.load()._name), Lib(a.parent_lib)
         stream = torch.cuda.current_stream().cuda_stream
-        prop = torch.cuda.get_device_properties(0)
-        say(f"device: {prop.name}, {prop.multi_processor_count} CUs; torch {torch.__version__}; hip {torch.version.hip}")
+        say(timing.device_header())
         say(f"tree: {_lib.load()._name}")
         say(f"parent: {os.path.abspath(a.parent_lib)}")
     g = torch.Generator().manual_seed(0)
@@ -323,9 +309,7 @@ def main():
             say(f"            {n}: {d_}")
     say(f"equality: {n_out - bad} of {n_out} outputs identical" + ("" if not bad else f", {bad} DIFFERENT"))
     if bad or a.no_speed:
-        if a.out:
-            with open(a.out, "w") as fh:
-                fh.write("\n".join(lines) + "\n")
+        log.write(a.out)
         sys.exit(1 if bad else 0)
 
     # ---- speed -------------------------------------------------------------------------------------------------------------------------
@@ -352,42 +336,26 @@ def main():
         say(f"speed: {len(rows)} rows built: " + "; ".join(t for t, _ in rows))
         return
 
-    def timed(fn, iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / iters * 1e3                          # us per call
-
+    timed = lambda fn, iters: timing.event_time(fn, iters) * 1e3         # us per call
     say()
     say(f"speed: us per call, {a.repeats} rounds of parent, tree, parent-2; {a.warm:.1f} s warm-up each, about {a.per_timing * 1e3:.0f} ms of calls per timing")
     outside = 0
     for title, contenders in rows:
         for fn in contenders.values():
-            t0 = time.time()
-            while time.time() - t0 < a.warm:
-                fn()
-            torch.cuda.synchronize()
+            timing.warm(fn, seconds=a.warm)
         iters = max(3, min(500, int(a.per_timing * 1e6 / max(timed(contenders["parent"], 3), 1.0))))
-        res = {n: [] for n in contenders}
-        for _ in range(a.repeats):
-            for n, fn in contenders.items():
-                res[n].append(timed(fn, iters))
-        med = {n: statistics.median(xs) for n, xs in res.items()}
+        res = timing.alternate(contenders, lambda fn: timed(fn, iters), a.repeats)
+        med = {n: timing.median(xs) for n, xs in res.items()}
         spread = abs(med["parent-2"] - med["parent"])
         ok = med["tree"] - med["parent"] <= spread
         outside += not ok
         say(f"  {title}   ({iters} calls per timing)")
         for n, xs in res.items():
-            say(f"    {n:9s} median {med[n]:9.1f}  min {min(xs):9.1f}  max {max(xs):9.1f}")
+            say(f"    {n:9s} " + timing.stats(xs, 9, 1))
         say(f"    tree - parent = {med['tree'] - med['parent']:+.1f} us ({100 * (med['tree'] / med['parent'] - 1):+.2f} %), "
             f"|parent-2 - parent| = {spread:.1f} us: {'inside' if ok else 'OUTSIDE'}")
     say(f"speed: {len(rows) - outside} of {len(rows)} rows inside" + ("" if not outside else f", {outside} OUTSIDE (repeat the command once before judging)"))
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    log.write(a.out)
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ GroupNorm * gate epilogue fused into the operator's forward kernel (SURVEY.md ro
 import os
 import sys
 
+import timing
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,17 +26,7 @@ x = torch.randn(B, T, C, device=dev).to(torch.bfloat16).requires_grad_(True)
 dout = torch.randn(B, T, C, device=dev).to(torch.bfloat16)
 
 
-def timeit(fn, n=30):
-    for _ in range(8):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
+timeit = lambda fn: timing.one_shot(fn, 30, 8)
 
 
 def train():

@@ -8,8 +8,8 @@ batch 32 triples = 96 rows of T = 512, activation checkpointing, DDP over a one-
 on (a) the benchmark's own synthetic batches (n uniform in 16..510, n + 1 tokens kept of 512) and (b) a batch of full-length rows (emb_id
 at position 511: nothing to leave out, packing can only cost).
 
-Method: one process, one model, one optimizer; the batches of a case are made once, staged in pinned memory, and every contender walks
-the same list.  A contender's time is dp.timed_steps (the benchmark's timing: --warmup untimed steps, then --steps steps between device
+Method: the alternated rounds of tools/timing.py around the benchmark's own timing.  One process, one model, one optimizer; the batches
+of a case are made once, staged in pinned memory, and every contender walks the same list.  A contender's time is dp.timed_steps (the benchmark's timing: --warmup untimed steps, then --steps steps between device
 synchronisations) and the contenders alternate within each of --rounds rounds; reported is ms per step, median [min, max] over the rounds,
 every round listed.  The batches differ in their token counts, so with total_multiple = 1 nearly every step of a round is a GEMM shape the
 process has not run before in round 1 and a repeated one afterwards: round 1 is what a real epoch sees.  The optimizer keeps stepping
@@ -20,8 +20,9 @@ through all of it, so the "last loss" of two contenders is of the same batch und
 import argparse
 import os
 import socket
-import statistics
 import sys
+
+import timing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -112,11 +113,8 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     model, net, opt, dist = build(args.layers, dev)
-    lines = []
-
-    def say(text=""):
-        print(text, flush=True)
-        lines.append(text)
+    log = timing.Log()
+    say = log.say
 
     say(f"time_train_packed.py: {torch.cuda.get_device_name(0)}, torch {torch.__version__}; {args.layers} layers, C = {N_EMBD}, dim_ffn = "
         f"{DIM_FFN}, {3 * args.per_gpu_batch} rows of T = {T} a step, grad checkpointing, DDP world size 1; {args.rounds} rounds of "
@@ -150,20 +148,15 @@ def main():
             one = contender(name)
             one()
         torch.cuda.synchronize()
-        times = {name: [] for name in batches}
-        for _ in range(args.rounds):
-            for name in batches:
-                elapsed = timed_steps(contender(name), args.steps, args.warmup, torch.cuda.synchronize, dist, dev)
-                times[name].append(elapsed * 1e3 / args.steps)
-        base = statistics.median(times["padded"])
+        ms_per_step = lambda name: timed_steps(contender(name), args.steps, args.warmup, torch.cuda.synchronize, dist, dev) * 1e3 / args.steps
+        times = timing.alternate({name: name for name in batches}, ms_per_step, args.rounds)
+        base = timing.median(times["padded"])
         for name, ts in times.items():
-            med = statistics.median(ts)
+            med = timing.median(ts)
             say(f"  {name:<11} {med:8.2f} [{min(ts):8.2f}, {max(ts):8.2f}]   x{med / base:5.3f} of padded   rounds: "
                 + ", ".join(f"{t:.2f}" for t in ts) + f"   last loss {float(last[name]):.4f}")
     dist.destroy_process_group()
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    log.write(args.out)
 
 
 if __name__ == "__main__":

@@ -7,18 +7,16 @@
   (d) dense-full      the dense op on the same tensor viewed as [48, 512, C]
   (e) dense-full-2    (d) again, as a contender of its own: the spread the dense op shows against itself in this run
 
-All keep their checkpoints from the forward to the backward, as the autograd functions do.  Method of tools/time_wkv5.py: everything is
-allocated first, each contender is warmed for --warm seconds, then --repeats rounds alternate the contenders, each round timing --iters
-back-to-back calls per phase with device events.
+All keep their checkpoints from the forward to the backward, as the autograd functions do.  Method: tools/timing.py (--warm seconds
+of warm-up each, --repeats rounds, --iters calls per timing of the forward, the backward and the step).
 
     python tools/time_varlen.py [--out profiles/varlen_time.txt]
 """
 import argparse
 import os
-import statistics
 import sys
-import time
 
+import timing
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,11 +39,8 @@ def main():
     a = ap.parse_args()
     B, T, H = a.B, a.T, a.H
     C = 64 * H
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
+    log = timing.Log()
+    say = log.say
 
     g = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s, scale=1.0: (torch.randn(*s, generator=g, device="cuda") * scale).to(bf)
@@ -80,7 +75,7 @@ def main():
                   "(e) dense-full-2": dense(ckpts[2])}
 
     prop = torch.cuda.get_device_properties(0)
-    say(f"device: {prop.name}, {prop.multi_processor_count} CUs; torch {torch.__version__}; hip {torch.version.hip}")
+    say(timing.device_header())
     say(f"shape: {B} sequences, T={T}, C={C}, H={H}; ragged lengths {int(lens.min())}..{int(lens.max())}, total {total_r} of {B * T} tokens "
         f"({100.0 * total_r / (B * T):.1f} % fill); 64-token groups: {int(((lens + 63) // 64).sum())} ragged vs {B * ((T + 63) // 64)} padded")
     say(f"{a.iters} calls per timing, {a.repeats} alternated repeats, {a.warm:.1f} s warm-up each")
@@ -92,35 +87,15 @@ def main():
     say(f"packed-full y == dense y bit for bit: {bool(torch.equal(yf.view(B, T, C), yd))}")
     del yd, yf
 
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / a.iters
-
-    for name, (fwd, bwd) in contenders.items():                          # warm by time
-        t0 = time.time()
-        while time.time() - t0 < a.warm:
-            fwd()
-            bwd()
-        torch.cuda.synchronize()
-    res = {name: {"fwd": [], "bwd": [], "step": []} for name in contenders}
-    for rep in range(a.repeats):
-        for name, (fwd, bwd) in contenders.items():
-            fwd()
-            res[name]["fwd"].append(timed(fwd))
-            res[name]["bwd"].append(timed(bwd))
-            res[name]["step"].append(timed(lambda: (fwd(), bwd())))
+    for fwd, bwd in contenders.values():
+        timing.warm(lambda: (fwd(), bwd()), seconds=a.warm)
+    rounds = timing.alternate(contenders, lambda pair: timing.phase_times(*pair, a.iters), a.repeats)
+    res = {name: dict(zip(("fwd", "bwd", "step"), zip(*rows))) for name, rows in rounds.items()}
     for name, d in res.items():
-        for ph in ("fwd", "bwd", "step"):
-            xs = d[ph]
-            say(f"{name:18s} {ph:4s} ms: " + " ".join(f"{x:7.3f}" for x in xs) +
-                f"   median {statistics.median(xs):7.3f}  min {min(xs):7.3f}  max {max(xs):7.3f}")
+        for ph, xs in d.items():
+            say(f"{name:18s} {ph:4s} ms: " + timing.values_and_stats(xs, 7, 3))
     say()
-    med = lambda n, ph: statistics.median(res[n][ph])
+    med = lambda n, ph: timing.median(res[n][ph])
     A, Bn, Cn, D, E = list(contenders)
     for ph in ("fwd", "bwd", "step"):
         say(f"ragged {ph}: (a) packed {med(A, ph):.3f} ms [{min(res[A][ph]):.3f}, {max(res[A][ph]):.3f}] vs (b) padded {med(Bn, ph):.3f} ms "
@@ -136,9 +111,7 @@ def main():
             f"{'(c) within the dense range' if lo <= med(Cn, ph) <= hi or med(Cn, ph) <= hi else '(c) OUTSIDE the dense range'}"
             f"; difference {diff * 1e3:+.1f} us = {diff * 1e6 / (B * H / prop.multi_processor_count):+.0f} ns per row of a CU "
             f"({B * H / prop.multi_processor_count:.1f} rows per CU)")
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    log.write(a.out)
 
 
 if __name__ == "__main__":

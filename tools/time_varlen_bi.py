@@ -8,18 +8,16 @@ stream's own projections under rev_mask = ALL) on a ragged batch, H=32, C=2048, 
   (d) packed-pair-full  the packed pair on 48 full rows of 512 against
   (e) dense-pair-full   the dense pair on the same tensor viewed as [48, 512, C]
 
-All keep their checkpoints from the forward to the backward.  Method of tools/time_varlen.py: everything is allocated first, each
-contender is warmed for --warm seconds, then --repeats rounds alternate the contenders, each round timing --iters back-to-back calls
-per phase with device events; medians with min and max.
+All keep their checkpoints from the forward to the backward.  Method: tools/timing.py (--warm seconds of warm-up each, --repeats
+rounds, --iters calls per timing of the forward, the backward and the step).
 
     python tools/time_varlen_bi.py [--out profiles/varlen_bi_time.txt]
 """
 import argparse
 import os
-import statistics
 import sys
-import time
 
+import timing
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,11 +40,8 @@ def main():
     a = ap.parse_args()
     B, T, H = a.B, a.T, a.H
     C = 64 * H
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
+    log = timing.Log()
+    say = log.say
 
     g = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s, scale=1.0: (torch.randn(*s, generator=g, device="cuda") * scale).to(bf)
@@ -99,9 +94,8 @@ def main():
                   "(c) dense-pair": dense_pair(rev_r), "(d) packed-pair-full": packed_pair(full, cu_f, B * T, rev_f),
                   "(e) dense-pair-full": dense_pair(rev_f)}
 
-    prop = torch.cuda.get_device_properties(0)
     groups = int(((lens + 63) // 64).sum())
-    say(f"device: {prop.name}, {prop.multi_processor_count} CUs; torch {torch.__version__}; hip {torch.version.hip}")
+    say(timing.device_header())
     say(f"shape: 2 problems x {B} sequences, T={T}, C={C}, H={H}; ragged lengths {int(lens.min())}..{int(lens.max())}, total {total_r} of "
         f"{B * T} tokens ({100.0 * total_r / (B * T):.1f} % fill); 64-token groups: {groups} ragged vs {B * ((T + 63) // 64)} padded")
     say(f"{a.iters} calls per timing, {a.repeats} alternated repeats, {a.warm:.1f} s warm-up each")
@@ -110,35 +104,15 @@ def main():
     yp = contenders["(d) packed-pair-full"][0]()
     say(f"packed-pair-full y == dense-pair y bit for bit: {all(bool(torch.equal(p.view(B, T, C), d)) for p, d in zip(yp, yd))}")
 
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / a.iters
-
-    for name, (fwd, bwd) in contenders.items():
-        t0 = time.time()
-        while time.time() - t0 < a.warm:
-            fwd()
-            bwd()
-        torch.cuda.synchronize()
-    res = {name: {"fwd": [], "bwd": [], "step": []} for name in contenders}
-    for rep in range(a.repeats):
-        for name, (fwd, bwd) in contenders.items():
-            fwd()
-            res[name]["fwd"].append(timed(fwd))
-            res[name]["bwd"].append(timed(bwd))
-            res[name]["step"].append(timed(lambda: (fwd(), bwd())))
+    for fwd, bwd in contenders.values():
+        timing.warm(lambda: (fwd(), bwd()), seconds=a.warm)
+    rounds = timing.alternate(contenders, lambda pair: timing.phase_times(*pair, a.iters), a.repeats)
+    res = {name: dict(zip(("fwd", "bwd", "step"), zip(*rows))) for name, rows in rounds.items()}
     for name, d in res.items():
-        for ph in ("fwd", "bwd", "step"):
-            xs = d[ph]
-            say(f"{name:22s} {ph:4s} ms: " + " ".join(f"{x:7.3f}" for x in xs) +
-                f"   median {statistics.median(xs):7.3f}  min {min(xs):7.3f}  max {max(xs):7.3f}")
+        for ph, xs in d.items():
+            say(f"{name:22s} {ph:4s} ms: " + timing.values_and_stats(xs, 7, 3))
     say()
-    med = lambda n, ph: statistics.median(res[n][ph])
+    med = lambda n, ph: timing.median(res[n][ph])
     A, Bn, Cn, D, E = list(contenders)
     for ph in ("fwd", "bwd", "step"):
         say(f"ragged {ph}: (a) packed pair {med(A, ph):.3f} ms, (b) two calls {med(Bn, ph):.3f} ms, (c) dense pair padded {med(Cn, ph):.3f} ms: "
@@ -147,9 +121,7 @@ def main():
     for ph in ("fwd", "bwd", "step"):
         say(f"full {ph}: (d) packed pair {med(D, ph):.3f} ms [{min(res[D][ph]):.3f}, {max(res[D][ph]):.3f}] vs (e) dense pair {med(E, ph):.3f} ms "
             f"[{min(res[E][ph]):.3f}, {max(res[E][ph]):.3f}]: {100.0 * (med(D, ph) / med(E, ph) - 1.0):+.1f} %")
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    log.write(a.out)
 
 
 if __name__ == "__main__":

@@ -4,19 +4,17 @@
   (b) wkv6-scan  w expanded to [B,T,C], the exact WKV6 scan kernels (WKV6_ALGO_SCAN), gw summed over batch and time
   (c) wkv6-chunk the same composition on the chunked MFMA kernels (the library's default WKV6 path, checkpoints kept)
 
-Each contender's forward, backward and step (forward + backward) are timed with device events: everything is allocated first,
-each contender is warmed for --warm seconds, then --repeats rounds alternate the contenders, each round timing --iters back-to-back
-calls per phase with no idle gap.  Also printed: the bf16 report of each contender's gw [H,N] against the WKV6 scan kernels in
+Each contender's forward, backward and step (forward + backward) are timed.  Method: tools/timing.py (--warm seconds of warm-up each,
+--repeats rounds, --iters calls per timing of each phase).  Also printed: the bf16 report of each contender's gw [H,N] against the WKV6 scan kernels in
 fp32 I/O reduced in fp64 (oracle/contract.py: bf16_report_torch, floor 0.1).
 
     python tools/time_wkv5.py [--out profiles/wkv5_time.txt]
 """
 import argparse
 import os
-import statistics
 import sys
-import time
 
+import timing
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,11 +38,8 @@ def main():
     a = ap.parse_args()
     B, T, H = a.B, a.T, a.H
     C = 64 * H
-    lines = []
-
-    def say(s=""):
-        print(s, flush=True)
-        lines.append(s)
+    log = timing.Log()
+    say = log.say
 
     g = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s, scale=1.0: (torch.randn(*s, generator=g, device="cuda") * scale).to(bf)
@@ -75,8 +70,7 @@ def main():
     contenders = {"(a) wkv5": (a_fwd, a_bwd), "(b) wkv6-scan": (lambda: w6_fwd("scan"), lambda: w6_bwd("scan")),
                   "(c) wkv6-chunk": (lambda: w6_fwd(None), lambda: w6_bwd(None))}
 
-    prop = torch.cuda.get_device_properties(0)
-    say(f"device: {prop.name}, {prop.multi_processor_count} CUs; torch {torch.__version__}; hip {torch.version.hip}")
+    say(timing.device_header())
     say(f"shape: B={B} T={T} C={C} H={H}; {a.iters} calls per timing, {a.repeats} alternated repeats, {a.warm:.1f} s warm-up each")
     say("bytes per token-channel: wkv5 fwd 8 (r,k,v in; y out), bwd 14 (r,k,v,gy in; gr,gk,gv out); wkv6 fwd 10, bwd 18")
     say()
@@ -96,47 +90,25 @@ def main():
             f"   | gu: rel-rms {rms_u:.2e}, {off_u * 100:.1f}%, max {ulps_u:.2f} ulp")
     say()
 
-    def timed(fn):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / a.iters
-
-    for name, (fwd, bwd) in contenders.items():                          # warm by time
-        t0 = time.time()
-        while time.time() - t0 < a.warm:
-            fwd()
-            bwd()
-        torch.cuda.synchronize()
-    res = {name: {"fwd": [], "bwd": [], "step": []} for name in contenders}
-    for rep in range(a.repeats):
-        for name, (fwd, bwd) in contenders.items():
-            fwd()
-            res[name]["fwd"].append(timed(fwd))
-            res[name]["bwd"].append(timed(bwd))
-            res[name]["step"].append(timed(lambda: (fwd(), bwd())))
+    for fwd, bwd in contenders.values():
+        timing.warm(lambda: (fwd(), bwd()), seconds=a.warm)
+    rounds = timing.alternate(contenders, lambda pair: timing.phase_times(*pair, a.iters), a.repeats)
+    res = {name: dict(zip(("fwd", "bwd", "step"), zip(*rows))) for name, rows in rounds.items()}
     tc = B * T * C
     for name, d in res.items():
-        for ph in ("fwd", "bwd", "step"):
-            xs = d[ph]
-            say(f"{name:15s} {ph:4s} ms: " + " ".join(f"{x:7.3f}" for x in xs) +
-                f"   median {statistics.median(xs):7.3f}  min {min(xs):7.3f}  max {max(xs):7.3f}")
+        for ph, xs in d.items():
+            say(f"{name:15s} {ph:4s} ms: " + timing.values_and_stats(xs, 7, 3))
     say()
     for name, d in res.items():
-        mf, mb, ms = (statistics.median(d[ph]) for ph in ("fwd", "bwd", "step"))
+        mf, mb, ms = (timing.median(d[ph]) for ph in ("fwd", "bwd", "step"))
         say(f"{name:15s} median: fwd {tc * 8 / mf / 1e9:6.3f} TB/s of 8 B/token-channel, bwd {tc * 14 / mb / 1e9:6.3f} TB/s of 14 B, "
             f"step {B * T / ms / 1e3:8.2f} Mtok/s")
     ra, rb = res["(a) wkv5"], res["(b) wkv6-scan"]
     for ph in ("fwd", "bwd", "step"):
-        say(f"acceptance {ph}: (a) median {statistics.median(ra[ph]):.3f} ms [{min(ra[ph]):.3f}, {max(ra[ph]):.3f}] vs "
-            f"(b) median {statistics.median(rb[ph]):.3f} ms [{min(rb[ph]):.3f}, {max(rb[ph]):.3f}] -> "
-            f"{'(a) not slower' if statistics.median(ra[ph]) <= max(rb[ph]) else '(a) SLOWER'}")
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+        say(f"acceptance {ph}: (a) median {timing.median(ra[ph]):.3f} ms [{min(ra[ph]):.3f}, {max(ra[ph]):.3f}] vs "
+            f"(b) median {timing.median(rb[ph]):.3f} ms [{min(rb[ph]):.3f}, {max(rb[ph]):.3f}] -> "
+            f"{'(a) not slower' if timing.median(ra[ph]) <= max(rb[ph]) else '(a) SLOWER'}")
+    log.write(a.out)
 
 
 if __name__ == "__main__":
