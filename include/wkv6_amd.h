@@ -520,6 +520,48 @@ int rwkv6_sample_slots_fp16(int n_seq, int V, int ld, const void* logits, float*
                             const int* slot_out, const float* params, const float* u, int* tokens, float* logprob, void* stream);
 int rwkv6_sample_slots_fp32(int n_seq, int V, int ld, const void* logits, float* occ_pool, int n_slots, const int* slot,
                             const int* slot_out, const float* params, const float* u, int* tokens, float* logprob, void* stream);
+/* ---- beam-search candidates on the rows of a packed decode step (forward only; csrc/wkv6_beam.hip): the reference runs beam search on the
+ * host, one request at a time, with a log-softmax and a top-k over every beam's row and a clone of every state list per beam and token
+ * (src/model_run.py:1317-1518); here one call gives, for every request (group) of a serving batch, the K best (parent row, token)
+ * continuations by cumulative log-probability, and the host reads nothing.  The states fork through the slot pools
+ * (rwkv6_forward_varlen_snap_*: several children read one parent slot and write slots of their own).
+ *   logits [n_rows,ld] in the entry point's type, only columns < V count (ld % 8 == 0, ld >= V, 1 <= V <= 65536: a padded head);
+ *   cum fp32 [n_rows]: the rows' running scores;  cu_rows int32 [n_groups + 1] on the device, never read by the host, every entry clamped
+ *   into [0, n_rows]: group g owns rows cu_rows[g] .. cu_rows[g+1] - 1, of which at most the first 64 are considered;  K in [1, 64];
+ *   occ_pool fp32 [n_slots,ld] (the sampler's occurrence counts), slot int32 [n_rows], penalty fp32 [n_groups]: all three NULL -- no
+ *   penalty; with occ_pool and penalty, slot may be NULL (slot = row index, n_slots >= n_rows);
+ *   parent, token int32 [n_groups,K], score fp32 [n_groups,K];  workspace: rwkv6_beam_candidates_workspace_bytes(n_rows, K) bytes (0 for
+ *   an n_rows < 1 or a K outside [1, 64]), written and read by the call, nothing in it outlives the call.
+ * Row r of group g with p = penalty[g] and o = occ_pool[slot[r]] (a slot outside the pool: o = 0), all values fp32, rows independent:
+ *   1. a row with cum[r] == -inf is dead: its logits are not read (the dead rows of a fixed-shape search hold garbage) and it gives no
+ *      candidate.
+ *   2. a live row with a NaN or +inf among its V logits, no finite logit, a NaN or +inf cum[r], or a negative or non-finite p is poisoned
+ *      and gives no candidate; its neighbours are unaffected.
+ *   3. lp[n] = (z[n] - m) - L with m = max z and L = log sum exp(z - m).
+ *   4. where p != 1 and o[n] > 0: lp[n] = lp[n] < 0 ? lp[n] * p : lp[n] / p (RepetitionPenaltyLogitsProcessor of
+ *      src/logits_processors.py on log-probabilities; 0 / 0 counts as 0).
+ *   5. s[n] = cum[r] + lp[n].  A -inf logit is never a candidate, nor is a score that comes out as -inf.
+ *   6. the candidates (r, n) of the group are ordered by (s descending, r ascending, n ascending) and the first K go out: parent = r (the
+ *      absolute row index), token = n, score = s; missing entries are parent = token = -1, score = -inf.
+ * The denominator of 3. is held as the sum of the integers floor(exp(z - m) * 2^46), which is exact in any order, and L is the log of it
+ * taken once per row in double and rounded to fp32: a row gives the same bits alone or in a batch, and the same call gives the same bits
+ * every time.  No atomics on floats.  Slot numbers are judged on the device before an address is formed from them.  Two launches (one
+ * workgroup per row, one wave per group).  Outputs and workspace may not overlap the inputs.
+ * Refused before any launch, in this order: (1) WKV6_EINVAL -- n_rows, V or n_groups < 1, ld < V or ld % 8, K outside [1, 64], with an
+ * occ_pool n_slots < 1 or slot == NULL with n_slots < n_rows, logits or occ_pool not 16-byte aligned, any other pointer (workspace
+ * included) not 4-byte aligned, parent, token, score or the workspace overlapping an input; (2) WKV6_EUNSUPPORTED -- V > 65536;
+ * (3) WKV6_ENULL -- a NULL logits, cum, cu_rows, parent, token, score or workspace, occ_pool without penalty or penalty without occ_pool,
+ * slot without occ_pool; (4) WKV6_EWORKSPACE -- workspace_bytes below rwkv6_beam_candidates_workspace_bytes(n_rows, K). */
+size_t rwkv6_beam_candidates_workspace_bytes(int n_rows, int K);
+int rwkv6_beam_candidates_bf16(int n_rows, int V, int ld, const void* logits, const float* cum, int n_groups, const int* cu_rows, int K,
+                               const float* occ_pool, int n_slots, const int* slot, const float* penalty, int* parent, int* token,
+                               float* score, void* workspace, size_t workspace_bytes, void* stream);
+int rwkv6_beam_candidates_fp16(int n_rows, int V, int ld, const void* logits, const float* cum, int n_groups, const int* cu_rows, int K,
+                               const float* occ_pool, int n_slots, const int* slot, const float* penalty, int* parent, int* token,
+                               float* score, void* workspace, size_t workspace_bytes, void* stream);
+int rwkv6_beam_candidates_fp32(int n_rows, int V, int ld, const void* logits, const float* cum, int n_groups, const int* cu_rows, int K,
+                               const float* occ_pool, int n_slots, const int* slot, const float* penalty, int* parent, int* token,
+                               float* score, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- sentence pooling on a packed batch (bf16, forward and backward; csrc/wkv6_pool.hip): RwkvForSequenceEmbedding.pooling
  * (src/model_ext.py:1708-1738) without the padded [B,T,C] tensor.
  *   x bf16 [total_T,C], C a multiple of 8;  cu_seqlens int32 [n_seq + 1] and actual_len int32 [n_seq] (or NULL) on the device, never read

@@ -75,6 +75,10 @@ SIGNATURES = {
     "rwkv6_sample_slots_bf16": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
     "rwkv6_sample_slots_fp16": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
     "rwkv6_sample_slots_fp32": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
+    "rwkv6_beam_candidates_workspace_bytes": (_SZ, [_I, _I]),
+    "rwkv6_beam_candidates_bf16": (_I, [_I] * 3 + [_VP] * 2 + [_I, _VP, _I, _VP, _I] + [_VP] * 6 + [_SZ, _VP]),
+    "rwkv6_beam_candidates_fp16": (_I, [_I] * 3 + [_VP] * 2 + [_I, _VP, _I, _VP, _I] + [_VP] * 6 + [_SZ, _VP]),
+    "rwkv6_beam_candidates_fp32": (_I, [_I] * 3 + [_VP] * 2 + [_I, _VP, _I, _VP, _I] + [_VP] * 6 + [_SZ, _VP]),
     "wkv6_pool_packed_forward": (_I, [_L] + [_I] * 3 + [_VP] * 5),
     "wkv6_pool_packed_backward": (_I, [_L] + [_I] * 3 + [_VP] * 5),
     "wkv6_ce_rows_forward_bf16": (_I, [_L, _I, _L] + [_VP] * 9 + [_L, _VP]),

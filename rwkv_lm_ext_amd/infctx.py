@@ -404,3 +404,294 @@ def decode_step_packed(emb, blocks, ln_out, head, tokens, pools, sampling_pool, 
     x = emb(tokens.clamp_min(0)).unsqueeze(0)
     x = step_packed(blocks, x, cu_seqlens, 1, pools, slots, pool_kernels=pool_kernels)
     return sample_packed(head(ln_out(x[0])), sampling_pool, slots, params, u, kernels=kernels)[0]
+
+
+# ---- the other decoding mode: beam search.  A beam that forks is several children reading one parent slot and each writing a slot of its
+# own, which out_slots of step_packed already provides; what is new is the selection (include/wkv6_amd.h: rwkv6_beam_candidates_*) and the
+# small bookkeeping behind it on [n_groups, K] tensors.  Everything is device-side and fixed-shape, so a step can be captured and replayed.
+def _best_first(s, k):
+    """(values [N,k], indices [N,k]) of the k first entries of every row of s [N,M] in the order (s descending, index ascending) -- a topk
+    whose ties, at the boundary included, fall to the lower index; M < k is padded with -inf / M.  No NaN in s."""
+    N, M = s.shape
+    if M < k:
+        s = torch.cat((s, s.new_full((N, k - M), float("-inf"))), 1)
+    kth = s.topk(k, dim=1).values[:, -1:]
+    above, equal = s > kth, s == kth
+    chosen = above | (equal & (equal.cumsum(1) <= k - above.sum(1, keepdim=True)))                     # exactly k a row
+    cols = torch.arange(s.shape[1], device=s.device)
+    idx = torch.where(chosen, s.shape[1] - cols, torch.zeros_like(cols)).topk(k, dim=1).indices        # ... by ascending index
+    v, order = s.gather(1, idx).sort(dim=1, descending=True, stable=True)
+    return v, idx.gather(1, order)
+
+
+def _beam_candidates_eager(logits, cum, cu_rows, K, occ, slots, penalty):
+    """The operation of include/wkv6_amd.h (rwkv6_beam_candidates_*) restated with torch ops, on any device: fp64 log_softmax and scores,
+    the K best of every row and then of every group's rows (the same K as a topk on the flattened group: the group's best lie in the union
+    of its rows' best), ties by row and token.  Reads nothing on the host."""
+    n_rows, V = logits.shape
+    dev, inf = logits.device, float("inf")
+    G = cu_rows.numel() - 1
+    cu = cu_rows.long().clamp(0, n_rows)
+    r = torch.arange(n_rows, device=dev)
+    g = torch.bucketize(r, cu[:G], right=True) - 1                          # the last group that starts at or in front of the row
+    gc = g.clamp_min(0)
+    in_group = (g >= 0) & (r < cu[gc + 1]) & (r - cu[gc] < 64)
+    x, c = logits.float(), cum.float()
+    p = torch.ones(n_rows, device=dev) if penalty is None else penalty.float()[gc]
+    live = in_group & (c > -inf) & (c < inf) & (p >= 0) & (p < inf) & (x < inf).all(1) & (x > -inf).any(1)
+    lp = torch.log_softmax(x.double(), 1)
+    if occ is not None:
+        n_slots = occ.shape[0]
+        src = r if slots is None else slots.long()
+        o = occ[src.clamp(0, n_slots - 1)].masked_fill(~((src >= 0) & (src < n_slots)).unsqueeze(1), 0.0)
+        pd = p.double().unsqueeze(1)
+        pen = torch.where(lp < 0, lp * pd, lp / pd)
+        lp = torch.where((o > 0) & (pd != 1), torch.where(pen == pen, pen, torch.zeros_like(pen)), lp)
+    s = c.double().unsqueeze(1) + lp
+    s = torch.where(live.unsqueeze(1) & (x > -inf) & (s > -inf), s, torch.full_like(s, -inf))
+    row_s, row_tok = _best_first(s, K)                                                                # [n_rows, K]
+    R = min(64, n_rows)
+    rows = cu[:G].unsqueeze(1) + torch.arange(R, device=dev)                                           # [G, R]
+    mine = (rows < cu[1:].unsqueeze(1)).unsqueeze(2)
+    rows = rows.clamp(max=n_rows - 1)
+    flat = torch.where(mine, row_s[rows], torch.full_like(row_s[rows], -inf)).reshape(G, R * K)
+    score, at = _best_first(flat, K)
+    at = at.clamp(max=R * K - 1)
+    none = score == -inf
+    parent = rows.gather(1, at // K).masked_fill(none, -1)
+    token = row_tok[rows].reshape(G, R * K).gather(1, at).masked_fill(none, -1)
+    return parent.int(), token.int(), score.float()
+
+
+def _beam_kernel(logits, cum, cu_rows, occ, slots, penalty, kernels):
+    """Whether mix_op.beam_candidates serves this call (kernels as in _sample_kernel: None where it applies, False never, True it must --
+    then mix_op says what is wrong).  Where it applies it is taken: profiles/beam_time.txt has the kernels ahead of the eager code at
+    every size measured."""
+    if kernels is False:
+        return False
+    if kernels:
+        return True
+    def ints(t):
+        return t is None or (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.is_contiguous() and t.device == logits.device)
+    def floats(t, shape):
+        return (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous()
+                and t.device == logits.device)
+    n_rows, V = logits.shape
+    ld = logits.stride(0)
+    G = cu_rows.numel() - 1 if isinstance(cu_rows, torch.Tensor) else 0
+    return (logits.is_cuda and logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and logits.stride(1) == 1 and ld >= V
+            and ld % 8 == 0 and V <= 65536 and logits.data_ptr() % 16 == 0 and floats(cum, (n_rows,)) and ints(cu_rows) and cu_rows is not None
+            and cu_rows.dim() == 1 and G >= 1 and ints(slots)
+            and (occ is None or (occ.device == logits.device and occ.dtype == torch.float32 and occ.stride(1) == 1 and occ.stride(0) == ld
+                                 and occ.data_ptr() % 16 == 0 and floats(penalty, (G,)) and (slots is not None or occ.shape[0] >= n_rows)))
+            and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (logits, cum, occ, penalty))))
+
+
+def beam_candidates(logits, cum, cu_rows, K, pool=None, slots=None, penalty=None, vocab=None, kernels=None):
+    """(parent int32, token int32, score fp32), each [n_groups, K]: for every group g of rows cu_rows[g] .. cu_rows[g+1] - 1 (int32 on the
+    device, at most the first 64 rows of a group) of logits [n_rows, >= vocab] the K (1..64) best continuations (row, token) by cum[row] +
+    log_softmax(logits[row, :vocab])[token], best first, equal scores by row and then token; missing entries are -1, -1, -inf.  A row with
+    cum == -inf is dead: it is not read and gives nothing.  A poisoned row (NaN or +inf logits, no finite logit, NaN or +inf cum, a
+    negative or non-finite penalty) gives nothing either.  pool (a SamplingPool; vocab is then the pool's) with penalty fp32 [n_groups]:
+    the repetition penalty, on the log-probabilities of the tokens that pool.occ[slots[row]] (slots None: row) counts.
+    include/wkv6_amd.h states the operation.
+    kernels None: the HIP kernels (mix_op.beam_candidates) where they apply (GPU tensors, the row stride of logits a multiple of 8 and
+    equal to the pool's), else the eager restatement, which also serves the CPU; False: always the eager code; True: the kernels, or this
+    raises."""
+    V = pool.vocab if pool is not None else (int(vocab) if vocab is not None else (logits.shape[1] if isinstance(logits, torch.Tensor) else 0))
+    if not (isinstance(logits, torch.Tensor) and logits.dim() == 2 and logits.shape[1] >= V >= 1 and logits.shape[0] >= 1):
+        raise RuntimeError(f"logits must be [n_rows, >= vocab = {V}]")
+    if not (isinstance(K, int) and 1 <= K <= 64):
+        raise RuntimeError(f"K must be an int in [1, 64], got {K!r}")
+    if (pool is None) != (penalty is None) or (slots is not None and pool is None):
+        raise RuntimeError("pool and penalty go together (both None: no penalty), and slots needs them")
+    lg, occ = logits[:, :V], None if pool is None else pool.occ[:, :V]
+    if _beam_kernel(lg, cum, cu_rows, occ, slots, penalty, kernels):
+        from . import mix_op
+        return mix_op.beam_candidates(lg, cum, cu_rows, K, occ_pool=occ, slots=slots, penalty=penalty)
+    with torch.no_grad():
+        return _beam_candidates_eager(lg, cum, cu_rows, K, occ, slots, penalty)
+
+
+@dataclass
+class BeamSearch:
+    """The state of a beam search over n_groups requests with W beams each, of fixed shape: n_rows = n_groups * W rows always, row
+    g * W + j the j-th beam of request g, a dead row carrying cum = -inf.  Everything is a device tensor updated in place, so a captured
+    beam_step_packed replays: `step` counts on the device and selects the half of the slots in use.
+
+    tokens int32 [n_rows]: the token every row feeds next;  cum fp32 [n_rows]: its cumulative log-probability;
+    slots_in / slots_out int32 [n_rows]: where a row's carried state is read and where it is left.  Request g owns the 2 W slots
+      slot_base + 2 W g .. + 2 W - 1 of every pool, in two halves: step t leaves row j's state in half t % 2, slot j, and the children read
+      it from there at step t + 1, whichever of them and however many.  At step 0 every slots_in entry names the request's prompt slot,
+      which is only ever read;
+    slots_occ int32 [n_rows]: the row's occurrence counts in a SamplingPool (the prompt slot at step 0, then the row's slots_out);
+    hist_parent / hist_token int32 [max_new_tokens, n_rows]: row r of step t + 1 continues row hist_parent[t, r] of step t with hist_token[t, r];
+    hyp_score fp32 / hyp_step, hyp_row int32 [n_groups, W]: the finished hypotheses, best first (-inf: none): cum / len^length_penalty
+      with len = hyp_step + 1 (the eos counted, as the reference does), the step at which the eos was chosen and the row that chose it;
+    done bool [n_groups]."""
+    n_groups: int
+    W: int
+    K: int
+    max_new_tokens: int
+    length_penalty: float
+    slot_base: int
+    eos_ids: torch.Tensor
+    penalty: torch.Tensor
+    step: torch.Tensor
+    tokens: torch.Tensor
+    cum: torch.Tensor
+    cu_rows: torch.Tensor
+    cu_tokens: torch.Tensor
+    slots_in: torch.Tensor
+    slots_out: torch.Tensor
+    slots_occ: torch.Tensor
+    hist_parent: torch.Tensor
+    hist_token: torch.Tensor
+    hyp_score: torch.Tensor
+    hyp_step: torch.Tensor
+    hyp_row: torch.Tensor
+    done: torch.Tensor
+
+    @property
+    def n_rows(self):
+        return self.n_groups * self.W
+
+    @staticmethod
+    def create(n_groups, W, max_new_tokens, eos_ids, length_penalty, repetition_penalty, tokens, prompt_slots, slot_base, device, K=None):
+        """tokens int [n_groups]: the token every request feeds first (the last one of its prompt);  prompt_slots int [n_groups]: the slot
+        the rest of the prompt was prefilled into, outside slot_base .. slot_base + 2 W n_groups - 1;  K (None: (1 + len(eos_ids)) * W, the
+        reference's reserve_beam_size, which is also the least allowed): candidates taken per request and step, at most 64."""
+        eos = [int(e) for e in eos_ids]
+        K = (1 + len(eos)) * W if K is None else int(K)
+        if n_groups < 1 or W < 1 or max_new_tokens < 1:
+            raise ValueError("n_groups, W and max_new_tokens must be at least 1")
+        if not (1 + len(eos)) * W <= K <= 64:
+            raise ValueError(f"K must be in [(1 + len(eos_ids)) * W, 64] = [{(1 + len(eos)) * W}, 64] so that W continuations always remain, got {K}")
+        n_rows = n_groups * W
+        i32 = dict(dtype=torch.int32, device=device)
+        first = torch.arange(n_rows, device=device) % W == 0
+        neg = torch.full((n_rows,), float("-inf"), device=device)
+        prompt = torch.as_tensor(prompt_slots, **i32).reshape(n_groups)
+        return BeamSearch(
+            n_groups=n_groups, W=W, K=K, max_new_tokens=int(max_new_tokens), length_penalty=float(length_penalty), slot_base=int(slot_base),
+            eos_ids=torch.tensor(eos, dtype=torch.int32, device=device), penalty=torch.full((n_groups,), float(repetition_penalty), device=device),
+            step=torch.zeros((), dtype=torch.int64, device=device),
+            tokens=torch.as_tensor(tokens, **i32).reshape(n_groups).repeat_interleave(W).contiguous(),
+            cum=torch.where(first, torch.zeros_like(neg), neg),
+            cu_rows=torch.arange(0, n_rows + 1, W, **i32), cu_tokens=torch.arange(n_rows + 1, **i32),
+            slots_in=prompt.repeat_interleave(W).contiguous(), slots_out=_beam_half(n_groups, W, slot_base, 0, device),
+            slots_occ=prompt.repeat_interleave(W).contiguous(),
+            hist_parent=torch.zeros((max_new_tokens, n_rows), **i32), hist_token=torch.full((max_new_tokens, n_rows), -1, **i32),
+            hyp_score=torch.full((n_groups, W), float("-inf"), device=device), hyp_step=torch.zeros((n_groups, W), **i32),
+            hyp_row=torch.zeros((n_groups, W), **i32), done=torch.zeros(n_groups, dtype=torch.bool, device=device))
+
+
+def _beam_half(n_groups, W, slot_base, half, device):
+    """int32 [n_groups * W]: row g * W + j -> slot_base + 2 W g + W half + j; half: 0, 1 or a device tensor of one element"""
+    r = torch.arange(n_groups * W, device=device)
+    return (slot_base + 2 * W * (r // W) + W * half + r % W).int()
+
+
+def beam_advance(state, parent, token, score, sampling_pool=None):
+    """One step of the bookkeeping, in place on `state`, from the candidates (parent, token, score), each [n_groups, K] best first, of
+    beam_candidates on the step's logits.  Of a request's candidates, those that end in an eos id and rank among the first W go to its
+    hypothesis table with cum / len^length_penalty (the worst entry leaves a full table; an equal newcomer does not displace it); the first
+    W others become the next rows: token, cum, the parent's slots_out as slots_in, the other half as slots_out.  A request is done when its
+    table is full and its worst entry is at least (best cum of the step) / len^length_penalty (BeamHypothesis.is_done of the reference with
+    early_stopping=False); its rows, and the rows that found no continuation, are dead: cum = -inf.  With a SamplingPool a child's
+    occurrence row is its parent's with the child's token counted, in the child's slots_out of the next step.  Nothing is read on the host."""
+    G, W, K = state.n_groups, state.W, state.K
+    if not all(isinstance(t, torch.Tensor) and tuple(t.shape) == (G, K) for t in (parent, token, score)):
+        raise RuntimeError(f"parent, token and score must be [n_groups = {G}, K = {K}]")
+    dev, inf = score.device, float("inf")
+    with torch.no_grad():
+        parent, token, score = parent.long(), token.long(), score.float()
+        t = state.step.clamp(max=state.max_new_tokens - 1)
+        length = (t + 1).float() ** state.length_penalty
+        valid = parent >= 0
+        eos = valid & (token.unsqueeze(2) == state.eos_ids.long().view(1, 1, -1)).any(2)
+        # ---- the first W continuations, in candidate order
+        cont = valid & ~eos
+        nth = cont.cumsum(1)
+        dest = torch.where(cont & (nth <= W), nth - 1, torch.full_like(nth, W))
+        at = torch.full((G, W + 1), K, dtype=torch.long, device=dev).scatter_(1, dest, torch.arange(K, device=dev).expand(G, K))[:, :W]
+        have = at < K
+        at = at.clamp(max=K - 1)
+        # ---- the hypothesis table: the old entries in front, so that a stable sort keeps them ahead of equal newcomers
+        n_new = min(W, K)
+        new_score = torch.where(eos[:, :n_new], score[:, :n_new] / length, torch.full_like(score[:, :n_new], -inf))
+        both = torch.cat((state.hyp_score, new_score), 1)
+        hyp_score, order = both.sort(dim=1, descending=True, stable=True)
+        hyp_score, order = hyp_score[:, :W], order[:, :W]
+        hyp_step = torch.cat((state.hyp_step, t.int().expand(G, n_new)), 1).gather(1, order)
+        hyp_row = torch.cat((state.hyp_row, parent[:, :n_new].int()), 1).gather(1, order)
+        best = score[:, 0]                                                      # -inf where the request has no candidate at all
+        done = state.done | ((hyp_score[:, W - 1] > -inf) & (hyp_score[:, W - 1] >= best / length))
+        # ---- the next rows
+        alive = (have & ~done.unsqueeze(1)).reshape(-1)
+        first_row = (torch.arange(G, device=dev) * W).unsqueeze(1)
+        new_parent = torch.where(have, parent.gather(1, at), first_row.expand(G, W)).reshape(-1)
+        new_token = torch.where(have, token.gather(1, at), torch.zeros_like(at)).reshape(-1)
+        new_cum = torch.where(alive, score.gather(1, at).reshape(-1), torch.full((G * W,), -inf, device=dev))
+        slots_in = state.slots_out[new_parent]
+        slots_out = _beam_half(G, W, state.slot_base, (state.step + 1) % 2, dev)
+        if sampling_pool is not None:
+            occ = sampling_pool.occ
+            rows = occ[state.slots_occ[new_parent].long()]
+            rows.scatter_add_(1, new_token.unsqueeze(1), alive.float().unsqueeze(1))
+            occ.index_copy_(0, slots_out.long(), rows)
+        state.hist_parent.index_copy_(0, t.view(1), new_parent.int().unsqueeze(0))
+        state.hist_token.index_copy_(0, t.view(1), torch.where(alive, new_token, torch.full_like(new_token, -1)).int().unsqueeze(0))
+        state.hyp_score.copy_(hyp_score); state.hyp_step.copy_(hyp_step); state.hyp_row.copy_(hyp_row); state.done.copy_(done)
+        state.tokens.copy_(new_token); state.cum.copy_(new_cum)
+        state.slots_in.copy_(slots_in); state.slots_out.copy_(slots_out); state.slots_occ.copy_(slots_out)
+        state.step.add_(1)
+    return state
+
+
+def beam_step_packed(emb, blocks, ln_out, head, state, pools, sampling_pool=None, pool_kernels=None, kernels=None):
+    """One step of a beam search on every request of a serving batch: emb(tokens) -> step_packed (one token per row, slots = slots_in,
+    out_slots = slots_out: the fork) -> ln_out -> head -> beam_candidates -> beam_advance.  Returns the step's candidates (parent, token,
+    score).  sampling_pool: the repetition penalty of state.penalty on the tokens a beam has counted there (the prompt's counts in the
+    prompt slot, if the caller put them there).  pool_kernels as in step_packed, kernels as in beam_candidates.  Nothing is read on the
+    host, so the step can be captured in a graph and replayed; `state` carries everything from one replay to the next."""
+    x = emb(state.tokens.clamp_min(0)).unsqueeze(0)
+    x = step_packed(blocks, x, state.cu_tokens, 1, pools, state.slots_in, out_slots=state.slots_out, pool_kernels=pool_kernels)
+    logits = head(ln_out(x[0]))
+    penalised = sampling_pool is not None
+    out = beam_candidates(logits, state.cum, state.cu_rows, state.K, pool=sampling_pool, slots=state.slots_occ if penalised else None,
+                          penalty=state.penalty if penalised else None, kernels=kernels)
+    beam_advance(state, *out, sampling_pool=sampling_pool)
+    return out
+
+
+def beam_finalize(state, n_return):
+    """(sequences int32 [n_groups, n_return, max_new_tokens] padded with -1, lengths int32 [n_groups, n_return], scores fp32 [n_groups,
+    n_return]), best first: of every request the n_return best of its finished hypotheses and its open beams together, as the reference
+    pools them -- an open beam with cum / len^length_penalty, len the steps taken.  A hypothesis' sequence does not hold its eos, as in
+    the reference.  Missing entries have score -inf and length 0.  The parent pointers are walked on the device."""
+    G, W, T = state.n_groups, state.W, state.max_new_tokens
+    dev, inf = state.cum.device, float("inf")
+    with torch.no_grad():
+        steps = state.step.clamp(max=T)
+        open_score = state.cum.view(G, W) / steps.clamp_min(1).float() ** state.length_penalty
+        score = torch.cat((state.hyp_score, open_score), 1)                                  # finished first: they win equal scores
+        length = torch.cat((state.hyp_step.long(), steps.expand(G, W)), 1)
+        row = torch.cat((state.hyp_row.long(), torch.arange(G * W, device=dev).view(G, W)), 1)
+        score, order = score.sort(dim=1, descending=True, stable=True)
+        n = min(n_return, 2 * W)
+        score, order = score[:, :n], order[:, :n]
+        missing = score == -inf
+        length = length.gather(1, order).masked_fill(missing, 0)
+        row = row.gather(1, order)
+        seq = torch.full((G, n, T), -1, dtype=torch.int32, device=dev)
+        for pos in range(T - 1, -1, -1):
+            on = pos < length
+            seq[:, :, pos] = torch.where(on, state.hist_token[pos][row], torch.full_like(row, -1).int())
+            row = torch.where(on, state.hist_parent[pos][row].long(), row)
+        if n < n_return:
+            pad = n_return - n
+            seq = torch.cat((seq, seq.new_full((G, pad, T), -1)), 1)
+            length = torch.cat((length, length.new_zeros((G, pad))), 1)
+            score = torch.cat((score, score.new_full((G, pad), -inf)), 1)
+        return seq, length.int(), score

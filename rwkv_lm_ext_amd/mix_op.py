@@ -337,6 +337,70 @@ def sample_slots(logits, occ_pool, slots, params, u, out_slots=None, want_logpro
     return (tokens, logprob) if want_logprob else tokens
 
 
+# ---- beam-search candidates on rows of logits (include/wkv6_amd.h: rwkv6_beam_candidates_*); inference only: no autograd.  Shapes and types
+# are judged first, the device last (there is no CPU path here: infctx.beam_candidates has the eager one).
+BEAM_MAX_K = 64
+_BEAM_ENTRY = {torch.bfloat16: "rwkv6_beam_candidates_bf16", torch.float16: "rwkv6_beam_candidates_fp16",
+               torch.float32: "rwkv6_beam_candidates_fp32"}
+
+
+def beam_candidates(logits, cum, cu_rows, K, occ_pool=None, slots=None, penalty=None):
+    """(parent int32, token int32, score fp32), each [n_groups, K]: for every group g of rows cu_rows[g] .. cu_rows[g+1] - 1 of logits
+    [n_rows, V] (bf16, fp16 or fp32; a view of the first V columns of a contiguous [n_rows, ld] tensor, ld % 8 == 0, is taken as it is) the
+    K best (row, token) by cum[row] + log_softmax(logits[row])[token], best first, ties by row and then token; missing entries are -1, -1,
+    -inf.  A row with cum == -inf is dead and is not read.  occ_pool fp32 [n_slots, V] (rows ld apart, as the sampler's) with penalty fp32
+    [n_groups] applies the repetition penalty to the log-probabilities of the tokens that row slots[r] (slots None: row r) counts.  The
+    operation is stated in include/wkv6_amd.h.  Nothing is read on the host.  Raises when a gradient is required."""
+    if not (isinstance(logits, torch.Tensor) and logits.dtype in _BEAM_ENTRY and logits.dim() == 2 and logits.shape[0] >= 1
+            and logits.shape[1] >= 1 and logits.stride(1) == 1):
+        raise RuntimeError("logits must be a bf16, fp16 or fp32 tensor [n_rows, V] with unit stride along V")
+    n_rows, V = logits.shape
+    ld = logits.stride(0)
+    if ld < V or ld % 8 or not _rows_in_storage(logits, ld):
+        raise RuntimeError(f"logits rows must lie ld elements apart in memory, ld a multiple of 8 and >= V = {V}: pass the first V columns "
+                           f"of a padded [n_rows, ld] tensor (INTEGRATION.md), got a row stride of {ld}")
+    if V > SAMPLE_MAX_VOCAB:
+        raise RuntimeError(f"beam_candidates: V must be at most {SAMPLE_MAX_VOCAB}, got {V}")
+    if not (isinstance(K, int) and 1 <= K <= BEAM_MAX_K):
+        raise RuntimeError(f"K must be an int in [1, {BEAM_MAX_K}], got {K!r}")
+    if not (isinstance(cum, torch.Tensor) and cum.dtype == torch.float32 and tuple(cum.shape) == (n_rows,) and cum.is_contiguous()):
+        raise RuntimeError(f"cum must be a contiguous fp32 tensor [n_rows = {n_rows}]")
+    _ints(cu_rows, _AT_LEAST_2, None, "cu_rows must be a contiguous int32 tensor [n_groups + 1]")
+    n_groups = cu_rows.numel() - 1
+    if (occ_pool is None) != (penalty is None) or (slots is not None and occ_pool is None):
+        raise RuntimeError("occ_pool and penalty go together (both None: no penalty), and slots needs them")
+    n_slots = 0
+    if occ_pool is not None:
+        if not (isinstance(occ_pool, torch.Tensor) and occ_pool.dtype == torch.float32 and occ_pool.dim() == 2 and occ_pool.shape[0] >= 1
+                and occ_pool.shape[1] == V and occ_pool.stride(1) == 1 and occ_pool.stride(0) == ld and _rows_in_storage(occ_pool, ld)):
+            raise RuntimeError(f"occ_pool must be an fp32 tensor [n_slots, V = {V}] whose rows lie ld = {ld} elements apart, as the rows of "
+                               "logits do (it is used in place, never copied)")
+        n_slots = occ_pool.shape[0]
+        if not (isinstance(penalty, torch.Tensor) and penalty.dtype == torch.float32 and tuple(penalty.shape) == (n_groups,)
+                and penalty.is_contiguous()):
+            raise RuntimeError(f"penalty must be a contiguous fp32 tensor [n_groups = {n_groups}]")
+        if slots is None and n_slots < n_rows:
+            raise RuntimeError("slots = None means slot = row index: the pool must hold n_rows slots")
+        if slots is not None:
+            _check_ints(slots, (n_rows,), "slots")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (logits, cum, occ_pool, penalty)):
+        raise RuntimeError("beam_candidates has no backward: call it under torch.no_grad()")
+    if not logits.is_cuda:
+        raise RuntimeError("logits must be on the GPU (beam_candidates has no CPU path: infctx.beam_candidates has the eager one)")
+    if any(t is not None and t.device != logits.device for t in (cum, cu_rows, occ_pool, slots, penalty)):
+        raise RuntimeError("cum, cu_rows, occ_pool, slots and penalty must be on the device of logits")
+    if logits.data_ptr() % 16 or (occ_pool is not None and occ_pool.data_ptr() % 16):
+        raise RuntimeError("logits and occ_pool must be 16-byte aligned")
+    dev = logits.device
+    parent, token = (torch.empty((n_groups, K), device=dev, dtype=torch.int32) for _ in range(2))
+    score = torch.empty((n_groups, K), device=dev, dtype=torch.float32)
+    ws_bytes = _lib.load().rwkv6_beam_candidates_workspace_bytes(n_rows, K)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    _call(_BEAM_ENTRY[logits.dtype], "beam candidates", dev, n_rows, V, ld, *_ptrs(logits, cum), n_groups, _ptr(cu_rows), K, _ptr(occ_pool),
+          n_slots, *_ptrs(slots, penalty, parent, token, score, ws), ws_bytes)
+    return parent, token, score
+
+
 # ---- sentence pooling on a packed batch (include/wkv6_amd.h: wkv6_pool_packed_*); bf16, GPU, with a backward.  Shapes and types are judged
 # first, the device last (there is no CPU path here: callers.pooling_packed has the eager one).
 class _PoolPacked(torch.autograd.Function):
