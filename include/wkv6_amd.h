@@ -483,6 +483,50 @@ int wkv6_lora_packed_bf16(long total_T, int n_seq, int K, int N, int R, int n_ad
                           const int* cu_seqlens, const int* adapter,
                           const void* x, const void* A_pool, const void* B_pool, const float* scale,
                           void* y, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- the two low-rank pairs in front of the time-mix projections (bf16, forward only; csrc/wkv6_lowrank.hip): the reference forms the
+ * operator's inputs with a chain of small matmuls around its token-shift lerps (src/model.py:435-452); here each pair is two launches.
+ * wkv6_tmix_lerp_lowrank_bf16, with xp[t] the token in front of row t (below) and fp32 arithmetic between the roundings:
+ *     lead[t,k]    = bf16( fmaf(xp[t,k] - x[t,k], maa_x[k], x[t,k]) )                       (never stored)
+ *     low[t,j]     = bf16( tanh( float( bf16( sum_k lead[t,k] W1t[j,k] ) ) ) )              j < 5 D; bf16 [total_T, 5 D] in the workspace
+ *     corr_s[t,n]  = bf16( sum_j low[t, s D + j] W2t[s,n,j] )                               (never stored)
+ *     out[s][t,n]  = bf16( fmaf(xp[t,n] - x[t,n], maa5[s,n] + corr_s[t,n], x[t,n]) )        s = 0..4: the planes w, k, v, r, g
+ * wkv6_decay_lowrank_bf16:
+ *     low[t,j] = bf16( tanh( float( bf16( sum_k xw[t,k] D1t[j,k] ) ) ) ),   w[t,n] = bf16( time_decay[n] + bf16( sum_j low[t,j] D2t[n,j] ) )
+ * These are the rounding points of wkv6_ddlerp_*_forward (NS = 1), a bf16 matmul, tanh, a bf16 matmul and wkv6_ddlerp_*_forward (NS = 5)
+ * in a row; only how the sums inside the two contractions are taken is the kernels' own: the shrink adds the fp32 results of its MFMAs (32
+ * products each) in fp64 and rounds the sum to bf16 once, tanh is taken in fp64 and rounded once; the expand is an fp32 MFMA chain.
+ *   x bf16 [total_T,C];  maa_x bf16 [C];  maa5 bf16 [5,C];  W1t bf16 [5 D,C] and W2t bf16 [5,C,D]: time_maa_w1 and time_maa_w2 in
+ *   nn.Linear layout [out, in], as the LoRA pools are;  out bf16 [5,total_T,C];  D in {32, 64};  C a multiple of 64, at most 4096.
+ *   xw bf16 [rows,C];  D1t bf16 [Dd,C];  D2t bf16 [N,Dd];  time_decay bf16 [N];  w bf16 [rows,N];  Dd in {64, 128};  C and N as C above.
+ * The token in front of a row follows wkv6_ddlerp_slots_forward: row t is the first row of sequence s (the last s with cu_seqlens[s] <= t)
+ * iff cu_seqlens[s] == t and then takes front[slot[s]]; every other row, rows outside every sequence included, takes row t - 1, and
+ * row 0 takes zero if it opens nothing.  front bf16 [n_slots,C], NULL: zero tokens;  slot int32 [n_seq], NULL: slot = sequence index, which
+ * needs n_slots >= n_seq -- this is also how carried tokens [n_seq,C] go in;  a slot outside [0, n_slots) is a zero token.  cu_seqlens ==
+ * NULL is the dense form: total_T % n_seq == 0 and sequence s owns rows [s T, (s + 1) T), T = total_T / n_seq.  The int arrays live on
+ * the device and are never read by the host; the slot is judged before an address is formed from it.
+ * Two launches in stream order, "shrink" and "expand", on the 16x16x32 bf16 MFMAs, tiles of 16 rows, operands straight from global
+ * memory.  Only the expand is an fp32 MFMA chain (one to four steps); in the shrink every MFMA sums its 32 products in fp32 from a zero
+ * accumulator and the steps are added in fp64.  Every output element is its own dot product; the split of C over the waves of a shrink workgroup depends
+ * on C alone and is summed in a fixed order; there are no atomics.  So a row's bits do not depend on the rows that share its tile or its
+ * batch, nor on its place in a tile: a batch equals its sequences served one call at a time, bit for bit.  Rows >= total_T are neither
+ * loaded nor stored and nothing is masked by a multiply: a NaN or Inf in a row of x reaches that row and the row behind it.
+ * Aliasing: out / w may not overlap any input or the workspace.
+ * wkv6_lowrank_workspace_bytes: rows * D_total * 2 rounded up to a multiple of 256, D_total = 5 D or Dd; 0 for a rows or a D_total the
+ * calls refuse.
+ * Refused before any launch, in this order: (1) WKV6_EINVAL -- total_T / rows, n_seq, D or Dd < 1, C or N not a multiple of 64 in
+ * [64, 4096], cu_seqlens == NULL with total_T % n_seq != 0, with a front n_slots < 1 or slot == NULL with n_slots < n_seq;
+ * (2) WKV6_EUNSUPPORTED -- D outside {32, 64}, Dd outside {64, 128}, total_T / rows > INT_MAX; (3) WKV6_ENULL -- a NULL tensor, weight or
+ * workspace (cu_seqlens, front and slot may be NULL); (4) WKV6_EINVAL -- a tensor, weight or the workspace not 16-byte aligned, cu_seqlens
+ * or slot not 4-byte aligned, out / w overlapping an input or the workspace; (5) WKV6_EWORKSPACE -- workspace_bytes below
+ * wkv6_lowrank_workspace_bytes(total_T, 5 D) / (rows, Dd). */
+size_t wkv6_lowrank_workspace_bytes(long rows, int D_total);
+int wkv6_tmix_lerp_lowrank_bf16(long total_T, int n_seq, int C, int D, const int* cu_seqlens,
+                                const void* x, const void* front, int n_slots, const int* slot,
+                                const void* maa_x, const void* W1t, const void* W2t, const void* maa5,
+                                void* out, void* workspace, size_t workspace_bytes, void* stream);
+int wkv6_decay_lowrank_bf16(long rows, int C, int Dd, int N, const void* xw,
+                            const void* D1t, const void* D2t, const void* time_decay,
+                            void* w, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- device-side token sampling with a penalty slot pool (forward only; csrc/wkv6_sample.hip): the reference samples on the host, one
  * sequence at a time (src/model_run.py:1230-1304, src/logits_processors.py); here one launch turns the logits rows of a decode step into
  * token ids, every sequence with its own parameters, and the host reads nothing.  The sequence's decaying token-occurrence counts are a

@@ -72,6 +72,9 @@ SIGNATURES = {
     "wkv6_shift_keep": (_I, [_L] + [_I] * 3 + [_VP] * 3 + [_I, _VP, _I, _VP, _VP, _I, _VP]),
     "wkv6_lora_packed_workspace_bytes": (_SZ, [_L, _I]),
     "wkv6_lora_packed_bf16": (_I, [_L] + [_I] * 5 + [_VP] * 8 + [_SZ, _VP]),
+    "wkv6_lowrank_workspace_bytes": (_SZ, [_L, _I]),
+    "wkv6_tmix_lerp_lowrank_bf16": (_I, [_L] + [_I] * 3 + [_VP] * 3 + [_I] + [_VP] * 7 + [_SZ, _VP]),
+    "wkv6_decay_lowrank_bf16": (_I, [_L] + [_I] * 3 + [_VP] * 6 + [_SZ, _VP]),
     "rwkv6_sample_slots_bf16": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
     "rwkv6_sample_slots_fp16": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),
     "rwkv6_sample_slots_fp32": (_I, [_I] * 3 + [_VP] * 2 + [_I] + [_VP] * 7),

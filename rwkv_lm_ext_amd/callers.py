@@ -104,6 +104,11 @@ class Tmix_x060(nn.Module):
         # forward_bi_b / forward_bi_c with in-kernel reversal: both operator calls of the layer in one launch per pass
         # (wkv.WKV_6_PAIR) instead of two
         self.pair_launch = True
+        # jit_func, inference only: the two low-rank pairs (ddlerp -> W1 -> tanh -> W2 -> ddlerp, and the decay) in two launches each
+        # (mix_op.tmix_inputs, mix_op.decay_lowrank) instead of eleven.  Off by default: the contractions sum in the kernels' own order, so
+        # the outputs differ from the torch matmuls' in their last bits (profiles/lowrank_parity.txt)
+        self.fuse_lowrank = False
+        self._lowrank_cache = None
         d_mix = 64 if n_embd == 4096 else 32                              # TIME_MIX_EXTRA_DIM
         d_decay = 128 if n_embd == 4096 else 64                           # TIME_DECAY_EXTRA_DIM
         z = lambda *s: nn.Parameter(torch.zeros(*s))
@@ -138,6 +143,43 @@ class Tmix_x060(nn.Module):
                     and C % 64 == 0 and C <= 4096)
         return self.fused
 
+    _LOWRANK_PARAMS = ("time_maa_x", "time_maa_w", "time_maa_k", "time_maa_v", "time_maa_r", "time_maa_g", "time_maa_w1", "time_maa_w2",
+                       "time_decay", "time_decay_w1", "time_decay_w2")
+
+    def _lowrank_weights(self):
+        """(maa_x [C], W1t [5 D, C], W2t [5, C, D], maa5 [5, C], D1t [Dd, C], D2t [N, Dd], time_decay [N]): the parameters of the two low-rank
+        pairs as mix_op.tmix_inputs and mix_op.decay_lowrank take them, the matrices in nn.Linear layout [out, in].  The copies are kept on
+        the module and rebuilt when a parameter's data_ptr() or _version changes (an optimizer step, load_state_dict, .to()).  A write
+        through `p.data` (p.data.copy_(...), p.data.mul_(...)) changes neither, and the copies go stale without notice: call
+        drop_lowrank_weights() behind such a write."""
+        params = [getattr(self, n) for n in self._LOWRANK_PARAMS]
+        key = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in params)
+        if self._lowrank_cache is None or self._lowrank_cache[0] != key:
+            with torch.no_grad():
+                C = self.time_maa_x.shape[-1]
+                held = (self.time_maa_x.detach().reshape(C).contiguous(), self.time_maa_w1.detach().t().contiguous(),
+                        self.time_maa_w2.detach().transpose(1, 2).contiguous(), self._maa5().detach().contiguous(),
+                        self.time_decay_w1.detach().t().contiguous(), self.time_decay_w2.detach().t().contiguous(),
+                        self.time_decay.detach().reshape(-1).contiguous())
+            self._lowrank_cache = (key, held)
+        return self._lowrank_cache[1]
+
+    def drop_lowrank_weights(self):
+        """Forget the copies of _lowrank_weights: the next call makes them again (not inside a graph capture)."""
+        self._lowrank_cache = None
+
+    def _use_lowrank(self, x, rev_n):
+        """fuse_lowrank applies: the fused path, nothing asks for a gradient, no reversal map, widths the kernels have."""
+        if not (self.fuse_lowrank and rev_n is None and self._use_fused(x)):
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or any(getattr(self, n).requires_grad for n in self._LOWRANK_PARAMS)):
+            return False
+        from .mix_op import LOWRANK_D, LOWRANK_DD
+        bf, N = torch.bfloat16, self.time_decay.shape[-1]
+        return (x.dtype == bf and all(getattr(self, n).dtype == bf and getattr(self, n).device == x.device for n in self._LOWRANK_PARAMS)
+                and self.time_maa_w2.shape[1] in LOWRANK_D and self.time_decay_w1.shape[1] in LOWRANK_DD
+                and x.shape[-1] % 64 == 0 and x.shape[-1] <= 4096 and N % 64 == 0 and N <= 4096)
+
     def jit_func(self, x, shifted=None, rev_n=None, cu_seqlens=None, shifted0=None, shift_pool=None, slots=None):
         """Inputs of the WKV operator from the block input (src/model.py:435-459): every projection reads its own
         data-dependent blend of x_t and x_{t-1},  x + (x_{t-1} - x) * (maa_s + m_s),  where the five corrections m_s come
@@ -154,32 +196,46 @@ class Tmix_x060(nn.Module):
         sequence's previous call -- instead of zero.
         `shift_pool` (bf16 [n_slots,C]) with `slots` (int32 [n_seq], None: the sequence index), instead of shifted0, on the packed fused
         path without autograd: the token in front of sequence s is shift_pool[slots[s]] (zero for a slot outside the pool), fetched by the
-        kernel itself (mix_op.ddlerp_slots)."""
+        kernel itself (mix_op.ddlerp_slots).
+        With `fuse_lowrank` set, on the fused path, where nothing requires a gradient and rev_n is None, the blends are one call of
+        mix_op.tmix_inputs and the decay one of mix_op.decay_lowrank (four launches for eleven), in the dense form, packed with shifted0 and
+        packed with shift_pool / slots alike; any other call keeps the code below.  The transposed weight copies are kept on the module
+        (_lowrank_weights) and rebuilt when a parameter's data_ptr() or _version changes, so a step that is captured in a graph needs one
+        warm-up call before the capture: the copies must exist, and must not be part of what the graph replays."""
         B, T, C = x.size()
         if cu_seqlens is not None:
             assert B == 1 and shifted is None, "a packed batch is [1,total_T,C]; the carried tokens go in as shifted0 [n_seq,C]"
         else:
             assert shifted0 is None, "shifted0 belongs to a packed batch (cu_seqlens); a dense batch passes `shifted`"
+        lowrank = self._use_lowrank(x, rev_n)               # fuse_lowrank: both low-rank pairs in two launches each (fused path only)
         if shift_pool is not None:
             assert cu_seqlens is not None and shifted0 is None and rev_n is None, \
                 "shift_pool / slots belong to a packed batch (cu_seqlens) and exclude shifted0 and rev_n"
             if not self._use_fused(x):
                 raise RuntimeError("shift_pool / slots exist in the fused (HIP) path only; gather the rows and pass shifted0")
             from . import mix_op
-            lead = mix_op.ddlerp_slots(x, self.time_maa_x.view(1, C), None, shift_pool, slots, cu_seqlens)[0]
-            low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
-            corr = torch.bmm(low, self.time_maa_w2).view(5, B, T, C)
-            xw, xk, xv, xr, xg = mix_op.ddlerp_slots(x, self._maa5(), corr, shift_pool, slots, cu_seqlens).unbind(0)
+            if lowrank:
+                maa_x, W1t, W2t, maa5 = self._lowrank_weights()[:4]
+                xw, xk, xv, xr, xg = mix_op.tmix_inputs(x.contiguous(), maa_x, W1t, W2t, maa5, cu_seqlens, None, shift_pool, slots).unbind(0)
+            else:
+                lead = mix_op.ddlerp_slots(x, self.time_maa_x.view(1, C), None, shift_pool, slots, cu_seqlens)[0]
+                low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
+                corr = torch.bmm(low, self.time_maa_w2).view(5, B, T, C)
+                xw, xk, xv, xr, xg = mix_op.ddlerp_slots(x, self._maa5(), corr, shift_pool, slots, cu_seqlens).unbind(0)
         elif self._use_fused(x):
             assert slots is None, "slots name rows of shift_pool"
             from . import mix_op
             first = None if shifted is None else shifted[:, 0].contiguous()
             if shifted0 is not None:
                 first = shifted0.contiguous()
-            lead = mix_op.ddlerp(x, self.time_maa_x.view(1, C), None, first, rev_n, cu_seqlens=cu_seqlens)[0]
-            low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
-            corr = torch.bmm(low, self.time_maa_w2).view(5, B, T, C)
-            xw, xk, xv, xr, xg = mix_op.ddlerp(x, self._maa5(), corr, first, rev_n, cu_seqlens=cu_seqlens).unbind(0)
+            if lowrank:
+                maa_x, W1t, W2t, maa5 = self._lowrank_weights()[:4]
+                xw, xk, xv, xr, xg = mix_op.tmix_inputs(x.contiguous(), maa_x, W1t, W2t, maa5, cu_seqlens, first).unbind(0)
+            else:
+                lead = mix_op.ddlerp(x, self.time_maa_x.view(1, C), None, first, rev_n, cu_seqlens=cu_seqlens)[0]
+                low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
+                corr = torch.bmm(low, self.time_maa_w2).view(5, B, T, C)
+                xw, xk, xv, xr, xg = mix_op.ddlerp(x, self._maa5(), corr, first, rev_n, cu_seqlens=cu_seqlens).unbind(0)
         else:
             assert rev_n is None, "the reversed-stream shift exists in the fused (HIP) path only"
             assert slots is None, "slots name rows of shift_pool"
@@ -192,7 +248,11 @@ class Tmix_x060(nn.Module):
             low = torch.tanh(lead @ self.time_maa_w1).view(B * T, 5, -1).transpose(0, 1)
             corr = torch.bmm(low, self.time_maa_w2).view(5, B, T, C)
             xw, xk, xv, xr, xg = (x + delta * (self._maa5().view(5, 1, 1, C) + corr)).unbind(0)
-        decay = self.time_decay + torch.tanh(xw @ self.time_decay_w1) @ self.time_decay_w2
+        if lowrank:
+            D1t, D2t, time_decay = self._lowrank_weights()[4:]
+            decay = mix_op.decay_lowrank(xw, D1t, D2t, time_decay)
+        else:
+            decay = self.time_decay + torch.tanh(xw @ self.time_decay_w1) @ self.time_decay_w2
         return self.receptance(xr), self.key(xk), self.value(xv), F.silu(self.gate(xg)), decay
 
     def jit_func_2(self, x, g):

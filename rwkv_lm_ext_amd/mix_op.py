@@ -278,6 +278,121 @@ def lora_packed(x, y, A_pool, B_pool, scale, adapter, cu_seqlens):
     return y
 
 
+# ---- the two low-rank pairs in front of the time-mix projections (include/wkv6_amd.h: wkv6_tmix_lerp_lowrank_bf16,
+# wkv6_decay_lowrank_bf16); inference only: no autograd.  Shapes and types are judged first, the device last (there is no CPU path here:
+# callers.Tmix_x060.jit_func has the eager one).
+LOWRANK_D = (32, 64)           # TIME_MIX_EXTRA_DIM the kernels have
+LOWRANK_DD = (64, 128)         # TIME_DECAY_EXTRA_DIM
+
+
+def _bf16_shape(t, shape):
+    return isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16 and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+
+
+def _lowrank_work(dev, rows, d_total):
+    nbytes = _lib.load().wkv6_lowrank_workspace_bytes(rows, d_total)
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8), nbytes
+
+
+def tmix_inputs(x, maa_x, W1t, W2t, maa5, cu_seqlens=None, shifted0=None, shift_pool=None, slots=None):
+    """The five inputs xw, xk, xv, xr, xg of an RWKV-6 time-mix layer, bf16 [5, *x.shape], in two launches:
+    x + (xp - x) * (maa5[s] + tanh((x + (xp - x) * maa_x) @ W1) [s] @ W2[s]), xp the token in front; the operation and its rounding points
+    are stated in include/wkv6_amd.h.  x bf16 [B, T, C] (dense; shifted0 [B, C] or None: the token in front of every batch row), or with
+    cu_seqlens (int32 [n_seq + 1]) a packed batch [1, total_T, C] (or [total_T, C]) with either shifted0 [n_seq, C] or shift_pool bf16
+    [n_slots, C] and slots (int32 [n_seq], None: the sequence index), as ddlerp_slots takes them.  maa_x bf16 [C] (any shape of C elements),
+    maa5 bf16 [5, C], W1t bf16 [5 D, C] and W2t bf16 [5, C, D]: time_maa_w1 and time_maa_w2 in nn.Linear layout; D in LOWRANK_D.  The workspace
+    is a torch tensor, so a graph capture owns it.  Raises when a gradient is required."""
+    bf = torch.bfloat16
+    if not (isinstance(x, torch.Tensor) and x.dtype == bf and x.dim() in (2, 3) and x.is_contiguous()):
+        raise RuntimeError("x must be a contiguous bf16 tensor [B, T, C] (packed: [1, total_T, C] or [total_T, C])")
+    C = x.shape[-1]
+    total = x.numel() // max(C, 1)
+    if cu_seqlens is None:
+        if x.dim() != 3:
+            raise RuntimeError("x must be a contiguous bf16 tensor [B, T, C] (packed: [1, total_T, C] or [total_T, C])")
+        n_seq = x.shape[0]
+    else:
+        if x.dim() == 3 and x.shape[0] != 1:
+            raise RuntimeError("a packed batch is [1, total_T, C] (or [total_T, C])")
+        n_seq = _ints(cu_seqlens, _AT_LEAST_2, None, _CU_SEQLENS).numel() - 1
+    if not (isinstance(maa_x, torch.Tensor) and maa_x.dtype == bf and maa_x.numel() == C and maa_x.is_contiguous()):
+        raise RuntimeError(f"maa_x must be a contiguous bf16 tensor of C = {C} elements")
+    if not (isinstance(W1t, torch.Tensor) and W1t.dtype == bf and W1t.dim() == 2 and W1t.shape[1] == C and W1t.shape[0] % 5 == 0
+            and W1t.is_contiguous()):
+        raise RuntimeError(f"W1t must be a contiguous bf16 tensor [5 D, C = {C}] (time_maa_w1 transposed)")
+    D = W1t.shape[0] // 5
+    if not _bf16_shape(W2t, (5, C, D)):
+        raise RuntimeError(f"W2t must be a contiguous bf16 tensor [5, C = {C}, D = {D}] (time_maa_w2 with its last two dimensions transposed)")
+    if not _bf16_shape(maa5, (5, C)):
+        raise RuntimeError(f"maa5 must be a contiguous bf16 tensor [5, C = {C}]")
+    if D not in LOWRANK_D:
+        raise RuntimeError(f"tmix_inputs: D must be one of {LOWRANK_D}, got {D}")
+    if total < 1 or n_seq < 1 or C % 64 or not 64 <= C <= 4096:
+        raise RuntimeError("tmix_inputs: x must hold at least one row, C a multiple of 64 in [64, 4096]")
+    if shifted0 is not None and shift_pool is not None:
+        raise RuntimeError("shifted0 and shift_pool exclude each other")
+    if shift_pool is not None and cu_seqlens is None:
+        raise RuntimeError("shift_pool / slots belong to a packed batch (cu_seqlens)")
+    if slots is not None and shift_pool is None:
+        raise RuntimeError("slots name rows of shift_pool")
+    front = shifted0 if shift_pool is None else shift_pool
+    if shifted0 is not None and not _bf16_shape(shifted0, (n_seq, C)):
+        raise RuntimeError(f"shifted0 must be a contiguous bf16 tensor [n_seq, C] = {[n_seq, C]}")
+    if shift_pool is not None:
+        if not (isinstance(shift_pool, torch.Tensor) and shift_pool.dtype == bf and shift_pool.dim() == 2 and shift_pool.shape[0] >= 1
+                and shift_pool.shape[1] == C and shift_pool.is_contiguous()):
+            raise RuntimeError(f"shift_pool must be a contiguous bf16 tensor [n_slots, C = {C}] (it is used in place, never copied)")
+        if slots is None and shift_pool.shape[0] < n_seq:
+            raise RuntimeError("slots = None means slot = sequence index: the pool must hold n_seq slots")
+        if slots is not None:
+            _check_ints(slots, (n_seq,), "slots")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, maa_x, W1t, W2t, maa5, front)):
+        raise RuntimeError("tmix_inputs has no backward: call it under torch.no_grad() (training uses ddlerp and the torch matmuls)")
+    if not x.is_cuda:
+        raise RuntimeError("x must be on the GPU (tmix_inputs has no CPU path)")
+    if any(t is not None and t.device != x.device for t in (maa_x, W1t, W2t, maa5, cu_seqlens, front, slots)):
+        raise RuntimeError("maa_x, W1t, W2t, maa5, cu_seqlens, shifted0, shift_pool and slots must be on the device of x")
+    out = torch.empty((5,) + tuple(x.shape), device=x.device, dtype=bf)
+    work, nbytes = _lowrank_work(x.device, total, 5 * D)
+    _call("wkv6_tmix_lerp_lowrank_bf16", "tmix lerp lowrank", x.device, total, n_seq, C, D, *_ptrs(cu_seqlens, x, front),
+          0 if front is None else front.shape[0], *_ptrs(slots, maa_x, W1t, W2t, maa5, out, work), nbytes)
+    return out
+
+
+def decay_lowrank(xw, D1t, D2t, time_decay):
+    """w = time_decay + tanh(xw @ D1) @ D2 in two launches, bf16 [*xw.shape[:-1], N]; the operation and its rounding points are stated in
+    include/wkv6_amd.h.  xw bf16 [.., C], D1t bf16 [Dd, C] and D2t bf16 [N, Dd]: time_decay_w1 and time_decay_w2 in nn.Linear layout, Dd in
+    LOWRANK_DD; time_decay bf16 of N elements.  The workspace is a torch tensor, so a graph capture owns it.  Raises when a gradient is
+    required."""
+    bf = torch.bfloat16
+    if not (isinstance(xw, torch.Tensor) and xw.dtype == bf and xw.dim() >= 2 and xw.is_contiguous()):
+        raise RuntimeError("xw must be a contiguous bf16 tensor [.., rows, C]")
+    C = xw.shape[-1]
+    rows = xw.numel() // max(C, 1)
+    if not (isinstance(D1t, torch.Tensor) and D1t.dtype == bf and D1t.dim() == 2 and D1t.shape[1] == C and D1t.is_contiguous()):
+        raise RuntimeError(f"D1t must be a contiguous bf16 tensor [Dd, C = {C}] (time_decay_w1 transposed)")
+    Dd = D1t.shape[0]
+    if not (isinstance(D2t, torch.Tensor) and D2t.dtype == bf and D2t.dim() == 2 and D2t.shape[1] == Dd and D2t.is_contiguous()):
+        raise RuntimeError(f"D2t must be a contiguous bf16 tensor [N, Dd = {Dd}] (time_decay_w2 transposed)")
+    N = D2t.shape[0]
+    if not (isinstance(time_decay, torch.Tensor) and time_decay.dtype == bf and time_decay.numel() == N and time_decay.is_contiguous()):
+        raise RuntimeError(f"time_decay must be a contiguous bf16 tensor of N = {N} elements")
+    if Dd not in LOWRANK_DD:
+        raise RuntimeError(f"decay_lowrank: Dd must be one of {LOWRANK_DD}, got {Dd}")
+    if rows < 1 or C % 64 or N % 64 or not (64 <= C <= 4096 and 64 <= N <= 4096):
+        raise RuntimeError("decay_lowrank: xw must hold at least one row, C and N multiples of 64 in [64, 4096]")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (xw, D1t, D2t, time_decay)):
+        raise RuntimeError("decay_lowrank has no backward: call it under torch.no_grad() (training uses the torch matmuls)")
+    if not xw.is_cuda:
+        raise RuntimeError("xw must be on the GPU (decay_lowrank has no CPU path)")
+    if any(t.device != xw.device for t in (D1t, D2t, time_decay)):
+        raise RuntimeError("D1t, D2t and time_decay must be on the device of xw")
+    w = torch.empty(tuple(xw.shape[:-1]) + (N,), device=xw.device, dtype=bf)
+    work, nbytes = _lowrank_work(xw.device, rows, Dd)
+    _call("wkv6_decay_lowrank_bf16", "decay lowrank", xw.device, rows, C, Dd, N, *_ptrs(xw, D1t, D2t, time_decay, w, work), nbytes)
+    return w
+
+
 # ---- device-side token sampling with a penalty slot pool (include/wkv6_amd.h: rwkv6_sample_slots_*); inference only: no autograd.  Shapes
 # and types are judged first, the device last (there is no CPU path here: infctx.sample_packed has the eager one).
 SAMPLE_MAX_VOCAB = 65536
