@@ -705,6 +705,11 @@ int wkv6_sigmul_backward(long n, const void* r, const void* kv, const void* dout
  * that both backward kernels run -- (forward and backward, all outputs within 2 bf16 ulps of the tensor scale, 4 for gw).
  * Returns 0 when it passes, WKV6_ESELFTEST (or the number of failed primitive checks) otherwise. */
 int wkv6_selftest(void* stream);
+/* Debug entry: the two forms of the chunked kernels' split of fp32 into bf16 hi + lo (csrc/wkv6_chunk.h: the residual lo = x - float(hi)
+ * by v_dot2c per lane, or by one MFMA per wave) on `rows` rows of 64 lanes x 4 floats at `x`.  out: 4 * rows * 256 bf16 bit patterns,
+ * [hi, lo of the v_dot2c form | hi, lo of the MFMA form][rows][64][4].  An Inf in one hi makes NaN of the MFMA form's residuals in the
+ * same lane % 16 of its row (all four lane groups, all four slots); nothing else crosses lanes. */
+int wkv6_debug_split(long rows, const void* x, void* out, void* stream);
 /* Measurement aids (bench.py; no effect on results).
  * wkv6_set_clock_ring: while `buf` (device memory, 2 * n_launches * n_slots * 4 uint64) is set, wave 0 of the first n_slots workgroups of
  * the n-th chunked forward launch since the call writes {s_memtime, s_memrealtime} at its start and its end into

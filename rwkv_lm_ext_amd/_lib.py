@@ -101,6 +101,7 @@ SIGNATURES = {
     "wkv6_sigmul_forward": (_I, [_L] + [_VP] * 4),
     "wkv6_sigmul_backward": (_I, [_L] + [_VP] * 6),
     "wkv6_selftest": (_I, [_VP]),
+    "wkv6_debug_split": (_I, [_L] + [_VP] * 3),
     "wkv6_set_clock_ring": (None, [_VP, _I, _I]),
     "wkv6_clock_ring_counts": (None, [ctypes.POINTER(_L), ctypes.POINTER(_L)]),
     "wkv6_pass_marker": (_I, [_VP]),

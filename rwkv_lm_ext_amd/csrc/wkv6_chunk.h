@@ -177,6 +177,79 @@ __device__ __forceinline__ void split4(const float (&x)[4], uint2& hi, uint2& lo
     lo.x = pack_bf2(__builtin_amdgcn_fdot2_f32_bf16(h0, m10, x[0], false), __builtin_amdgcn_fdot2_f32_bf16(h0, m01, x[1], false));
     lo.y = pack_bf2(__builtin_amdgcn_fdot2_f32_bf16(h1, m10, x[2], false), __builtin_amdgcn_fdot2_f32_bf16(h1, m01, x[3], false));
 }
+// The same split with the residual formed on the MATRIX pipe: one v_mfma_f32_16x16x16_bf16 in place of the four v_dot2c.  The B operand and
+// the C / D operand of that MFMA share one lane and slot indexing (lane l, slot j <-> element [4 (l / 16) + j][l % 16]), so with A = -I
+// (lane l, slot j of A holds A[l % 16][4 (l / 16) + j]: -1 where l % 16 == 4 (l / 16) + j) D = C - B slot for slot: C = the lane's four
+// floats, B = their packed hi -> D = the four residuals, exact as above (one non-zero product, and x - float(hi) is representable).
+// 4 v_cvt_pk + 1 MFMA per four elements instead of 4 v_cvt_pk + 4 v_dot2c.  What differs from the v_dot2c form:
+//   * an MFMA ignores EXEC: a site that can run with a partial lane mask keeps the v_dot2c form;
+//   * a NaN or Inf in ONE hi reaches the residuals of all 16 elements of its tile column (0 x Inf in the zero entries of -I), where v_dot2c
+//     kept it in its own packed pair.  The contraction that consumes hi | lo spreads it the same way, so no finite-input result changes
+//     (hi is Inf only for |x| >= 0x7f7f8000 ~ 3.39e38);
+//   * subnormals: nothing differs.  Neither form flushes an fp32-subnormal x or residual on gfx950 -- measured bit for bit against
+//     RNE_bf16(x - float(hi)) down to the bf16 subnormals (tests/test_mfma_split_gpu.py, profiles/mfma_split.txt).
+// The operand -I is two registers per wave, made once like SplitConst (opaque: it must stay in VGPRs across the loop, not be re-made).
+struct SplitMfma { s4v negI; };
+__device__ __forceinline__ SplitMfma split_mfma_const(int lane)
+{
+    const int d = (lane & 15) - 4 * (lane >> 4);         // the slot of this lane that lies on the diagonal, if it is one of 0..3
+    unsigned a0 = d == 0 ? 0x0000bf80u : (d == 1 ? 0xbf800000u : 0u), a1 = d == 2 ? 0x0000bf80u : (d == 3 ? 0xbf800000u : 0u);
+    asm volatile("" : "+v"(a0), "+v"(a1));
+    return SplitMfma{__builtin_bit_cast(s4v, make_uint2(a0, a1))};
+}
+__device__ __forceinline__ f4v split_residual(const float (&x)[4], const uint2& hi, const SplitMfma& sm)
+{
+    return mfma16(sm.negI, __builtin_bit_cast(s4v, hi), f4v{x[0], x[1], x[2], x[3]});
+}
+__device__ __forceinline__ void split4(const float (&x)[4], uint2& hi, uint2& lo, const SplitMfma& sm)
+{
+    hi.x = pack_bf2(x[0], x[1]);
+    hi.y = pack_bf2(x[2], x[3]);
+    const f4v d = split_residual(x, hi, sm);
+    lo.x = pack_bf2(d[0], d[1]);
+    lo.y = pack_bf2(d[2], d[3]);
+}
+// a C-layout tile pair (8 floats) into the hi / lo bf16x8 fragments of one k-step: both forms.  The MFMA form issues both MFMAs before
+// either residual is converted, so that one MFMA's latency lies under the other's issue.
+__device__ __forceinline__ void split8(const float (&t0)[4], const float (&t1)[4], b8v& hi, b8v& lo, const SplitConst& spc)
+{
+    uint2 h0, l0, h1, l1;
+    split4(t0, h0, l0, spc);
+    split4(t1, h1, l1, spc);
+    hi = __builtin_bit_cast(b8v, make_uint4(h0.x, h0.y, h1.x, h1.y));
+    lo = __builtin_bit_cast(b8v, make_uint4(l0.x, l0.y, l1.x, l1.y));
+}
+__device__ __forceinline__ void split8(const float (&t0)[4], const float (&t1)[4], b8v& hi, b8v& lo, const SplitMfma& sm)
+{
+    const uint2 h0 = make_uint2(pack_bf2(t0[0], t0[1]), pack_bf2(t0[2], t0[3])), h1 = make_uint2(pack_bf2(t1[0], t1[1]), pack_bf2(t1[2], t1[3]));
+    const f4v d0 = split_residual(t0, h0, sm), d1 = split_residual(t1, h1, sm);
+    hi = __builtin_bit_cast(b8v, make_uint4(h0.x, h0.y, h1.x, h1.y));
+    lo = __builtin_bit_cast(b8v, make_uint4(pack_bf2(d0[0], d0[1]), pack_bf2(d0[2], d0[3]), pack_bf2(d1[0], d1[1]), pack_bf2(d1[2], d1[3])));
+}
+// Which form each role's sites use: one bit per role, set = the MFMA form (measured role by role: profiles/mfma_split.txt).
+// -DWKV6_MFMA_SPLIT=<mask> builds another choice for an A/B run; the two forms give the same bits (tests/test_mfma_split_gpu.py).
+enum : unsigned {
+    MS_BWD_PROD = 1u << 0,       // backward: the producers' Rhat / Khat
+    MS_BWD_TILE = 1u << 1,       //           the row waves' shared dA and score tiles
+    MS_BWD_ROW = 1u << 2,        //           the row waves' state (and, two-workgroup launches, their copy of G)
+    MS_BWD_COL = 1u << 3,        //           the column waves' G operand (and, two-workgroup launches, their score tiles)
+    MS_FWD_PROD = 1u << 4,       // forward:  the producers' Rhat / Khat
+    MS_FWD_SC = 1u << 5,         //           the producers' score tiles
+    MS_FWD_CONS = 1u << 6,       //           the consumers' state
+};
+#ifndef WKV6_MFMA_SPLIT
+#define WKV6_MFMA_SPLIT 0x7fu
+#endif
+// both constants of a wave; a role's sites pick theirs with form<ROLE>() (one that no site of a wave uses is dead once made)
+struct SplitForms {
+    SplitConst dot;
+    SplitMfma mfma;
+    template <unsigned ROLE> __device__ __forceinline__ const auto& form() const
+    {
+        if constexpr ((WKV6_MFMA_SPLIT & ROLE) != 0) return mfma; else return dot;
+    }
+};
+__device__ __forceinline__ SplitForms split_forms(int lane) { return SplitForms{split_const(), split_mfma_const(lane)}; }
 
 }  // namespace chunk
 }  // namespace wkv6

@@ -164,7 +164,7 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
     [[maybe_unused]] const int nxrev = ch.nx_rev, b_known = ch.b, ntok_known = ch.ntok, nxb = ch.nx_b, nxntok = ch.nx_ntok, pb = CHAIN ? ch.pb : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];      // [2][NBLK][BLK_BYTES] | GN: float [2][4 waves][NBLK][16][2] | float [4 consumers][1024] | y rows [2][64][YRS]
     const int tid = threadIdx.x, lane = tid & 63;
-    const SplitConst spc = split_const();
+    const SplitForms spf = split_forms(lane);
     // a.split (B*H <= half the CUs): two 6-wave workgroups per (batch, head) on two CUs, each with all four producers and two
     // of the four consumers (value columns [32 part, 32 part + 32)): hardware wave w plays consumer 2 part + w for w < 2 and
     // producer w - 2 (wave id 4 + w - 2) otherwise.  The preparation is duplicated, on CUs that would otherwise idle.
@@ -347,10 +347,10 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
                 char* const row = bb + (4 * tq + tt) * RSB + 8 * c4;
                 uint2 hi, lo;
                 if constexpr (!STATE_ONLY) {
-                    split4(rh, hi, lo, spc);
+                    split4(rh, hi, lo, spf.form<MS_FWD_PROD>());
                     *reinterpret_cast<uint2*>(row + A_RH * ARR) = hi; *reinterpret_cast<uint2*>(row + A_RL * ARR) = lo;
                 }
-                split4(kh, hi, lo, spc);
+                split4(kh, hi, lo, spf.form<MS_FWD_PROD>());
                 *reinterpret_cast<uint2*>(row + A_KH * ARR) = hi; *reinterpret_cast<uint2*>(row + A_KL * ARR) = lo;
             }
             if constexpr (!STATE_ONLY) {
@@ -379,7 +379,7 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
                     scm[q] = bt < x ? sc[q] : (bt == x ? cf : 0.f);
                 }
                 uint2 sh, sl;
-                split4(scm, sh, sl, spc);
+                split4(scm, sh, sl, spf.form<MS_FWD_SC>());
                 *reinterpret_cast<uint4*>(bb + OFF_SC + lane * 16) = make_uint4(sh.x, sh.y, sl.x, sl.y);   // hi (4 key tokens) | lo: the lane's 8 k-slots
             }
         };
@@ -670,11 +670,8 @@ __device__ __forceinline__ void chunk_fwd_body(const ScanArgs& a, const unsigned
                     for (int s = 0; s < 2; ++s) {
                         const float t0[4] = {Tt[2 * s][0], Tt[2 * s][1], Tt[2 * s][2], Tt[2 * s][3]};
                         const float t1[4] = {Tt[2 * s + 1][0], Tt[2 * s + 1][1], Tt[2 * s + 1][2], Tt[2 * s + 1][3]};
-                        uint2 h0, l0, h1, l1;
-                        split4(t0, h0, l0, spc);
-                        split4(t1, h1, l1, spc);
-                        const b8v s_hi = __builtin_bit_cast(b8v, make_uint4(h0.x, h0.y, h1.x, h1.y));
-                        const b8v s_lo = __builtin_bit_cast(b8v, make_uint4(l0.x, l0.y, l1.x, l1.y));
+                        b8v s_hi, s_lo;
+                        split8(t0, t1, s_hi, s_lo, spf.form<MS_FWD_CONS>());
                         const b8v zh = pzh[s], zl = pzl[s];
                         yt = mfma32(s_hi, zh, yt);
                         yt = mfma32(s_hi, zl, yt);

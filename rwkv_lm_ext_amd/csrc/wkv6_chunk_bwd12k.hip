@@ -95,16 +95,6 @@ static_assert(BWD12K_LDS <= 160 * 1024, "LDS budget");
     "v_add_f32_dpp %2, %2, %2 " ctrl " row_mask:0xf bank_mask:0xf\n\t" "v_add_f32_dpp %3, %3, %3 " ctrl " row_mask:0xf bank_mask:0xf" \
     : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]))
 
-// split a C-layout tile pair (8 floats) into the hi / lo bf16x8 fragments of one k-step
-__device__ __forceinline__ void split8(const float (&t0)[4], const float (&t1)[4], b8v& hi, b8v& lo, const SplitConst& spc)
-{
-    uint2 h0, l0, h1, l1;
-    split4(t0, h0, l0, spc);
-    split4(t1, h1, l1, spc);
-    hi = __builtin_bit_cast(b8v, make_uint4(h0.x, h0.y, h1.x, h1.y));
-    lo = __builtin_bit_cast(b8v, make_uint4(l0.x, l0.y, l1.x, l1.y));
-}
-
 // The modes of chunk_bwd12k_body<MODE, GEN, ROLE>, one bit each.  A call site ORs the bits it switches on and names nothing else; a bit that
 // follows a kernel's own template parameter goes through bit().  (BWD_: the forward has FWD_ bits of its own, wkv6_chunk.hip.)  GEN and ROLE
 // are numbers and stay template parameters of their own.  The notes below call a bit by its name without the prefix, which is also the
@@ -187,7 +177,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
     // lane-invariant address parts of BOTH bodies out of the row loop and keeps them alive across the calls -- vector-register spills)
     if constexpr (CHAIN) asm volatile("" : "+v"(tid_));
     const int tid = tid_, lane = tid & 63;
-    const SplitConst spc = split_const();
+    const SplitForms spf = split_forms(lane);      // the split constants of this wave (wkv6_chunk.h)
     const int hwid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int part = SPLIT ? (int)(slot & 1) : 0;
     const int bh = SPLIT ? (int)(slot >> 1) : (int)slot;
@@ -476,7 +466,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                 const int tok = 2 * tq + tt;
                 char* const row = rb + tok * RSB + ch0 * 2;
                 uint2 hi, lo;
-                split4(rh, hi, lo, spc);
+                split4(rh, hi, lo, spf.form<MS_BWD_PROD>());
                 *reinterpret_cast<uint2*>(row + R_RH * ARR) = hi; *reinterpret_cast<uint2*>(row + R_RL * ARR) = lo;
                 *reinterpret_cast<float4*>(rb + ROFF_FR + tok * FRS + ch0 * 4) = make_float4(fr[0], fr[1], fr[2], fr[3]);
             }
@@ -495,7 +485,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
             if constexpr (HASK) {
                 char* const row = kb + (2 * tq + tt) * RSB + ch0 * 2;
                 uint2 hi, lo;
-                split4(kh, hi, lo, spc);
+                split4(kh, hi, lo, spf.form<MS_BWD_PROD>());
                 *reinterpret_cast<uint2*>(row + K_KH * ARR) = hi; *reinterpret_cast<uint2*>(row + K_KL * ARR) = lo;
             }
         }
@@ -786,10 +776,10 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                     dba[q] = o < x ? dA_ba[q] : 0.f;              // dA^T[b = o][a = x], strictly lower
                 }
                 uint2 th, tl;
-                split4(dab, th, tl, spc);
+                split4(dab, th, tl, spf.form<MS_BWD_TILE>());
                 tile_store(XT_OFF + (2 * tb) * 1024, th, tl);
                 publish_at(tag_tb, TAG_DA, 0, tagv);            // slot TAG_DA + 2 tb
-                split4(dba, th, tl, spc);
+                split4(dba, th, tl, spf.form<MS_BWD_TILE>());
                 tile_store(XT_OFF + (2 * tb + 1) * 1024, th, tl);
                 publish_at(tag_tb, TAG_DA, 4, tagv);            // slot TAG_DA + 2 tb + 1
             } else if constexpr (!SPLIT) {   // row waves 0 and 1: the masked score tile of block wv, for the column waves
@@ -815,7 +805,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                     scm[q] = x < o ? sc[q] : (x == o ? cf[q] : 0.f);
                 }
                 uint2 th, tl;
-                split4(scm, th, tl, spc);
+                split4(scm, th, tl, spf.form<MS_BWD_TILE>());
                 tile_store(XS_OFF + wv * 1024, th, tl);
                 publish(TAG_SC, tagv);
             }
@@ -869,7 +859,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                     b8v hi, lo;                                  // k-slot (s, g, e) <-> value channel 32s + 8g + e
 #pragma unroll
                     for (int q = 0; q < 4; ++q) { t0[q] = ST[blk][2 * s][q]; t1[q] = ST[blk][2 * s + 1][q]; }
-                    split8(t0, t1, hi, lo, spc);
+                    split8(t0, t1, hi, lo, spf.form<MS_BWD_ROW>());
                     accs = mfma32(hi, gyr[s], accs);
                     accs = mfma32(lo, gyr[s], accs);
                 }
@@ -965,7 +955,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                         b8v hi, lo;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) { t0[q] = GI[2 * s][q] * e16m8x; t1[q] = GI[2 * s + 1][q] * e16m8x; }
-                        split8(t0, t1, hi, lo, spc);
+                        split8(t0, t1, hi, lo, spf.form<MS_BWD_ROW>());
                         acck = mfma32(hi, vr, acck);
                         acck = mfma32(lo, vr, acck);
                     }
@@ -1106,7 +1096,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                 t0[0] = GJ[2 * s][0] * m0.x; t0[1] = GJ[2 * s][1] * m0.y; t0[2] = GJ[2 * s][2] * m0.z; t0[3] = GJ[2 * s][3] * m0.w;
                 t1[0] = GJ[2 * s + 1][0] * m1.x; t1[1] = GJ[2 * s + 1][1] * m1.y;
                 t1[2] = GJ[2 * s + 1][2] * m1.z; t1[3] = GJ[2 * s + 1][3] * m1.w;
-                split8(t0, t1, h[s], l[s], spc);
+                split8(t0, t1, h[s], l[s], spf.form<MS_BWD_COL>());
             }
         };
         auto gop_write = [&](const b8v (&h)[2], const b8v (&l)[2]) {
@@ -1221,7 +1211,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                     scm[q] = x < o ? sc[q] : (x == o ? cf[q] : 0.f);
                 }
                 uint2 th, tl;
-                split4(scm, th, tl, spc);
+                split4(scm, th, tl, spf.form<MS_BWD_COL>());
                 tile_store(XS_OFF + wv * 1024, th, tl);
                 publish(TAG_SC, tagv);
             }
@@ -1269,7 +1259,7 @@ __device__ __forceinline__ void chunk_bwd12k_body(const ScanArgs& a, const unsig
                         t0[0] = GJ[2 * s][0] * m0.x; t0[1] = GJ[2 * s][1] * m0.y; t0[2] = GJ[2 * s][2] * m0.z; t0[3] = GJ[2 * s][3] * m0.w;
                         t1[0] = GJ[2 * s + 1][0] * m1.x; t1[1] = GJ[2 * s + 1][1] * m1.y;
                         t1[2] = GJ[2 * s + 1][2] * m1.z; t1[3] = GJ[2 * s + 1][3] * m1.w;
-                        split8(t0, t1, gh[blk][s], gl[blk][s], spc);
+                        split8(t0, t1, gh[blk][s], gl[blk][s], spf.form<MS_BWD_COL>());
                     }
                     acc = mfma32(gh[blk][s], kh, acc);       // k-slot (s, g, e) <-> key channel 32s + 8g + e
                     acc = mfma32(gh[blk][s], kl, acc);

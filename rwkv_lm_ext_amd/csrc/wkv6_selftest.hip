@@ -1,5 +1,5 @@
 // Device self-test (wkv6_selftest, include/wkv6_amd.h): run at load time by the Python layer, through the public entry points alone.
-#include "wkv6_host.h"
+#include "wkv6_chunk.h"                // (wkv6_host.h; the split forms of wkv6_debug_split)
 
 #include <cmath>
 #include <cstring>
@@ -7,7 +7,38 @@
 
 using namespace wkv6;
 
+namespace {
+// wkv6_debug_split: both forms of the bf16 hi | lo split of the chunked kernels (wkv6_chunk.h: split4 with v_dot2c / with the MFMA residual)
+// on rows of 64 lanes x 4 floats, one wave per workgroup, every lane active.  out: bf16 bits [4 (hi, lo of v_dot2c; hi, lo of MFMA)][rows][64][4]
+__global__ __launch_bounds__(64) void debug_split_kernel(const float4* __restrict__ x, uint2* __restrict__ out, long rows)
+{
+    using namespace chunk;
+    const int lane = threadIdx.x;
+    const SplitForms spf = split_forms(lane);
+    for (long r = blockIdx.x; r < rows; r += gridDim.x) {      // (uniform bound: an MFMA ignores EXEC)
+        const float4 v = x[r * 64 + lane];
+        const float xs[4] = {v.x, v.y, v.z, v.w};
+        uint2 hd, ld, hm, lm;
+        split4(xs, hd, ld, spf.dot);
+        split4(xs, hm, lm, spf.mfma);
+        out[(0 * rows + r) * 64 + lane] = hd;
+        out[(1 * rows + r) * 64 + lane] = ld;
+        out[(2 * rows + r) * 64 + lane] = hm;
+        out[(3 * rows + r) * 64 + lane] = lm;
+    }
+}
+}  // namespace
+
 extern "C" {
+
+int wkv6_debug_split(long rows, const void* x, void* out, void* stream)
+{
+    if (rows < 1) return WKV6_EINVAL;
+    if (!x || !out) return WKV6_ENULL;
+    const unsigned grid = (unsigned)(rows < 256 ? rows : 256);
+    return to_rc(launch<debug_split_kernel>(dim3(grid), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const float4*>(x),
+                                            reinterpret_cast<uint2*>(out), rows));
+}
 
 static int selftest_problem(int B, void* stream)
 {

@@ -69,6 +69,20 @@
 #define B_SPLIT4 "v_cvt_pk_bf16_f32 v88, v64, v65\n v_cvt_pk_bf16_f32 v89, v66, v67\n v_mov_b32 v80, v64\n v_mov_b32 v81, v65\n v_mov_b32 v82, v66\n v_mov_b32 v83, v67\n" \
                  "v_dot2c_f32_bf16 v80, v88, v78\n v_dot2c_f32_bf16 v81, v88, v79\n v_dot2c_f32_bf16 v82, v89, v78\n v_dot2c_f32_bf16 v83, v89, v79\n" \
                  "v_cvt_pk_bf16_f32 v90, v80, v81\n v_cvt_pk_bf16_f32 v91, v82, v83\n"       /* 12 instructions */
+// the same split with the residual on the matrix pipe (wkv6_chunk.h: split4 with SplitMfma): 2 cvt_pk, one 16x16x16 MFMA with A = -I, B = the
+// packed hi, C = D = x in place (A's value does not matter to the timing: v[96:97]), 2 cvt_pk.  Nothing inside an asm string is padded, and an
+// MFMA result wants 8 wait states before a VALU read (what hipcc puts there): "dependent" waits them out with s_nop 7 as a lone split4 must,
+// "interleaved" runs two splits half a body apart, each MFMA's result converted behind the other split's front half (9 instructions), as split8
+// and the batched sites of the kernels do.
+#define B_SPLIT4M "v_cvt_pk_bf16_f32 v88, v64, v65\n v_cvt_pk_bf16_f32 v89, v66, v67\n v_mov_b32 v80, v64\n v_mov_b32 v81, v65\n v_mov_b32 v82, v66\n v_mov_b32 v83, v67\n" \
+                  "v_mfma_f32_16x16x16_bf16 v[80:83], v[96:97], v[88:89], v[80:83]\n s_nop 7\n" \
+                  "v_cvt_pk_bf16_f32 v90, v80, v81\n v_cvt_pk_bf16_f32 v91, v82, v83\n"       /* 9 instructions + s_nop 7 */
+#define B_SPLIT4M2 "v_cvt_pk_bf16_f32 v88, v64, v65\n v_cvt_pk_bf16_f32 v89, v66, v67\n v_mov_b32 v80, v64\n v_mov_b32 v81, v65\n v_mov_b32 v82, v66\n v_mov_b32 v83, v67\n" \
+                  "v_mfma_f32_16x16x16_bf16 v[80:83], v[96:97], v[88:89], v[80:83]\n" \
+                  "v_cvt_pk_bf16_f32 v92, v84, v85\n v_cvt_pk_bf16_f32 v93, v86, v87\n" \
+                  "v_cvt_pk_bf16_f32 v94, v68, v69\n v_cvt_pk_bf16_f32 v95, v70, v71\n v_mov_b32 v84, v68\n v_mov_b32 v85, v69\n v_mov_b32 v86, v70\n v_mov_b32 v87, v71\n" \
+                  "v_mfma_f32_16x16x16_bf16 v[84:87], v[96:97], v[94:95], v[84:87]\n" \
+                  "v_cvt_pk_bf16_f32 v90, v80, v81\n v_cvt_pk_bf16_f32 v91, v82, v83\n"       /* two splits: 18 instructions */
 #define B_MFMA32 "v_mfma_f32_16x16x32_bf16 v[104:107], v[96:99], v[100:103], v[104:107]\n v_mfma_f32_16x16x32_bf16 v[108:111], v[96:99], v[100:103], v[108:111]\n" \
                  "v_mfma_f32_16x16x32_bf16 v[112:115], v[96:99], v[100:103], v[112:115]\n v_mfma_f32_16x16x32_bf16 v[116:119], v[96:99], v[100:103], v[116:119]\n" \
                  "v_mfma_f32_16x16x32_bf16 v[104:107], v[96:99], v[100:103], v[104:107]\n v_mfma_f32_16x16x32_bf16 v[108:111], v[96:99], v[100:103], v[108:111]\n" \
@@ -120,7 +134,8 @@
     X(37, "ds_read_b128", B_DSR128, 8) X(38, "ds_read_b64_tr_b16", B_DSRTR, 8) X(39, "ds_write_b64", B_DSW64, 8) X(40, "v_fmac_f32", OP2("v_fmac_f32"), 8) \
     X(41, "own wave: mfma + 6 v_pk_fma_f32", B_M_PKFMA, 7) X(42, "own wave: mfma + 6 v_fma_f32", B_M_FMA6, 7) X(43, "own wave: mfma + 12 v_fma_f32", B_M_FMA12, 13) \
     X(44, "own wave: mfma + 6 v_dot2c", B_M_DOT6, 7) X(45, "own wave: mfma + 6 v_cvt_pk", B_M_CVT6, 7) \
-    X(46, "v_mul_lo_u32", B_MULLO, 8) X(47, "v_mad_u64_u32", B_MAD64, 8)
+    X(46, "v_mul_lo_u32", B_MULLO, 8) X(47, "v_mad_u64_u32", B_MAD64, 8) \
+    X(48, "split4 mfma dependent (10)", B_SPLIT4M, 10) X(49, "split4 mfma interleaved (2x9)", B_SPLIT4M2, 18)
 constexpr int NKIND = 46;
 
 // role 0 = the class, role 1 = back-to-back MFMAs (16x16x32, four accumulators)
@@ -183,7 +198,7 @@ int main(int argc, char** argv)
     printf("%-28s %-34s %8s %14s %14s %10s\n", "class", "config", "dispatch", "cyc/instr/wave", "SIMD cyc/instr", "mfma cyc");
     for (const Kind& kd : kinds) {
         if (!strstr(kd.name, filt)) continue;
-        const bool is_mfma = (kd.id >= 34 && kd.id <= 36) || kd.id >= 41;
+        const bool is_mfma = (kd.id >= 34 && kd.id <= 36) || (kd.id >= 41 && kd.id <= 47);    // (48, 49: vector work with one MFMA in it -- all conditions)
         // alone, W waves per SIMD
         for (int W = 1; W <= 4; ++W) {
             if (quick && W == 3) continue;
