@@ -10,6 +10,12 @@ INT_MIN = -(1 << 31)
 # (K, N, R): the smallest sizes; a second MFMA tile of j and of n with R = 16 (half the contraction padded); a long K split over the
 # waves with two contraction steps (R = 64); many column blocks per workgroup with R = 8 (three quarters padded); a long K with R = 32
 SHAPES = [(64, 64, 8), (192, 192, 16), (2048, 64, 64), (128, 7168, 8), (7168, 128, 32)]
+# (K, N, R) whose K runs BOTH loops of the shrink -- K / 32 steps in 4 interleaved chunks, 4 steps a pass (main loop), then singly
+# (remainder) -- and whose N / 64 column blocks do not share out evenly over the expand's 16 workgroups: 24 steps (main once, two remainder
+# steps a chunk) with R = 8 and 42 blocks (ten workgroups walk 3, six walk 2); 84 steps (main five times, a remainder step a chunk) with
+# R = 16; 18 steps (main once, a remainder step for chunks 0 and 1 only) with R = 64's two expand steps and 17 blocks (workgroup 0 walks 2);
+# 34 steps (main twice, a remainder step for two chunks) with R = 32.  768 is n_embd of the 0.1B model, 2688 = 3.5 * 768 its dim_ffn.
+MIXED_SHAPES = [(768, 2688, 8), (2688, 768, 16), (576, 1088, 64), (1088, 64, 32)]
 N_ADAPTERS = 5
 LENS = [37, 1, 1, 0, 1, 16, 1, 1, 70, 1]          # runs cross tile edges (tiles of 16 rows), and tile 2 holds five sequences
 ADAPTERS = [2, 0, -1, 3, 4, N_ADAPTERS, 1, INT_MIN, 2, 0]
@@ -17,6 +23,32 @@ LEAD = 3                                          # rows in front of cu_seqlens[
 # total_T, neither a multiple of 16: 135 leaves three rows behind the last sequence; 130 cuts sequence 8 short, leaves sequence 9 no row and
 # puts cu_seqlens[9] and cu_seqlens[10] past total_T
 TOTALS = [135, 130]
+
+
+# Sixteen groups in a tile, over a pool of MANY_ADAPTERS = 20.  Tile 0 is one sequence up to the tile edge; tile 1 (rows 16..31) is sixteen
+# one-token sequences on sixteen distinct adapters, 16..19 among them; tile 2 (rows 32..47) holds nine groups -- single tokens, a two-row
+# sequence and a row on no adapter between them -- the ninth a sequence of 30 rows that crosses the edges at 48 and 64; three rows behind it
+# are in no sequence.
+MANY_ADAPTERS = 20
+GROUPS_LENS = [16] + [1] * 16 + [1, 1, 2, 1, 1, 1, 1, 1, 1, 30]
+GROUPS_ADAPTERS = [3] + [19, 0, 18, 5, 17, 7, 16, 9, 1, 15, 2, 14, 3, 13, 4, 12] + [6, 8, 10, -1, 11, 19, 0, 17, 5, 16]
+GROUPS_TOTAL = 75
+GROUPS_SHAPES = [(192, 192, 16), (768, 64, 8)]
+# Many tiles: 4100 rows (257 tiles) of K = N = 64, R = 8, about 60 sequences over the 20 adapters
+MANY_TOTAL, MANY_SHAPE = 4100, (64, 64, 8)
+
+
+@functools.lru_cache(maxsize=None)
+def many_batch():
+    """(cu, adapters) of the many-tiles case: boundaries drawn over the whole range behind LEAD rows of no sequence, an empty sequence in
+    the middle, adapters in [-1, MANY_ADAPTERS] (-1 and MANY_ADAPTERS: no adapter) and one INT_MIN; the last rows are in no sequence."""
+    g = torch.Generator().manual_seed(43)
+    cuts = sorted(set(torch.randint(LEAD + 1, MANY_TOTAL - 5, (60,), generator=g).tolist()))
+    half = len(cuts) // 2
+    cu = [LEAD] + cuts[:half] + [cuts[half - 1]] + cuts[half:]
+    adapters = torch.randint(-1, MANY_ADAPTERS + 1, (len(cu) - 1,), generator=g).tolist()
+    adapters[7], adapters[11], adapters[23] = INT_MIN, MANY_ADAPTERS, -1
+    return tuple(cu), tuple(adapters)
 
 
 def cu_of(lens=LENS, lead=LEAD):

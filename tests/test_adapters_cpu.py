@@ -198,7 +198,7 @@ def test_the_eager_path_has_autograd():
 
 
 @pytest.mark.parametrize("total_T", lc.TOTALS)
-@pytest.mark.parametrize("K,N,R", lc.SHAPES)
+@pytest.mark.parametrize("K,N,R", lc.SHAPES + lc.MIXED_SHAPES)
 def test_eager_bf16_meets_the_error_bound_of_the_gpu_tests(K, N, R, total_T):
     """lora_packed_eager in bf16 on the CPU, on the inputs of tests/test_lora_packed_gpu.py, against the fp64 restatement:
     |out - E| <= 2^-8 |E| + 2 |scale| sum_j |B_nj| (2^-9 |e_j| + K 2^-23 S_j) for every element, rows of no adapter exact."""

@@ -8,7 +8,17 @@ alone, and all sequences on -1 equal the blocks before injection; (g) a captured
 
 The batch of (a)-(d): lengths LENS behind LEAD rows of no sequence, adapters ADAPTERS (-1, n_adapters and INT_MIN among them, sequence 3
 empty), total_T in TOTALS.  (d) says that nobody names adapter 1 and that adapter 3 has rows, which ADAPTERS does not give (sequence 6
-names 1, and only the empty sequence names 3): it runs ADAPTERS with sequences 1 and 6 moved to adapter 3."""
+names 1, and only the empty sequence names 3): it runs ADAPTERS with sequences 1 and 6 moved to adapter 3.
+
+(a)-(d) run lora_common.SHAPES and MIXED_SHAPES.  (K, N, R), MIXED_SHAPES -- the shrink walks K / 32 steps in 4 interleaved chunks, 4 steps
+a pass (main loop), then singly (remainder), and no shape of SHAPES runs both loops in one call: (768, 2688, 8): main once, two remainder
+steps a chunk, three quarters of the contraction padded, 42 column blocks over the expand's 16 workgroups (3, 3, .., 2, 2); (2688, 768,
+16): main five times, one remainder step a chunk, half padded; (576, 1088, 64): main once, a remainder step for chunks 0 and 1 only, two
+expand steps, 17 blocks (workgroup 0 walks one more than the rest); (1088, 64, 32): main twice, a remainder step for two chunks.
+(h) sixteen groups in a tile: GROUPS_LENS / GROUPS_ADAPTERS over 20 adapters at (192, 192, 16) and (768, 64, 8) -- rows 16..31 are sixteen
+one-token sequences on sixteen adapters (16..19 among them), rows 32..47 nine groups with a two-row sequence and a row on no adapter
+between them -- (a) and (c).  (i) many tiles: 4100 rows of (64, 64, 8) under many_batch(), 60 sequences over the 20 adapters with -1,
+20 and INT_MIN among them: (a), (c) and (b)."""
 import pytest
 import torch
 
@@ -23,8 +33,8 @@ def i32(x):
     return torch.tensor([int(v) for v in x], dtype=torch.int32, device="cuda")
 
 
-def on_gpu(K, N, R, total_T):
-    return tuple(t.cuda() for t in lc.case(K, N, R, total_T))
+def on_gpu(K, N, R, total_T, n_adapters=lc.N_ADAPTERS):
+    return tuple(t.cuda() for t in lc.case(K, N, R, total_T, n_adapters=n_adapters))
 
 
 def run(x, y0, A, B, scale, adapters, cu):
@@ -38,7 +48,7 @@ def run(x, y0, A, B, scale, adapters, cu):
 
 
 @pytest.mark.parametrize("total_T", lc.TOTALS)
-@pytest.mark.parametrize("K,N,R", lc.SHAPES)
+@pytest.mark.parametrize("K,N,R", lc.SHAPES + lc.MIXED_SHAPES)
 def test_mixed_batch_equals_one_call_per_sequence_bitwise(K, N, R, total_T):
     x, y0, A, B, scale = on_gpu(K, N, R, total_T)
     cu = lc.cu_of()
@@ -55,7 +65,7 @@ def test_mixed_batch_equals_one_call_per_sequence_bitwise(K, N, R, total_T):
 
 
 @pytest.mark.parametrize("total_T", lc.TOTALS)
-@pytest.mark.parametrize("K,N,R", lc.SHAPES)
+@pytest.mark.parametrize("K,N,R", lc.SHAPES + lc.MIXED_SHAPES)
 def test_rows_of_no_adapter_and_of_no_sequence_keep_their_bits(K, N, R, total_T):
     x, _, A, B, scale = on_gpu(K, N, R, total_T)
     g = torch.Generator().manual_seed(5)
@@ -73,7 +83,7 @@ def test_rows_of_no_adapter_and_of_no_sequence_keep_their_bits(K, N, R, total_T)
 
 
 @pytest.mark.parametrize("total_T", lc.TOTALS)
-@pytest.mark.parametrize("K,N,R", lc.SHAPES)
+@pytest.mark.parametrize("K,N,R", lc.SHAPES + lc.MIXED_SHAPES)
 def test_error_against_the_fp64_restatement(K, N, R, total_T):
     """|out - E| <= 2^-8 |E| + 2 |scale| sum_j |B_nj| (2^-9 |e_j| + K 2^-23 S_j) for every element."""
     out = run(*on_gpu(K, N, R, total_T), lc.ADAPTERS, lc.cu_of())
@@ -83,7 +93,7 @@ def test_error_against_the_fp64_restatement(K, N, R, total_T):
     assert ratio <= 1.0
 
 
-@pytest.mark.parametrize("K,N,R", lc.SHAPES)
+@pytest.mark.parametrize("K,N,R", lc.SHAPES + lc.MIXED_SHAPES)
 def test_a_nan_adapter_reaches_exactly_the_rows_that_name_it(K, N, R):
     total_T = lc.TOTALS[0]
     x, y0, A, B, scale = on_gpu(K, N, R, total_T)
@@ -105,6 +115,58 @@ def test_a_nan_adapter_reaches_exactly_the_rows_that_name_it(K, N, R):
     for An_, Bn_ in ((An, B), (A, Bn)):
         out = run(x, y0, An_, Bn_, scale, adapters, cu)
         assert bool(out[which == 3].isnan().all()) and same(out[which != 3], clean[which != 3])
+
+
+def equals_one_call_per_sequence_and_meets_the_bound(K, N, R, total_T, cu, adapters, what):
+    """(a) and (c) on a batch of its own over lc.MANY_ADAPTERS adapters; returns (which, the inputs on the GPU)."""
+    n = lc.MANY_ADAPTERS
+    x, y0, A, B, scale = on_gpu(K, N, R, total_T, n)
+    mixed = run(x, y0, A, B, scale, adapters, cu)
+    joined = y0.clone()
+    for s, a in enumerate(adapters):
+        lo, hi = min(cu[s], total_T), min(cu[s + 1], total_T)
+        if hi > lo:
+            joined[lo:hi] = run(x, y0, A, B, scale, [a], cu[s:s + 2])[lo:hi]
+    assert same(mixed, joined)
+    which = lc.rows_of(cu, adapters, total_T, n)
+    E, bound = lc.restate(*lc.case(K, N, R, total_T, n_adapters=n), which)
+    ratio = lc.worst_ratio(mixed.cpu(), E, bound)
+    print(f"{what} K={K} N={N} R={R} total_T={total_T}: max |out - E| / bound = {ratio:.3f}")
+    assert ratio <= 1.0
+    w = torch.from_numpy(which).cuda()
+    assert same(mixed[w < 0], y0[w < 0]) and not bool((bits(mixed[w >= 0]) == bits(y0[w >= 0])).all(1).any())
+    return which, (x, y0, A, B, scale)
+
+
+@pytest.mark.parametrize("K,N,R", lc.GROUPS_SHAPES)
+def test_sixteen_groups_in_a_tile(K, N, R):
+    """A tile of sixteen one-token sequences on sixteen adapters of a pool of 20 (for_each_group's longest walk: the shrink deals 16 x 4
+    items round its 8 waves, an expand wave serves groups w, w + 4, w + 8, w + 12) beside a tile of nine groups: (a) and (c)."""
+    cu, total_T = lc.cu_of(lc.GROUPS_LENS, 0), lc.GROUPS_TOTAL
+    which = lc.rows_of(cu, lc.GROUPS_ADAPTERS, total_T, lc.MANY_ADAPTERS)
+    assert len(set(which[16:32].tolist())) == 16 and which[16:32].min() >= 0 and which[16:32].max() > 15      # sixteen groups, adapters above 15
+    third = which[32:48].tolist()
+    assert len(set(third) - {-1}) == 9 and third[4] == -1 and third[2] == third[3] and third[10:] == [third[10]] * 6
+    assert which[15] != which[16] and (which[42:72] == which[42]).all() and (which[72:] == -1).all() and len(which) == total_T
+    got, _ = equals_one_call_per_sequence_and_meets_the_bound(K, N, R, total_T, cu, lc.GROUPS_ADAPTERS, "sixteen groups")
+    assert (got == which).all()
+
+
+def test_many_tiles():
+    """4100 rows, 257 tiles: row * K, row * N and row * R from rows in the thousands, about 60 sequences over 20 adapters with boundaries
+    inside tiles all the way: (a), (c), and (b) with random bit patterns in y."""
+    (K, N, R), total_T = lc.MANY_SHAPE, lc.MANY_TOTAL
+    cu, adapters = (list(v) for v in lc.many_batch())
+    assert total_T >= 4096 and len(adapters) >= 55 and -1 in adapters and lc.MANY_ADAPTERS in adapters and lc.INT_MIN in adapters
+    assert len({a for a in adapters if 0 <= a < lc.MANY_ADAPTERS}) >= 18 and any(b == a for a, b in zip(cu, cu[1:]))
+    assert sum(1 for v in cu if v % 16) >= 50 and min(cu) == lc.LEAD and cu[1] < 512 and total_T - 512 < max(cu) < total_T
+    which, (x, _, A, B, scale) = equals_one_call_per_sequence_and_meets_the_bound(K, N, R, total_T, cu, adapters, "many tiles")
+    assert int((which < 0).sum()) >= 100 and int((which >= 0).sum()) >= 3000
+    g = torch.Generator().manual_seed(6)
+    y0 = torch.randint(-32768, 32768, (total_T, N), generator=g, dtype=torch.int32).to(torch.int16).cuda().view(bf)      # NaN payloads included
+    out = run(x, y0, A, B, scale, adapters, cu)
+    w = torch.from_numpy(which).cuda()
+    assert bool(y0.isnan().any()) and same(out[w < 0], y0[w < 0]) and not same(out[w >= 0], y0[w >= 0])
 
 
 def test_three_hundred_sequences_against_the_eager_path():

@@ -62,6 +62,43 @@ def test_the_restatement_without_roundings_is_the_formula_of_jit_func():
     check_formula(got, p, lc.token_in_front(p["x"], cu, p["front"], None))
 
 
+def _yardstick(shares_and_ratios, what):
+    from test_lowrank_gpu import K_BOUND
+    share, ratio = max(shares_and_ratios[0::2]), max(shares_and_ratios[1::2])
+    print(f"{what}: largest share {share * 100:.4f} %, largest ratio at k = 1 {ratio:.3f}")
+    assert ratio <= K_BOUND / 2, f"{what}: the emulation lies {ratio:.3f} bounds (k = 1) from the restatement; K_BOUND / 2 = {K_BOUND / 2}"
+    assert share <= lc.CAP, f"{what}: {share * 100:.4f} % of the emulation's elements differ (cap {lc.CAP * 100} %)"
+
+
+@pytest.mark.parametrize("width", lc.WIDTHS + (lc.MANY_WIDTH + (lc.MANY_T,),), ids=lambda w: "-".join(map(str, w)))
+def test_the_emulations_keep_half_of_k_bound_on_the_parity_inputs(width):
+    """The yardstick of the GPU parity tests, guarded for as long as their inputs live (tools/lowrank_parity.py prints the same figures
+    into profiles/lowrank_parity.txt): on every input set of lc.TMIX_CASES the fp32-accumulating emulation of the chain, under each of the
+    three summation orders, lies within K_BOUND / 2 bounds (k = 1) of the restatement on out and on w and differs from it in at most CAP of
+    the elements.  A width or a seed that fails here cannot carry a parity case: exchange it, never K_BOUND or CAP."""
+    (C, D, Dd), rows = width[:3], width[3:] or lc.ROWS                     # (a fourth entry: the one row count of the many-tiles case)
+    assert all((C, D, Dd, r) in lc.TMIX_CASES for r in rows)
+    seen = []
+    for total_T in rows:
+        case = lc.tmix_case(C, D, Dd, total_T)
+        for mm in lc.ORDERS.values():
+            seen += lc.emulate_tmix(case, mm)
+    _yardstick(seen, f"C={C} D={D} Dd={Dd} rows={rows}")
+
+
+@pytest.mark.parametrize("C,N,Dd", lc.DECAY_CASES)
+def test_the_emulations_keep_half_of_k_bound_on_the_decay_inputs_with_dim_att_unlike_n_embd(C, N, Dd):
+    assert N != C
+    seen = []
+    for rows in lc.ROWS:
+        assert (C, N, Dd, rows) in lc.DECAY_NC_CASES
+        case = lc.decay_case(C, N, Dd, rows)
+        assert tuple(case["w"].shape) == (rows, N) and tuple(case["xw"].shape) == (rows, C)
+        for mm in lc.ORDERS.values():
+            seen += lc.emulate_decay(case, mm)
+    _yardstick(seen, f"decay C={C} N={N} Dd={Dd}")
+
+
 class Calls:
     """Stand-ins for the three ops of mix_op that the fused path of jit_func calls: eager on the CPU, recorded."""
 
