@@ -12,7 +12,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "librwkv6_amd.so")
 SOURCES = ["wkv6_scan.hip", "wkv5_scan.hip", "wkv6_chunk.hip", "wkv6_chunk_bwd12k.hip", "wkv6_mix.hip", "wkv6_lora.hip", "wkv6_lowrank.hip", "wkv6_sample.hip",
            "wkv6_beam.hip", "wkv6_pool.hip", "wkv6_ce.hip", "wkv6_policy.hip", "wkv6_state.hip", "wkv6_tsplit.hip", "wkv6_prepare.hip", "wkv6_bi_rows.hip", "wkv6_api.hip", "wkv6_selftest.hip"]
-HEADERS = ["wkv6_common.h", "wkv6_scan.h", "wkv6_scan_stage.h", "wkv6_host.h", "wkv5_scan.h", "wkv6_chunk.h", "wkv6_sample.h", "wkv6_beam.h", "wkv6_rows.h",
+HEADERS = ["wkv6_common.h", "wkv6_scan.h", "wkv6_scan_stage.h", "wkv6_host.h", "wkv5_scan.h", "wkv6_chunk.h", "wkv6_sample.h", "wkv6_beam.h", "wkv6_rows.h", "wkv6_tile16.h",
            os.path.join("..", "..", "include", "wkv6_amd.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function"]
 

@@ -2,9 +2,9 @@
 // decode step and the beams' running scores, the K best (parent row, token) continuations of every request by cumulative log-probability.
 // The header states the operation; this is how it is done.  Two launches.
 //
-// Row kernel, one workgroup of 1024 threads (16 waves) per row, built like the sampler (wkv6_sample.hip): the row lives in neither
-// registers nor LDS, every pass streams it again as 16-byte loads (after the first from L2 / Infinity Cache) and recomputes the score,
-// because the repetition penalty makes the score non-monotone in the logit.  Pass A: is the row sound, and m = max z.  Pass B: the softmax
+// Row kernel, one workgroup of 1024 threads (16 waves) per row, on the streamed-row radix selection of wkv6_rows.h that the sampler
+// (wkv6_sample.hip) uses too: every pass streams the row again as 16-byte loads (after the first from L2 / Infinity Cache) and recomputes
+// the score, because the repetition penalty makes the score non-monotone in the logit.  Pass A: is the row sound, and m = max z.  Pass B: the softmax
 // denominator as a sum of the integers floor(exp(z - m) * 2^46) -- exact, so the order in which waves arrive cannot change it and a row has
 // the same bits alone or in a batch; L = log of it, once per row, in double.  Then the row's K best scores by radix selection over the
 // monotone 32-bit key of the score -- four passes of 8 bits, most significant first, one 256-bin COUNT histogram in LDS -- the ties at the
@@ -17,28 +17,14 @@
 // (the order of the list).
 #include <cmath>
 #include "wkv6_beam.h"
-#include "wkv6_rows.h"                 // load8
-#include "wkv6_host.h"                 // to_rc, align_up
+#include "wkv6_rows.h"                 // the row walker, the radix selection, block_reduce
+#include "wkv6_host.h"                 // to_rc, align_up, overlap
 
 // the same expression must give the same bits wherever it is inlined (the score is formed again on every pass)
 #pragma clang fp contract(off)
 
 namespace wkv6 {
 namespace {
-
-typedef unsigned long long u64;
-
-constexpr int THREADS = 1024, WAVES = THREADS / 64;
-constexpr float FIX = 70368744177664.f;                      // 2^46
-constexpr float NEG_INF = -__builtin_inff();
-
-// ---- the monotone key of a (non-NaN) float: a > b  <=>  key(a) > key(b); no float has key 0 but a NaN
-__device__ __forceinline__ unsigned key_of(float z)
-{
-    const unsigned b = __float_as_uint(z);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float z_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // ---- what a row's scores are made of
 struct Row {
@@ -61,133 +47,24 @@ __device__ __forceinline__ float score_of(float x, float o, const Row& r)
     return s;
 }
 
-// f(n, x, o) for every token n < V, thread t on the chunks t, t + 1024, ...  The loads of BATCH chunks are issued before the first of them
-// is used: a pass is a handful of dependent round trips to L2 per thread, and this is what keeps them from queueing one behind the other.
+// f(n, x, o) for every token of the row, four chunks' loads in flight (for_each_row_token); a row without a penalty loads no occurrences
 constexpr int BATCH = 4;
-template <bool OCC, typename T, typename F> __device__ __forceinline__ void for_each_token_of(const T* lg, const Row& r, F f)
-{
-    for (int c0 = threadIdx.x; c0 < r.nch; c0 += BATCH * THREADS) {
-        float x[BATCH][8], o[BATCH][8];
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            const int c = c0 + u * THREADS;
-            if (c < r.nch) {
-                load8<T>(lg + 8 * c, x[u]);
-                if (OCC) load8<float>(r.occ + 8 * c, o[u]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            const int c = c0 + u * THREADS;
-            if (c < r.nch) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (8 * c + j < r.V) f(8 * c + j, x[u][j], OCC ? o[u][j] : 0.f);
-            }
-        }
-    }
-}
 template <typename T, typename F> __device__ __forceinline__ void for_each_token(const T* lg, const Row& r, F f)
 {
-    if (r.occ) for_each_token_of<true>(lg, r, f);
-    else for_each_token_of<false>(lg, r, f);
+    if (r.occ) for_each_row_token<BATCH>(lg, r.occ, r.V, r.nch, f);
+    else for_each_row_token<BATCH>(lg, nullptr, r.V, r.nch, f);
 }
 // ... and for the passes in front of the scores, which read the logits alone
 template <typename T, typename F> __device__ __forceinline__ void for_each_logit(const T* lg, const Row& r, F f)
 {
-    for_each_token_of<false>(lg, r, [&](int, float x, float) { f(x); });
+    for_each_row_token<BATCH>(lg, nullptr, r.V, r.nch, [&](int, float x, float) { f(x); });
 }
-
-// ---- workgroup and wave primitives.  Integer maxima and sums: any order gives the same bits.
-__device__ __forceinline__ u64 wave_max(u64 v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-        const u64 t = __shfl_xor(v, off);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-template <bool SUM> __device__ __forceinline__ u64 block_reduce(u64 v, u64* red)
-{
-    v = SUM ? wave_sum(v) : wave_max(v);
-    __syncthreads();                                         // red may still be read from the call before
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 m = red[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) m = SUM ? m + red[w] : (red[w] > m ? red[w] : m);
-    return m;
-}
-__device__ __forceinline__ unsigned wave_inclusive_scan(unsigned v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-struct Pick { unsigned digit, above, equal; };
-// One wave: the largest bin d of hist[256] with hist[d] > 0 and above + sum_{d' >= d} hist[d'] >= target; where there is none (fewer
-// entries than the target), the smallest bin with hist[d] > 0 (an empty histogram: bin 0).  .above: `above` plus everything in the bins
-// over d; .equal: hist[d].
-__device__ __forceinline__ Pick select_bin(const unsigned* hist, unsigned above, unsigned target)
-{
-    const int lane = threadIdx.x & 63;
-    unsigned h[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = hist[255 - (4 * lane + j)];         // lane 0 holds the top four bins
-    const unsigned mine = h[0] + h[1] + h[2] + h[3];
-    int first = -1, last = -1;
-    unsigned first_above = 0, first_equal = 0, last_above = 0, last_equal = 0, acc = above + wave_inclusive_scan(mine, lane) - mine;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (h[j] > 0) {
-            if (first < 0 && acc + h[j] >= target) { first = 255 - (4 * lane + j); first_above = acc; first_equal = h[j]; }
-            last = 255 - (4 * lane + j); last_above = acc; last_equal = h[j];
-        }
-        acc += h[j];
-    }
-    const u64 hit = __ballot(first >= 0), any = __ballot(last >= 0);
-    Pick p = {0u, above, 0u};
-    if (hit) {
-        const int src = __ffsll((long long)hit) - 1;
-        p.digit = (unsigned)__shfl(first, src); p.above = __shfl(first_above, src); p.equal = __shfl(first_equal, src);
-    } else if (any) {
-        const int src = 63 - __clzll((long long)any);
-        p.digit = (unsigned)__shfl(last, src); p.above = __shfl(last_above, src); p.equal = __shfl(last_equal, src);
-    }
-    return p;
-}
-
-// a thread's run of equal digits is added to the histogram once (the top digit of a row's keys takes a handful of values)
-struct Run {
-    unsigned digit = 0, count = 0;
-    __device__ __forceinline__ void add(unsigned* hist, unsigned d)
-    {
-        if (d != digit) { flush(hist); digit = d; }
-        ++count;
-    }
-    __device__ __forceinline__ void flush(unsigned* hist)
-    {
-        if (count) atomicAdd(&hist[digit], count);
-        count = 0;
-    }
-};
 
 struct Shared {
     unsigned hist[256];
-    u64 red[WAVES];
+    u64 red[ROW_WAVES];
     u64 won[BEAM_MAX_K];              // the winners as key << 32 | 65535 - token, in the order they arrived
-    Pick pick;
+    Pick<unsigned> pick;
     unsigned n_won;
 };
 
@@ -197,10 +74,10 @@ __device__ __forceinline__ void no_winners(const BeamArgs& a, int r)
 }
 
 template <typename T>
-__global__ void __launch_bounds__(THREADS) beam_rows_kernel(const BeamArgs a)
+__global__ void __launch_bounds__(ROW_THREADS) beam_rows_kernel(const BeamArgs a)
 {
     __shared__ Shared sh;
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K = a.K;
+    const int r = blockIdx.x, tid = threadIdx.x, K = a.K;
     const T* lg = static_cast<const T*>(a.logits) + (long)r * a.ld;
 
     // the group of the row: rows in no group, behind the first 64 of theirs, and dead rows leave an empty list and read nothing else
@@ -238,48 +115,23 @@ __global__ void __launch_bounds__(THREADS) beam_rows_kernel(const BeamArgs a)
     unsigned key_k = 0, above_k = 0, equal_k = 0;
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 24 - 8 * pass;
-        if (tid < 256) sh.hist[tid] = 0;
-        __syncthreads();
-        Run run;
-        for_each_token(lg, row, [&](int, float x, float o) {
-            const float s = score_of(x, o, row);
-            const unsigned key = key_of(s);
-            if (s > NEG_INF && (pass == 0 || (key ^ key_k) >> (shift + 8) == 0)) run.add(sh.hist, (key >> shift) & 255u);
-        });
-        run.flush(sh.hist);
-        __syncthreads();
-        if (wave == 0) {
-            const Pick p = select_bin(sh.hist, above_k, (unsigned)K);
-            if (lane == 0) sh.pick = p;
-        }
-        __syncthreads();
-        key_k |= sh.pick.digit << shift; above_k = sh.pick.above; equal_k = sh.pick.equal;
-    }
-    // ---- ties at the boundary: of the equal_k tokens at key_k the K - above_k lowest ids stay.  Where that is not all of them, the same
-    // selection over 65535 - n (two passes) finds the last id that stays.
-    unsigned rid_cut = 0;                                    // tokens at key_k stay while 65535 - n >= rid_cut
-    if (above_k < (unsigned)K && (unsigned)K - above_k < equal_k) {
-        unsigned above_id = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            const int shift = 8 - 8 * pass;
-            if (tid < 256) sh.hist[tid] = 0;
-            __syncthreads();
-            Run run;
-            for_each_token(lg, row, [&](int n, float x, float o) {
-                const unsigned rid = 65535u - (unsigned)n;
-                if (key_of(score_of(x, o, row)) == key_k && (pass == 0 || (rid ^ rid_cut) >> 8 == 0)) run.add(sh.hist, (rid >> shift) & 255u);
+        const Pick<unsigned> p = radix_step(sh.hist, &sh.pick, above_k, (unsigned)K, [&](auto add) {
+            for_each_token(lg, row, [&](int, float x, float o) {
+                const float s = score_of(x, o, row);
+                const unsigned key = key_of(s);
+                if (s > NEG_INF && (pass == 0 || (key ^ key_k) >> (shift + 8) == 0)) add((key >> shift) & 255u, 1u);
             });
-            run.flush(sh.hist);
-            __syncthreads();
-            if (wave == 0) {
-                const Pick p = select_bin(sh.hist, above_id, (unsigned)K - above_k);
-                if (lane == 0) sh.pick = p;
-            }
-            __syncthreads();
-            rid_cut |= sh.pick.digit << shift;
-            above_id = sh.pick.above;
-        }
+        });
+        key_k |= p.digit << shift; above_k = p.above; equal_k = p.equal;
     }
+    // ---- ties at the boundary: of the equal_k tokens at key_k the K - above_k lowest ids stay (tie_cut)
+    unsigned rid_cut = 0;                                    // tokens at key_k stay while 65535 - n >= rid_cut
+    if (above_k < (unsigned)K && (unsigned)K - above_k < equal_k)
+        rid_cut = tie_cut(sh.hist, &sh.pick, (unsigned)K - above_k, [&](auto at) {
+            for_each_token(lg, row, [&](int n, float x, float o) {
+                if (key_of(score_of(x, o, row)) == key_k) at(n);
+            });
+        });
 
     // ---- the winners, in the order they arrive (at most K by construction; the bound is checked where the list is written all the same)
     if (tid == 0) sh.n_won = 0;
@@ -344,7 +196,7 @@ hipError_t launch_beam_candidates(const BeamArgs& a, int io, hipStream_t st)
     if (!(a.logits && a.cum && a.cu_rows && a.parent && a.token && a.score && a.keys && a.ids)) return hipErrorInvalidValue;
     if (a.n_rows < 1 || a.n_groups < 1 || a.K < 1 || a.K > BEAM_MAX_K || a.V < 1 || a.V > BEAM_MAX_V || a.ld < a.V || a.ld % 8) return hipErrorInvalidValue;
     if (a.occ && a.n_slots < 1) return hipErrorInvalidValue;
-    const dim3 grid(a.n_rows), block(THREADS);
+    const dim3 grid(a.n_rows), block(ROW_THREADS);
     hipError_t e;
     if (io == IO_F32) e = launch<beam_rows_kernel<float>>(grid, block, 0, st, a);
     else if (io == IO_F16) e = launch<beam_rows_kernel<f16_t>>(grid, block, 0, st, a);
@@ -366,12 +218,6 @@ size_t rwkv6_beam_candidates_workspace_bytes(int n_rows, int K)
 {
     if (n_rows < 1 || K < 1 || K > BEAM_MAX_K) return 0;
     return 2 * list_bytes(n_rows, K);
-}
-
-static bool overlap(const void* p, size_t p_bytes, const void* q, size_t q_bytes)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return p && q && a < b + q_bytes && b < a + p_bytes;
 }
 
 static int beam_candidates(int n_rows, int V, int ld, const void* logits, const float* cum, int n_groups, const int* cu_rows, int K,

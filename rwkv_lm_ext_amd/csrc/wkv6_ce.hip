@@ -23,7 +23,6 @@ namespace wkv6 {
 namespace {
 
 constexpr int CE_THREADS = 1024, CE_WAVES = CE_THREADS / 64, CE_UNROLL = 4;
-constexpr float NEG_INF = -__builtin_inff();
 constexpr long long CE_IGNORE = -100;
 enum { CE_STATS = 0, CE_FUSED = 1, CE_GRAD = 2 };            // statistics only; statistics and gradient in one launch; gradient from stored statistics
 

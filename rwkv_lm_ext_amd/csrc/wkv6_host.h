@@ -13,6 +13,13 @@ inline int to_rc(hipError_t e) { return e == hipSuccess ? WKV6_OK : (int)e; }
 constexpr size_t ALIGN = 256;
 inline size_t align_up(size_t x) { return (x + ALIGN - 1) / ALIGN * ALIGN; }
 
+// do the byte ranges [p, p + pn) and [q, q + qn) meet?  A null pointer meets nothing: whether it may be null is the entry point's to say
+inline bool overlap(const void* p, size_t pn, const void* q, size_t qn)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + qn && b < a + pn;
+}
+
 inline int check_shape(int B, int T, int C, int H)
 {
     if (B < 1 || T < 1 || C < 1 || H < 1) return WKV6_EINVAL;

@@ -5,11 +5,8 @@
 //     y[t,n]  = bf16( fmaf(scale[a], sum_j xa[t,j] B[a,n,j], float(y[t,n])) )   ("expand",  B_pool bf16 [n_adapters,N,R])
 // and every other row keeps its bits.  Two launches in stream order with the bf16 xa [total_T,R] between them in the workspace.
 //
-// Both kernels work on tiles of 16 packed rows with v_mfma_f32_16x16x32_bf16, the TOKEN as the MFMA column: lane (c = lane & 15,
-// g = lane >> 4) feeds 8 consecutive k of token c (one 16-byte global load of x[row] / xa[row]) and 8 consecutive k of pool row c
-// (one 16-byte load of A[a,j] / B[a,n]), and receives rows 4g..4g+3 of column c -- four consecutive j (or n) of its own token, which
-// leave as one wide store.  No LDS for the operands.  Every output element is its own dot product in the MFMA's own k order, so a
-// row's result does not depend on the rows beside it.
+// Both kernels work on the 16-row MFMA tile of wkv6_tile16.h (lane roles, K walk, expand tile), shared with wkv6_lowrank.hip; the token
+// operand is x[row] / xa[row], the weight operand A[a,j] / B[a,n].  This file's own are the adapter groups:
 //
 // A tile may hold up to 16 adapters (decode tokens).  Each wave finds the adapter of the tile's 16 rows (bisection in cu_seqlens, the
 // rule of the packed kernels of wkv6_mix.hip; the adapter number is judged before anything is addressed with it) and walks the GROUPS of
@@ -17,21 +14,15 @@
 // literal zero, and only the lanes of the group's rows keep (select by lane) what the pass computed.  Nothing is masked by a multiply:
 // a NaN in adapter a's matrices stays in the discarded columns of a's pass.
 #include <climits>
-#include "wkv6_host.h"                 // launch<>, to_rc
+#include "wkv6_host.h"                 // launch<>, to_rc, overlap
+#include "wkv6_tile16.h"
 
 namespace wkv6 {
 namespace {
 
-typedef __bf16 b8v __attribute__((ext_vector_type(8)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-
-constexpr int TILE = 16;               // packed rows per tile (the MFMA's 16 columns)
 constexpr int SHRINK_WAVES = 8;        // waves of a shrink workgroup: they share the (group, K chunk) work items of one tile
 constexpr int SHRINK_CHUNKS = 4;       // K is cut into min(4, K / 32) interleaved chunks of 32-wide steps: fixed by K alone
 constexpr int EXPAND_WAVES = 4;        // waves of an expand workgroup: wave w serves the tile's groups w, w + 4, ...
-constexpr int EXPAND_NB = 64;          // output columns per pass of a wave (4 MFMA tiles: 16 consecutive n per lane)
 constexpr int EXPAND_GRID_Y = 16;      // at most this many workgroups share a tile's N / 64 column blocks
 
 struct LoraArgs {
@@ -68,10 +59,6 @@ __device__ __forceinline__ int row_adapter(const LoraArgs& a, long row)
     return ad >= 0 && ad < a.n_adapters ? ad : -1;
 }
 
-__device__ __forceinline__ b8v zero8() { return __builtin_bit_cast(b8v, v4u{0u, 0u, 0u, 0u}); }
-__device__ __forceinline__ b8v load8(const bf16_t* p) { return __builtin_bit_cast(b8v, *reinterpret_cast<const v4u*>(p)); }
-__device__ __forceinline__ f4v mfma32(b8v a, b8v b, f4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
 // Walks the groups of equal adapter among the tile's 16 rows (`mine`: the adapter of row lane & 15, -1: none; the four 16-lane rows of
 // the wave hold copies).  f(index, adapter, in_group): adapter is wave-uniform, in_group per lane.
 template <typename F> __device__ __forceinline__ void for_each_group(int mine, F f)
@@ -87,16 +74,16 @@ template <typename F> __device__ __forceinline__ void for_each_group(int mine, F
 }
 
 // ---- shrink: xa = bf16(x A[a]^T).  One workgroup per (tile of 16 rows, 16 columns j of xa); MFMA rows = j, columns = tokens, so lane
-// (c, g) ends with xa[row c][j0 + 4g .. + 3].  The work items of a tile are (group, K chunk): chunk q takes the 32-wide k steps q, q + NCH,
-// q + 2 NCH, ... with NCH = min(4, K / 32) -- fixed by K alone -- and the items go round the waves.  An item leaves its fp32 partial sums
-// in LDS at [chunk][token][j] (a token is in one group only, so the items never meet), and after the barrier wave 0 adds a token's chunks
-// in the order 0, 1, 2, 3, rounds once and stores.  Rows of R that do not exist (R = 8: j = 8..15) are literal zeros, never loaded; a
-// token outside the group, or past total_T, is a literal zero too.
+// (c, g) ends with xa[row c][j0 + 4g .. + 3].  The work items of a tile are (group, K chunk of for_each_kstep) and go round the waves.  An
+// item chains its steps in one fp32 accumulator and leaves it in LDS (a token is in one group only, so the items never meet); after the
+// barrier wave 0 adds a token's chunks (sum_chunks), rounds once and stores.  Rows of R that do not exist (R = 8: j = 8..15) are literal
+// zeros, never loaded; a token outside the group, or past total_T, is a literal zero too.
 template <int R>
 __global__ void __launch_bounds__(SHRINK_WAVES * 64) lora_shrink_kernel(const LoraArgs a)
 {
-    __shared__ float part[SHRINK_CHUNKS][TILE][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    __shared__ __align__(16) float part[SHRINK_CHUNKS][TILE][16];     // (written and read four at a time)
+    const Lane16 ln;
+    const int wave = ln.wave, c = ln.c, g = ln.g;
     const long row = (long)blockIdx.x * TILE + c;
     const int j = blockIdx.y * 16 + c;                   // the pool row this lane feeds
     const bool j_ok = j < R;
@@ -109,48 +96,34 @@ __global__ void __launch_bounds__(SHRINK_WAVES * 64) lora_shrink_kernel(const Lo
         for (int q = 0; q < nch; ++q, ++item) {
             if (item % SHRINK_WAVES != wave) continue;
             f4v acc = {0.f, 0.f, 0.f, 0.f};
-            int s = q;
-            for (; s + 3 * nch < nsteps; s += 4 * nch) {               // four steps' loads in flight
-                b8v af[4], xf[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int k = 32 * (s + u * nch);
-                    af[u] = j_ok ? load8(ar + k) : zero8();
-                    xf[u] = in ? load8(xr + k) : zero8();
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) acc = mfma32(af[u], xf[u], acc);
-            }
-            for (; s < nsteps; s += nch) {
-                const b8v af = j_ok ? load8(ar + 32 * s) : zero8();
-                const b8v xf = in ? load8(xr + 32 * s) : zero8();
-                acc = mfma32(af, xf, acc);
-            }
+            b8v af[4], xf[4];
+            for_each_kstep(q, nch, nsteps,
+                           [&](int u, int k) {
+                               af[u] = j_ok ? load8(ar + k) : zero8();
+                               xf[u] = in ? load8(xr + k) : zero8();
+                           },
+                           [&](int u) { acc = mfma32(af[u], xf[u], acc); });
             if (in) *reinterpret_cast<float4*>(&part[q][c][4 * g]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
         }
     });
     __syncthreads();
     const int j0 = blockIdx.y * 16 + 4 * g;
     if (wave == 0 && mine >= 0 && j0 < R) {
-        float4 sum = *reinterpret_cast<const float4*>(&part[0][c][4 * g]);
-        for (int q = 1; q < nch; ++q) {
-            const float4 p = *reinterpret_cast<const float4*>(&part[q][c][4 * g]);
-            sum.x += p.x; sum.y += p.y; sum.z += p.z; sum.w += p.w;
-        }
-        *reinterpret_cast<v2u*>(a.xa + row * R + j0) = v2u{pack_bf2(sum.x, sum.y), pack_bf2(sum.z, sum.w)};
+        const auto sum = sum_chunks(part, nch, c, g);
+        *reinterpret_cast<v2u*>(a.xa + row * R + j0) = v2u{pack_bf2(sum[0], sum[1]), pack_bf2(sum[2], sum[3])};
     }
 }
 
 // ---- expand: y = bf16(fmaf(scale[a], xa B[a]^T, y)).  One workgroup per tile of 16 rows and share of the N / 64 column blocks; wave w
 // serves the tile's groups w, w + 4, ...  MFMA rows = n, columns = tokens, contraction over j: one step of 32 for R <= 32 (for R = 8 and
-// 16 the lanes whose 8 j lie past R hold literal zeros in both operands), two for R = 64.  MFMA row rho of tile i stands for column
-// n0 + 16 (rho >> 2) + 4 i + (rho & 3), so that lane (c, g) ends with the 16 CONSECUTIVE columns n0 + 16 g .. + 15 of its token: the
-// read-modify-write of y is two 16-byte accesses per lane, 128 contiguous bytes per token.  Only the lanes of the group's rows touch y.
+// 16 the lanes whose 8 j lie past R hold literal zeros in both operands), two for R = 64.  The tile and its column map are expand_pass's
+// (wkv6_tile16.h): the read-modify-write of y is two 16-byte accesses per lane.  Only the lanes of the group's rows touch y.
 template <int R>
 __global__ void __launch_bounds__(EXPAND_WAVES * 64) lora_expand_kernel(const LoraArgs a)
 {
     constexpr int STEPS = R == 64 ? 2 : 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const Lane16 ln;
+    const int wave = ln.wave, c = ln.c, g = ln.g;
     const long row = (long)blockIdx.x * TILE + c;
     const int mine = row_adapter(a, row);
     const bool j_ok = 8 * g < R;                         // (R >= 32: every lane)
@@ -165,28 +138,15 @@ __global__ void __launch_bounds__(EXPAND_WAVES * 64) lora_expand_kernel(const Lo
         for (int nb = blockIdx.y; nb < nblocks; nb += gridDim.y) {
             const int n0 = nb * EXPAND_NB;
             f4v acc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int n = n0 + 16 * (c >> 2) + 4 * i + (c & 3);
-                acc[i] = f4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int st = 0; st < STEPS; ++st) {
-                    const b8v bf = j_ok ? load8(bp + (long)n * R + 32 * st) : zero8();
-                    acc[i] = mfma32(bf, xf[st], acc[i]);
-                }
-            }
+            expand_pass<R, STEPS>(acc, bp, j_ok, n0, c, xf);
             if (in) {
                 v4u* yp = reinterpret_cast<v4u*>(a.y + row * a.N + n0 + 16 * g);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const v4u old = yp[h];
-                    v4u out;
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {        // word p of half h: columns 8 h + 2 p, + 1 = tile i = 2 h + (p >> 1), rows 2 (p & 1), + 1
-                        const int i = 2 * h + (p >> 1), q = 2 * (p & 1);
-                        out[p] = pack_bf2(fmaf(sc, acc[i][q], bf_lo(old[p])), fmaf(sc, acc[i][q + 1], bf_hi(old[p])));
-                    }
-                    yp[h] = out;
+                    yp[h] = expand_half(acc, h, [&](int p, float lo, float hi) {
+                        return pack_bf2(fmaf(sc, lo, bf_lo(old[p])), fmaf(sc, hi, bf_hi(old[p])));
+                    });
                 }
             }
         }
@@ -212,11 +172,6 @@ hipError_t launch_lora_packed(const LoraArgs& a, hipStream_t st)
     }
 }
 
-bool overlap(const void* p, size_t pn, const void* q, size_t qn)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
-}
 bool rank_ok(int R) { return R == 8 || R == 16 || R == 32 || R == 64; }
 
 }  // namespace

@@ -8,29 +8,20 @@
 // stand for: lead, the product in front of tanh, low and corr are each rounded to bf16 once; what differs is how the sums inside the
 // two contractions are taken (the shrink's: 32 products in fp32 inside an MFMA, the steps in fp64; the expand's: an fp32 MFMA chain).
 //
-// Both kernels are the pair of wkv6_lora.hip without its adapter groups: tiles of 16 rows on v_mfma_f32_16x16x32_bf16 with the TOKEN as the
-// MFMA column.  Lane (c = lane & 15, g = lane >> 4) feeds 8 consecutive k of token c (one 16-byte global load) and 8 consecutive k of
-// weight row c (one 16-byte load of a matrix in nn.Linear layout [out, in]), and receives rows 4g..4g+3 of column c.  No LDS for the
-// operands.  Every output element is its own dot product in the MFMA's own k order, so a row's bits do not depend on the rows beside it,
-// on its place in the tile or on the batch.  A row past the end is a literal zero operand, never loaded, never stored, and nothing is
-// masked by a multiply.
+// Both kernels work on the 16-row MFMA tile of wkv6_tile16.h (lane roles, K walk, expand tile), shared with wkv6_lora.hip, here without
+// adapter groups and with the weights in nn.Linear layout [out, in]: a row's bits do not depend on the rows beside it, on its place in the
+// tile or on the batch.  A row past the end is a literal zero operand, never loaded, never stored.
 //
 // Which token stands in front of a row is the rule of ddlerp_fwd_slots_kernel (wkv6_mix.hip), front_of below.
 #include <climits>
-#include "wkv6_host.h"                 // launch<>, to_rc
+#include "wkv6_host.h"                 // launch<>, to_rc, overlap
+#include "wkv6_tile16.h"
 
 namespace wkv6 {
 namespace {
 
-typedef __bf16 b8v __attribute__((ext_vector_type(8)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef unsigned v4u __attribute__((ext_vector_type(4)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-
-constexpr int TILE = 16;               // rows per tile (the MFMA's 16 columns)
 constexpr int SHRINK_WAVES = 4;        // waves of a shrink workgroup = the most K chunks: wave q sums chunk q
 constexpr int EXPAND_WAVES = 4;        // waves of an expand workgroup: wave w serves column block 4 blockIdx.y + w of the tile
-constexpr int EXPAND_NB = 64;          // output columns per wave (4 MFMA tiles: 16 consecutive n per lane)
 
 struct LowrankArgs {
     int rows, n_seq, C, N, DT, n_slots;   // C: width of x / xw (the shrink's K);  N: output columns of the expand;  DT: columns of low
@@ -45,11 +36,6 @@ struct LowrankArgs {
     bf16_t* out;              // lerp: [5,rows,N];  bias: [rows,N]
     bf16_t* low;              // [rows,DT]  (workspace)
 };
-
-__device__ __forceinline__ b8v zero8() { return __builtin_bit_cast(b8v, v4u{0u, 0u, 0u, 0u}); }
-__device__ __forceinline__ v4u ld16(const bf16_t* p) { return *reinterpret_cast<const v4u*>(p); }
-__device__ __forceinline__ b8v load8(const bf16_t* p) { return __builtin_bit_cast(b8v, ld16(p)); }
-__device__ __forceinline__ f4v mfma32(b8v a, b8v b, f4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 // The token in front of row `row` (0 <= row < rows): where its C channels lie, or null for a zero token.  Row t is the first row of
 // sequence s = seq_of_row(t) iff cu[s] == t; every other row, rows outside every sequence included, takes row t - 1, and row 0 takes zero
@@ -93,16 +79,17 @@ __device__ __forceinline__ float to_odd_f32(double v)
 
 // ---- shrink: low = bf16(tanh(float(bf16(a W1t^T)))), a = the rows of x (the decay) or the lerp with maa_x formed in registers (LERP).
 // One workgroup per (tile of 16 rows, 16 columns j of low); MFMA rows = j, columns = tokens, so lane (c, g) ends with low[row c][j0 + 4g
-// .. + 3].  K = C is cut into NCH = min(4, C / 32) interleaved chunks of 32-wide steps -- fixed by C alone --, wave q takes the steps q,
-// q + NCH, ...  Every MFMA sums its 32 products in fp32 from a zero accumulator and the steps' results are added in fp64 (four adds a lane
-// and step): the product in front of tanh is then off its exact value by about 1e-8 at C = 4096, where an fp32 chain over the steps is
-// off by 2e-7 and rounds to the other bf16 neighbour ten times as often.  The waves leave their fp64 sums in LDS, and after the barrier
-// wave 0 adds a token's chunks in the order 0, 1, 2, 3, rounds once to bf16, takes the tanh of the rounded value in fp64 and rounds once.
+// .. + 3].  K = C is walked in the chunks of for_each_kstep (wkv6_tile16.h), wave q takes chunk q.  Every MFMA sums its 32 products in
+// fp32 from a zero accumulator and the steps' results are added in fp64 (four adds a lane and step): the product in front of tanh is
+// then off its exact value by about 1e-8 at C = 4096, where an fp32 chain over the steps is off by 2e-7 and rounds to the other bf16
+// neighbour ten times as often.  The waves leave their fp64 sums in LDS, and after the barrier wave 0 adds a token's chunks
+// (sum_chunks), rounds once to bf16, takes the tanh of the rounded value in fp64 and rounds once.
 template <bool LERP>
 __global__ void __launch_bounds__(SHRINK_WAVES * 64) lowrank_shrink_kernel(const LowrankArgs a)
 {
-    __shared__ double part[SHRINK_WAVES][TILE][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    __shared__ __align__(32) double part[SHRINK_WAVES][TILE][16];               // (sum_chunks reads four at a time)
+    const Lane16 ln;
+    const int wave = ln.wave, c = ln.c, g = ln.g;
     const long row = (long)blockIdx.x * TILE + c;
     const bool in = row < a.rows;
     const int nsteps = a.C / 32, nch = min(SHRINK_WAVES, nsteps);
@@ -125,40 +112,22 @@ __global__ void __launch_bounds__(SHRINK_WAVES * 64) lowrank_shrink_kernel(const
     if (wave < nch) {
         const f4v zero = {0.f, 0.f, 0.f, 0.f};
         double acc[4] = {0., 0., 0., 0.};
-        int s = wave;
-        for (; s + 3 * nch < nsteps; s += 4 * nch) {                   // four steps' loads in flight
-            b8v wf[4];
-            v4u xv[4], pv[4], mv[4];
+        b8v wf[4];
+        v4u xv[4], pv[4], mv[4];
+        for_each_kstep(wave, nch, nsteps,
+                       [&](int u, int k) {
+                           wf[u] = load8(wr + k);
+                           xv[u] = in ? ld16(xr + k) : z;
+                           if constexpr (LERP) {
+                               pv[u] = pr ? ld16(pr + k) : z;
+                               mv[u] = ld16(mr + k);
+                           }
+                       },
+                       [&](int u) {
+                           const f4v p = mfma32(wf[u], in ? token(xv[u], pv[u], mv[u]) : zero8(), zero);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = 32 * (s + u * nch);
-                wf[u] = load8(wr + k);
-                xv[u] = in ? ld16(xr + k) : z;
-                if constexpr (LERP) {
-                    pv[u] = pr ? ld16(pr + k) : z;
-                    mv[u] = ld16(mr + k);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const f4v p = mfma32(wf[u], in ? token(xv[u], pv[u], mv[u]) : zero8(), zero);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] += (double)p[i];
-            }
-        }
-        for (; s < nsteps; s += nch) {
-            const int k = 32 * s;
-            const b8v wf = load8(wr + k);
-            const v4u xv = in ? ld16(xr + k) : z;
-            v4u pv = z, mv = z;
-            if constexpr (LERP) {
-                if (pr) pv = ld16(pr + k);
-                mv = ld16(mr + k);
-            }
-            const f4v p = mfma32(wf, in ? token(xv, pv, mv) : zero8(), zero);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] += (double)p[i];
-        }
+                           for (int i = 0; i < 4; ++i) acc[i] += (double)p[i];
+                       });
         if (in) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) part[wave][c][4 * g + i] = acc[i];
@@ -166,12 +135,11 @@ __global__ void __launch_bounds__(SHRINK_WAVES * 64) lowrank_shrink_kernel(const
     }
     __syncthreads();
     if (wave == 0 && in) {
+        const auto sum = sum_chunks(part, nch, c, g);
         float t[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            double sum = part[0][c][4 * g + i];
-            for (int q = 1; q < nch; ++q) sum += part[q][c][4 * g + i];
-            const float z = bf_lo(pack_bf2(to_odd_f32(sum), 0.f));                        // the product, rounded as the matmul's output is
+            const float z = bf_lo(pack_bf2(to_odd_f32(sum[i]), 0.f));                     // the product, rounded as the matmul's output is
             t[i] = to_odd_f32(tanh((double)z));
         }
         *reinterpret_cast<v2u*>(a.low + row * a.DT + blockIdx.y * 16 + 4 * g) = v2u{pack_bf2(t[0], t[1]), pack_bf2(t[2], t[3])};
@@ -179,9 +147,8 @@ __global__ void __launch_bounds__(SHRINK_WAVES * 64) lowrank_shrink_kernel(const
 }
 
 // ---- expand: corr = bf16(low W2t^T) and one of two epilogues.  One workgroup per tile of 16 rows and 4 blocks of 64 output columns, a
-// wave per block.  MFMA rows = n, columns = tokens, contraction over j in R / 32 steps.  MFMA row rho of tile i stands for column
-// n0 + 16 (rho >> 2) + 4 i + (rho & 3), so that lane (c, g) ends with the 16 CONSECUTIVE columns n0 + 16 g .. + 15 of its token: every
-// access of the epilogue is two 16-byte accesses per lane, 128 contiguous bytes per token.
+// wave per block.  Contraction over j in R / 32 steps; the tile and its column map are expand_pass's (wkv6_tile16.h): lane (c, g) ends with
+// the 16 consecutive columns n0 + 16 g .. + 15 of its token.
 //   LERP:  out[s][t,n] = bf16(fmaf(xp - x, maa5[s][n] + corr_s[t,n], x)),  s = 0..4 with low_s = low[t, s R .. (s + 1) R) and W2t[s] [N,R];
 //          x and xp - x of the lane's 16 channels are loaded once and serve the five planes
 //   else:  out[t,n] = bf16(bias[n] + corr[t,n])
@@ -189,7 +156,8 @@ template <int R, bool LERP>
 __global__ void __launch_bounds__(EXPAND_WAVES * 64) lowrank_expand_kernel(const LowrankArgs a)
 {
     constexpr int STEPS = R / 32, NS = LERP ? 5 : 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+    const Lane16 ln;
+    const int wave = ln.wave, c = ln.c, g = ln.g;
     const long row = (long)blockIdx.x * TILE + c;
     const bool in = row < a.rows;
     const int nb = blockIdx.y * EXPAND_WAVES + wave;
@@ -218,28 +186,19 @@ __global__ void __launch_bounds__(EXPAND_WAVES * 64) lowrank_expand_kernel(const
         for (int st = 0; st < STEPS; ++st) lf[st] = in ? load8(a.low + row * a.DT + s * R + 32 * st + 8 * g) : zero8();
         const bf16_t* wp = a.W2t + (long)s * a.N * R + 8 * g;
         f4v acc[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + 16 * (c >> 2) + 4 * i + (c & 3);
-            acc[i] = f4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int st = 0; st < STEPS; ++st) acc[i] = mfma32(load8(wp + (long)n * R + 32 * st), lf[st], acc[i]);
-        }
+        expand_pass<R, STEPS>(acc, wp, true, n0, c, lf);
         if (in) {
             const bf16_t* bp = a.bias + (long)s * a.N + nl;
             v4u* op = reinterpret_cast<v4u*>(a.out + ((long)s * a.rows + row) * a.N + nl);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const v4u b = ld16(bp + 8 * h);
-                v4u o;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {            // word p of half h: columns 8 h + 2 p, + 1 = tile i = 2 h + (p >> 1), rows 2 (p & 1), + 1
-                    const int i = 2 * h + (p >> 1), q = 2 * (p & 1), e = 8 * h + 2 * p;
-                    const unsigned corr = pack_bf2(acc[i][q], acc[i][q + 1]);            // rounded as the matmul's output is
-                    if constexpr (LERP) o[p] = pack_bf2(fmaf(d[e], bf_lo(b[p]) + bf_lo(corr), x[e]), fmaf(d[e + 1], bf_hi(b[p]) + bf_hi(corr), x[e + 1]));
-                    else o[p] = pack_bf2(bf_lo(b[p]) + bf_lo(corr), bf_hi(b[p]) + bf_hi(corr));
-                }
-                op[h] = o;
+                op[h] = expand_half(acc, h, [&](int p, float lo, float hi) {
+                    const int e = 8 * h + 2 * p;                                       // the word's lower column among the lane's 16
+                    const unsigned corr = pack_bf2(lo, hi);                            // rounded as the matmul's output is
+                    if constexpr (LERP) return pack_bf2(fmaf(d[e], bf_lo(b[p]) + bf_lo(corr), x[e]), fmaf(d[e + 1], bf_hi(b[p]) + bf_hi(corr), x[e + 1]));
+                    else return pack_bf2(bf_lo(b[p]) + bf_lo(corr), bf_hi(b[p]) + bf_hi(corr));
+                });
             }
         }
     }
@@ -253,11 +212,6 @@ template <int R, bool LERP> hipError_t launch_lowrank(const LowrankArgs& a, hipS
     return launch<lowrank_expand_kernel<R, LERP>>(dim3(tiles, (nblocks + EXPAND_WAVES - 1) / EXPAND_WAVES), dim3(EXPAND_WAVES * 64), 0, st, a);
 }
 
-bool overlap(const void* p, size_t pn, const void* q, size_t qn)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return q && a < b + qn && b < a + pn;
-}
 // a row width the kernels have: a multiple of 64, at most 4096 (check_rows of wkv6_mix.hip)
 bool width_ok(int C) { return C >= 64 && C % 64 == 0 && C <= 4096; }
 

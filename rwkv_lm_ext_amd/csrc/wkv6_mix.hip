@@ -524,12 +524,6 @@ int check_rows(long rows, int C)
     return WKV6_OK;
 }
 
-bool overlap(const void* p, size_t pn, const void* q, size_t qn)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
-}
-
 // The (NS, m) pairs the lerp kernels are built for, in one place: f(NS, HAS_M), both as integral constants, launches; any other pair is
 // refused.
 template <typename F> int dispatch_lerp(int NS, bool has_m, F f)

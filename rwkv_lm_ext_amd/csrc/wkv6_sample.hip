@@ -6,6 +6,8 @@
 // occurrence row itself: the kept set of the definition is a THRESHOLD on the penalised logit z, so it is found by radix selection over
 // the monotone 32-bit key of z -- four passes of 8 bits, most significant digit first, with one 256-bin histogram of probability MASS
 // (nucleus) and one of COUNTS (top-k) in LDS -- and the ties at the top-k boundary are cut by a second radix selection over the token id.
+// The pieces of the selection (keys, row walker, histogram runs, select_bin, tie_cut) are those of wkv6_rows.h, shared with wkv6_beam.hip;
+// the pass that fills both histograms in ONE walk of the row is this file's own.
 //
 // Where the row lives: in neither registers nor LDS.  Every pass streams the row again as 16-byte loads (thread t takes the chunks of 8
 // tokens t, t + 1024, ...) and recomputes z; after the first pass the loads are served by L2 / Infinity Cache, so a logits row and an
@@ -18,8 +20,8 @@
 // 2^46 stay below 2^63.  The quantisation is 2^-46 of the largest weight per term.
 #include <cmath>
 #include "wkv6_sample.h"
-#include "wkv6_rows.h"                 // load8, load1
-#include "wkv6_host.h"                 // to_rc
+#include "wkv6_rows.h"                 // load8, load1, the row walker, the radix selection, block_reduce
+#include "wkv6_host.h"                 // to_rc, overlap
 
 // the same expression must give the same bits wherever it is inlined (weights are formed once for W and once more for the draw)
 #pragma clang fp contract(off)
@@ -27,20 +29,7 @@
 namespace wkv6 {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int THREADS = 1024, WAVES = THREADS / 64;
 constexpr int PARTS = SAMPLE_MAX_V / 8 / 64;                  // 128: the chunks of 8 tokens come in blocks of 64 (one wave, one round)
-constexpr float FIX = 70368744177664.f;                      // 2^46
-constexpr float NEG_INF = -__builtin_inff();
-
-// ---- the monotone key of a (non-NaN) float: a > b  <=>  key(a) > key(b)
-__device__ __forceinline__ unsigned key_of(float z)
-{
-    const unsigned b = __float_as_uint(z);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float z_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // ---- what a sequence's row is made of
 struct Row {
@@ -67,6 +56,7 @@ __device__ __forceinline__ float repeat_penalty(float z, float o, const Row& r)
 // floor(exp((z - top) / t) * 2^46): at most 2^46, 0 for z = -inf (and for a NaN, which only garbage parameters can make)
 __device__ __forceinline__ u64 weight(float z, float top, float t) { return (u64)(expf((z - top) / t) * FIX); }
 
+// z and o of the 8 tokens of chunk c, for the passes that keep a chunk's weights in registers (W and the draw)
 template <typename T> __device__ __forceinline__ void load_chunk(const T* lg, const Row& r, int c, float (&z)[8], float (&o)[8])
 {
     float x[8];
@@ -78,110 +68,23 @@ template <typename T> __device__ __forceinline__ void load_chunk(const T* lg, co
         z[j] = penalise(x[j], o[j], r);
     }
 }
-// f(n, z, o) for every token n < V, thread t on the chunks t, t + 1024, ...
+// f(n, z, o) for every token n < V, one chunk's loads in flight (for_each_row_token)
 template <typename T, typename F> __device__ __forceinline__ void for_each_token(const T* lg, const Row& r, F f)
 {
-    for (int c = threadIdx.x; c < r.nch; c += THREADS) {
-        float z[8], o[8];
-        load_chunk(lg, r, c, z, o);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (8 * c + j < r.V) f(8 * c + j, z[j], o[j]);
-    }
+    for_each_row_token<1>(lg, r.src, r.V, r.nch, [&](int n, float x, float o) { f(n, penalise(x, o, r), o); });
 }
-
-// ---- workgroup and wave primitives.  Integer maxima and sums: any order gives the same bits.
-__device__ __forceinline__ u64 block_max(u64 v, u64* red)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-        const u64 t = __shfl_xor(v, off);
-        v = t > v ? t : v;
-    }
-    __syncthreads();                                         // red may still be read from the call before
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 m = red[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) m = red[w] > m ? red[w] : m;
-    return m;
-}
-__device__ __forceinline__ u64 wave_sum(u64 v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ u64 wave_inclusive_scan(u64 v, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u64 t = __shfl_up(v, off);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-struct Pick { unsigned digit; u64 above, equal; };
-// One wave: the largest bin d of hist[256] with hist[d] > 0 and above + sum_{d' >= d} hist[d'] >= target; where rounding leaves none,
-// the smallest bin with hist[d] > 0 (an empty histogram: bin 0).  .above: `above` plus everything in the bins over d; .equal: hist[d].
-__device__ __forceinline__ Pick select_bin(const u64* hist, u64 above, u64 target)
-{
-    const int lane = threadIdx.x & 63;
-    u64 h[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = hist[255 - (4 * lane + j)];         // lane 0 holds the top four bins
-    const u64 mine = h[0] + h[1] + h[2] + h[3];
-    const u64 before = above + wave_inclusive_scan(mine, lane) - mine;
-    int first = -1, last = -1;
-    u64 first_above = 0, first_equal = 0, last_above = 0, last_equal = 0, acc = before;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (h[j] > 0) {
-            if (first < 0 && acc + h[j] >= target) { first = 255 - (4 * lane + j); first_above = acc; first_equal = h[j]; }
-            last = 255 - (4 * lane + j); last_above = acc; last_equal = h[j];
-        }
-        acc += h[j];
-    }
-    const u64 hit = __ballot(first >= 0), any = __ballot(last >= 0);
-    Pick p = {0u, above, 0};
-    if (hit) {
-        const int src = __ffsll((long long)hit) - 1;
-        p.digit = (unsigned)__shfl(first, src); p.above = __shfl(first_above, src); p.equal = __shfl(first_equal, src);
-    } else if (any) {
-        const int src = 63 - __clzll((long long)any);
-        p.digit = (unsigned)__shfl(last, src); p.above = __shfl(last_above, src); p.equal = __shfl(last_equal, src);
-    }
-    return p;
-}
-
-// a thread's run of equal digits is added to the histogram once (the top digit of a row's keys takes a handful of values)
-struct Run {
-    unsigned digit = 0;
-    u64 sum = 0;
-    __device__ __forceinline__ void add(u64* hist, unsigned d, u64 v)
-    {
-        if (d != digit) { flush(hist); digit = d; }
-        sum += v;
-    }
-    __device__ __forceinline__ void flush(u64* hist)
-    {
-        if (sum) atomicAdd(&hist[digit], sum);
-        sum = 0;
-    }
-};
 
 struct Shared {
     u64 hist_p[256], hist_k[256];     // nucleus: mass per digit; top-k (and the id selection behind it): count per digit
-    u64 red[WAVES];
+    u64 red[ROW_WAVES];
     u64 part[PARTS];                  // W per (round, wave) = per 512 consecutive tokens
-    Pick pick_p, pick_k;
+    Pick<u64> pick_p, pick_k;
     u64 base;                         // the draw: W in front of the block that holds the token, and the block
     int block, token;
 };
 
 template <typename T>
-__global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs a)
+__global__ void __launch_bounds__(ROW_THREADS) sample_slots_kernel(const SampleArgs a)
 {
     __shared__ Shared sh;
     const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -208,21 +111,14 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
     // ---- pass A: is the row sound, and max z.  (A logit of +inf has no softmax: it poisons the row like a NaN.)
     int bad = 0, finite = 0;
     unsigned kmax = 0;
-    for (int c = tid; c < r.nch; c += THREADS) {
-        float x[8], z[8], o[8];
-        load8<T>(lg + 8 * c, x);
-        load_chunk(lg, r, c, z, o);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (8 * c + j < r.V) {
-                bad |= !(x[j] < __builtin_inff());
-                finite |= x[j] > NEG_INF;
-                kmax = max(kmax, key_of(z[j]));
-            }
-    }
+    for_each_row_token<1>(lg, r.src, r.V, r.nch, [&](int, float x, float o) {
+        bad |= !(x < __builtin_inff());
+        finite |= x > NEG_INF;
+        kmax = max(kmax, key_of(penalise(x, o, r)));
+    });
     bad = __syncthreads_or(bad);
     finite = __syncthreads_or(finite);
-    const float top = z_of((unsigned)block_max(kmax, sh.red));
+    const float top = z_of((unsigned)block_reduce<false>(kmax, sh.red));
     if (poisoned || bad || !finite || !(top > NEG_INF)) {
         if (tid == 0) {
             a.tokens[s] = -1;
@@ -241,7 +137,7 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
             const u64 v = ((u64)key_of(repeat_penalty(z, o, r)) << 32) | (0xffffffffu - (unsigned)n);
             best = v > best ? v : best;
         });
-        token = (int)(0xffffffffu - (unsigned)block_max(best, sh.red));
+        token = (int)(0xffffffffu - (unsigned)block_reduce<false>(best, sh.red));
     } else {
         // ---- radix selection, 8 bits a pass: key_p = the largest key whose mass {key >= key_p} reaches top_p of the total, key_k = the
         // k-th largest key.  A pass adds to the histograms only the tokens that match the digits found so far.
@@ -251,7 +147,7 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
             const int shift = 24 - 8 * pass;
             if (tid < 256) sh.hist_p[tid] = sh.hist_k[tid] = 0;
             __syncthreads();
-            Run run_p, run_k;
+            Run<u64> run_p, run_k;
             for_each_token(lg, r, [&](int, float z, float) {
                 const unsigned key = key_of(z), digit = (key >> shift) & 255u;
                 if (use_p && (pass == 0 || (key ^ key_p) >> (shift + 8) == 0)) run_p.add(sh.hist_p, digit, weight(z, top, 1.f));
@@ -266,42 +162,25 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
                     const double t = ceil((double)top_p * (double)S);
                     target_p = t >= (double)S ? S : (u64)t;
                 }
-                const Pick p = select_bin(sh.hist_p, above_p, target_p);
+                const Pick<u64> p = select_bin(sh.hist_p, above_p, target_p);
                 if (lane == 0) sh.pick_p = p;
             }
             if (wave == 1 && use_k) {
-                const Pick p = select_bin(sh.hist_k, above_k, (u64)k);
+                const Pick<u64> p = select_bin(sh.hist_k, above_k, (u64)k);
                 if (lane == 0) sh.pick_k = p;
             }
             __syncthreads();
             if (use_p) { key_p |= sh.pick_p.digit << shift; above_p = sh.pick_p.above; }
             if (use_k) { key_k |= sh.pick_k.digit << shift; above_k = sh.pick_k.above; equal_k = sh.pick_k.equal; }
         }
-        // ---- ties at the top-k boundary: of the equal_k tokens at key_k the k - above_k lowest ids stay.  Where that is not all of them,
-        // the same selection over 65535 - n (two passes) finds the last id that stays.
+        // ---- ties at the top-k boundary: of the equal_k tokens at key_k the k - above_k lowest ids stay (tie_cut)
         unsigned rid_cut = 0;                                 // tokens at key_k stay while 65535 - n >= rid_cut
-        if (use_k && (u64)k - above_k < equal_k) {
-            u64 above_id = 0;
-            for (int pass = 0; pass < 2; ++pass) {
-                const int shift = 8 - 8 * pass;
-                if (tid < 256) sh.hist_k[tid] = 0;
-                __syncthreads();
-                Run run;
+        if (use_k && (u64)k - above_k < equal_k)
+            rid_cut = tie_cut(sh.hist_k, &sh.pick_k, (u64)k - above_k, [&](auto at) {
                 for_each_token(lg, r, [&](int n, float z, float) {
-                    const unsigned rid = 65535u - (unsigned)n;
-                    if (key_of(z) == key_k && (pass == 0 || (rid ^ rid_cut) >> 8 == 0)) run.add(sh.hist_k, (rid >> shift) & 255u, 1);
+                    if (key_of(z) == key_k) at(n);
                 });
-                run.flush(sh.hist_k);
-                __syncthreads();
-                if (wave == 0) {
-                    const Pick p = select_bin(sh.hist_k, above_id, (u64)k - above_k);
-                    if (lane == 0) sh.pick_k = p;
-                }
-                __syncthreads();
-                rid_cut |= sh.pick_k.digit << shift;
-                above_id = sh.pick_k.above;
-            }
-        }
+            });
         const auto kept = [&](int n, float z) {
             const unsigned key = key_of(z);
             return key >= key_p && (!use_k || key > key_k || (key == key_k && 65535u - (unsigned)n >= rid_cut));
@@ -312,14 +191,14 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
         for_each_token(lg, r, [&](int n, float z, float o) {
             if (kept(n, z)) { ktop = max(ktop, key_of(repeat_penalty(z, o, r))); nmax = (unsigned)n + 1; }
         });
-        top_kept = z_of((unsigned)block_max(ktop, sh.red));
-        const int last_kept = (int)block_max(nmax, sh.red) - 1;
+        top_kept = z_of((unsigned)block_reduce<false>(ktop, sh.red));
+        const int last_kept = (int)block_reduce<false>(nmax, sh.red) - 1;
 
         // ---- pass D: W, kept per block of 512 consecutive tokens (one wave, one round) for the draw
         if (tid < PARTS) sh.part[tid] = 0;
         if (tid == 0) { sh.block = -1; sh.token = last_kept; }
         __syncthreads();
-        const int rounds = (r.nch + THREADS - 1) / THREADS;
+        const int rounds = (r.nch + ROW_THREADS - 1) / ROW_THREADS;
         const auto chunk_weights = [&](int c, u64 (&w)[8]) {
             float z[8], o[8];
             load_chunk(lg, r, c, z, o);
@@ -328,7 +207,7 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
                 w[j] = 8 * c + j < r.V && kept(8 * c + j, z[j]) ? weight(repeat_penalty(z[j], o[j], r), top_kept, temperature) : 0;
         };
         for (int i = 0; i < rounds; ++i) {
-            const int c = tid + THREADS * i;
+            const int c = tid + ROW_THREADS * i;
             u64 w[8], sum = 0;
             if (c < r.nch) {
                 chunk_weights(c, w);
@@ -336,7 +215,7 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
                 for (int j = 0; j < 8; ++j) sum += w[j];
             }
             sum = wave_sum(sum);
-            if (lane == 0) sh.part[i * WAVES + wave] = sum;
+            if (lane == 0) sh.part[i * ROW_WAVES + wave] = sum;
         }
         __syncthreads();
         // ---- the draw, in token-id order: wave 0 finds the block of 512 tokens in which the CDF passes u W, that block's wave the token
@@ -358,8 +237,8 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
         }
         __syncthreads();
         W = sh.red[0]; target = sh.red[1];
-        if (sh.block >= 0 && wave == (sh.block & (WAVES - 1))) {
-            const int c = tid + THREADS * (sh.block / WAVES);
+        if (sh.block >= 0 && wave == (sh.block & (ROW_WAVES - 1))) {
+            const int c = tid + ROW_THREADS * (sh.block / ROW_WAVES);
             u64 w[8] = {}, sum = 0;
             if (c < r.nch) chunk_weights(c, w);
 #pragma unroll
@@ -400,7 +279,7 @@ __global__ void __launch_bounds__(THREADS) sample_slots_kernel(const SampleArgs 
 
     // ---- the update: dst = o * alpha_decay, + 1 at the token; columns >= V are not touched
     if (dst == nullptr) return;
-    for (int c = tid; c < r.nch; c += THREADS) {
+    for (int c = tid; c < r.nch; c += ROW_THREADS) {
         float o[8];
         if (r.src) load8<float>(r.src + 8 * c, o);
 #pragma unroll
@@ -425,7 +304,7 @@ hipError_t launch_sample_slots(const SampleArgs& a, int io, hipStream_t st)
 {
     if (!(a.logits && a.occ && a.params && a.u && a.tokens)) return hipErrorInvalidValue;
     if (a.n_seq < 1 || a.n_slots < 1 || a.V < 1 || a.V > SAMPLE_MAX_V || a.ld < a.V || a.ld % 8) return hipErrorInvalidValue;
-    const dim3 grid(a.n_seq), block(THREADS);
+    const dim3 grid(a.n_seq), block(ROW_THREADS);
     if (io == IO_F32) return launch<sample_slots_kernel<float>>(grid, block, 0, st, a);
     if (io == IO_F16) return launch<sample_slots_kernel<f16_t>>(grid, block, 0, st, a);
     return launch<sample_slots_kernel<bf16_t>>(grid, block, 0, st, a);
@@ -445,9 +324,7 @@ static int sample_slots(int n_seq, int V, int ld, const void* logits, float* occ
     if (!slot && n_slots < n_seq) return WKV6_EINVAL;
     if (((uintptr_t)logits | (uintptr_t)occ_pool) & 15) return WKV6_EINVAL;
     if (((uintptr_t)slot | (uintptr_t)slot_out | (uintptr_t)params | (uintptr_t)u | (uintptr_t)tokens | (uintptr_t)logprob) & 3) return WKV6_EINVAL;
-    const uintptr_t lo = (uintptr_t)logits, oc = (uintptr_t)occ_pool;
-    const size_t lo_bytes = (size_t)n_seq * ld * (io == IO_F32 ? 4 : 2), oc_bytes = (size_t)n_slots * ld * 4;
-    if (logits && occ_pool && lo < oc + oc_bytes && oc < lo + lo_bytes) return WKV6_EINVAL;
+    if (overlap(logits, (size_t)n_seq * ld * (io == IO_F32 ? 4 : 2), occ_pool, (size_t)n_slots * ld * 4)) return WKV6_EINVAL;
     if (V > SAMPLE_MAX_V) return WKV6_EUNSUPPORTED;
     if (!logits || !occ_pool || !params || !u || !tokens) return WKV6_ENULL;
     SampleArgs a = {};
